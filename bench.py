@@ -2,9 +2,13 @@
 """Headline benchmark: pipeline evals/sec (osc + reweight + hist + LLH) on 1e7
 synthetic MC events (BASELINE.json metric).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
         --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+
+A plain run sets up, runs W warm-up steps, times exactly K steps (`ms_per_step`), writes the last
+step's outputs with --dump-outputs and prints the line.  Everything else described below -- the legs,
+the CPU baseline and LLH gate, the roofline's kernel timings, the weak-scaling rate -- runs with --full.
 
 One "step" = one template evaluation with fresh oscillation parameters (every
 stage recomputes, no memo hit; protocol of
@@ -23,8 +27,8 @@ is measured in the same run and reported as `weak_value`.
 
 Rank 0 prints, as its LAST stdout line, ONE compact JSON object below 4 KB: the contract's fields, `roofline`,
 `cpu_baseline`, the LLH gate and one number per leg (`compact_line`).  The full result goes to `bench_detail.json`
-beside this script (`--detail-out`) and, marked `bench_detail `, to stderr.  Besides the headline the full result
-carries, at N = 1, the `legs`:
+beside this script (`--detail-out`) and, marked `bench_detail `, to stderr.  Besides the headline the result of a
+--full run carries, at N = 1, the `legs`:
 bounded extra measurements of the same hot path (larger-than-L3 sample, the reference-order and
 the coordinate-form kernels, a 4 800-bin output binning, flux systematics moving every evaluation
 with the flux per event and on the oscillation grid, the evaluation through the Pipeline/cfg
@@ -99,11 +103,19 @@ def parse(argv=None):
                     help="do not call pisa_amd.warm_up() beside the generation of the sample: `setup.first_in_process` then includes "
                          "the runtime's first-use costs (code objects, staging buffers)")
     ap.add_argument("--cpu-baseline-worker", default=None, help=argparse.SUPPRESS)
-    ap.add_argument("--min-timed-s", type=float, default=0.2,
+    ap.add_argument("--min-timed-s", type=float, default=0.0,
                     help="repeat the block of --steps timed steps until this much timed work has been seen "
-                         "(0: exactly one block)")
+                         "(default 0: exactly one block, --steps timed steps)")
     ap.add_argument("--event-order", default="auto", choices=["auto", "node", "bin", "part"],
                     help="resident event order: sorted by calc-grid node, or by (output bin, node)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, everything else: the legs (--legs), the CPU baseline and the LLH gate against "
+                         "the oracle, the kernel and phase timings of the roofline, the second set-up, the unbinned-events "
+                         "probe, and with N > 1 the weak-scaling rate and the per-rank LLH bits.  Without it a run sets up, "
+                         "warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step handed its caller as float64 .npy files "
+                         "in DIR: llh.npy (the LLH read back) and hist.npy / sumw2.npy (the maps it was computed from)")
     return ap.parse_args(argv)
 
 
@@ -274,6 +286,18 @@ def launch_ranks(args, argv, standin):
     if line is not None and rc == 0:
         print(line, flush=True)
     return rc
+
+
+def dump_outputs(path, llh, maps=None):
+    """--dump-outputs: the LLH of the last timed step and, on the device, the maps it was computed from
+    (n_containers x n_bins each, a few kB), float64 -- two builds run with the same arguments compare file by file"""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "llh.npy"), np.array([llh], dtype=np.float64))
+    if maps is not None:
+        for name, a in zip(("hist", "sumw2"), maps):
+            np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def param_list(wl, n, **kw):
@@ -1379,6 +1403,9 @@ def main(argv=None, hooks=None):
     dev_sync = torch.cuda.synchronize if cuda else (lambda: None)
     if not cuda or share:
         args.no_kernel_timing = args.no_batch_probe = args.no_drop_probe = args.no_cpu_baseline = True
+    if not args.full:   # a plain run does what the headline needs: set-up, warm-up, the timed steps, the line
+        args.no_kernel_timing = args.no_batch_probe = args.no_drop_probe = args.no_cpu_baseline = True
+        args.legs = "none"
 
     n_e, n_cz = (int(v) for v in args.grid.split("x"))
     compact = not (args.exact_association or args.coordinate_form)
@@ -1442,7 +1469,7 @@ def main(argv=None, hooks=None):
             print("bench.py: pisa_amd.warm_up() failed (%s: %s)" % (type(exc).__name__, exc), file=sys.stderr)
     t_setup0 = time.perf_counter()
     st = make_state(wl, rank=rank, world_size=world, indexed=not args.coordinate_form,
-                    sort_events=order, compact=compact, index16=index16, **({"time_setup": True} if cuda else {}))
+                    sort_events=order, compact=compact, index16=index16, **({"time_setup": True} if cuda and args.full else {}))
     dev_sync()
     setup_first = {"wall_ms": 1e3 * (time.perf_counter() - t_setup0), "phases_ms": getattr(st, "setup_ms", None),
                    "after_warm_up": warm_ms is not None, "warm_up_ms": warm_ms}
@@ -1454,9 +1481,11 @@ def main(argv=None, hooks=None):
     mats_last = dict(wl.last_matrices)     # of plist[-1], the point whose LLH the line reports
     dt, llh = timed_loop(st, plist)
     headline_blocks = timed_loop.blocks
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, llh, st.maps() if cuda else None)
     # set-up a second time in the warm process (allocator grown, code objects loaded): host columns -> engine ready
     setup_warm = None
-    if cuda and not dist_on:
+    if cuda and not dist_on and args.full:
         t_setup0 = time.perf_counter()
         st_again = make_state(wl, rank=rank, world_size=world, indexed=not args.coordinate_form,
                               sort_events=order, compact=compact, index16=index16, time_setup=True)
@@ -1490,18 +1519,18 @@ def main(argv=None, hooks=None):
         st._maps_valid = False
         st._tail("llh", st.metric_out)
 
-    t_prob3 = time_phase(lambda: st.compute_probs(nominal)) if cuda else None
-    t_tail = time_phase(tail) if cuda else None
-    t_allreduce = time_phase(st.allreduce) if (dist_on and cuda) else None
+    t_prob3 = time_phase(lambda: st.compute_probs(nominal)) if (cuda and args.full) else None
+    t_tail = time_phase(tail) if (cuda and args.full) else None
+    t_allreduce = time_phase(st.allreduce) if (dist_on and cuda and args.full) else None
     n_comm = None
-    if dist_on and st._rccl:
+    if dist_on and st._rccl and args.full:
         n_comm = st._rccl.count()
         if n_comm != world:
             raise SystemExit("bench.py: the RCCL communicator spans %d rank(s), %d launched" % (n_comm, world))
     # the LLH of the last timed point as every rank holds it: integer limbs summed over the ranks, the tail
     # replicated -- the bits must be the same everywhere (north star: bit-reproducible across GPU counts)
     llh_bits = None
-    if dist_on:
+    if dist_on and args.full:
         import torch.distributed as dist
 
         mine = torch.tensor([int(np.float64(llh).view(np.int64))], dtype=torch.int64,
@@ -1514,7 +1543,7 @@ def main(argv=None, hooks=None):
 
     # ---- weak scaling beside it: every rank a sample of its own, limbs all-reduced, N samples per step
     weak = None
-    if dist_on:
+    if dist_on and (args.full or args.weak_scaling):
         wl_w = synthetic.Workload(n_events=int(args.events), grid=(n_e, n_cz), out_binning=args.binning, seed=rank)
         st_w = make_state(wl_w, rank=0, world_size=1, indexed=not args.coordinate_form,
                           sort_events=order, compact=compact, index16=index16)
@@ -1633,7 +1662,7 @@ def main(argv=None, hooks=None):
     if rank == 0:
         evals_per_s = args.steps / dt
         headline_weak = dist_on and args.weak_scaling
-        traffic, traffic_src = pmc_traffic(args) if not dist_on else (None, None)
+        traffic, traffic_src = pmc_traffic(args) if (args.full and not dist_on) else (None, None)
         out = {
             "metric": "pipeline evals/sec (osc+reweight+hist+LLH) on 1e7 MC events",
             "value": weak["value"] if headline_weak else evals_per_s,
@@ -1714,7 +1743,7 @@ def main(argv=None, hooks=None):
                 "traffic": traffic,
                 "traffic_source": traffic_src,
                 "timing": "HIP events recorded on the launch stream around the kernel, inside the library",
-                "by_kernel_trace": trace_roofline(args, bpe * st.n_local) if not dist_on else None,
+                "by_kernel_trace": trace_roofline(args, bpe * st.n_local) if (args.full and not dist_on) else None,
                 # the same kernel on 4 x the events (800 MB of columns: beyond the 256 MiB Infinity Cache, every byte from HBM):
                 # the HBM-true fraction beside `frac` (whose 200 MB of columns stay inside the Infinity Cache between launches)
                 "frac_beyond_l3": ((legs.get("l3_exceeding") or {}).get("roofline") or {}).get("frac"),

@@ -1,6 +1,6 @@
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 OUT=gpurun_out/coord_traffic; rm -rf $OUT; mkdir -p $OUT
-LEAN="--no-cpu-baseline --no-drop-probe --no-batch-probe --legs none"
+LEAN="--full --no-cpu-baseline --no-drop-probe --no-batch-probe --legs none"
 python3 bench.py $LEAN --coordinate-form --steps 100 2>/dev/null | python3 -c "
 import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('coord evals/s', round(d['value']), 'roofline', {k: d['roofline'][k] for k in ('achieved','frac','avg_launch_ms')})"
 for c in FETCH_SIZE WRITE_SIZE; do

@@ -1,5 +1,5 @@
 # Full measurement set of the default bench for profiles/<tag> (run on the GPU box):
-#   bench.json                  plain bench.py run (the judged line, with all legs)
+#   bench.json                  bench.py --full run (the headline line, with all legs)
 #   kernel_stats.csv            timeout 600 rocprofv3 --kernel-trace --stats of the headline loop (bench.py --legs none)
 #   kernels_by_phase.json       per-kernel mean over the timed loop from the same trace
 #   pmc_FETCH_SIZE.csv / pmc_WRITE_SIZE.csv   separate --pmc passes (bench.py --steps 3 --no-kernel-timing)
@@ -14,13 +14,13 @@ TAG=$1
 cd /tmp && export TMPDIR=/tmp
 OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG; rm -rf $OUT; mkdir -p $OUT
 cd $GRAFT_REPO_ROOT
-python3 bench.py > $OUT/bench.json 2> $OUT/bench.stderr
+python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.stderr
 tail -c 400 $OUT/bench.json
 cp bench_detail.json $OUT/bench_detail.json
 # every profiled run below: set-up uploads on the calling thread (counter-collecting profilers serialise dispatches and have
 # been seen to stall with several submitting host threads) -- set in this script's environment, never as a hop after `--`
 export PISA_HIP_UPLOAD_THREADS=0
-LEAN="--no-cpu-baseline --no-drop-probe --no-batch-probe --legs none"
+LEAN="--full --no-cpu-baseline --no-drop-probe --no-batch-probe --legs none"
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o bench -- python3 bench.py $LEAN > $OUT/bench_under_rocprof.json 2> $OUT/stats.log
 cp $OUT/stats/bench_kernel_stats.csv $OUT/kernel_stats.csv
 pmc_pair () {  # name, extra bench args
@@ -59,7 +59,7 @@ trace l3 python3 bench.py $LEAN --no-kernel-timing --steps 100 --events 4e7
 trace exact python3 bench.py $LEAN --no-kernel-timing --steps 200 --exact-association
 trace coord python3 bench.py $LEAN --no-kernel-timing --steps 100 --coordinate-form
 trace fine python3 bench.py $LEAN --no-kernel-timing --steps 200 --binning fine3d
-trace update_flux python3 bench.py --no-cpu-baseline --no-drop-probe --no-batch-probe --no-kernel-timing --steps 50 --legs update_flux
+trace update_flux python3 bench.py --full --no-cpu-baseline --no-drop-probe --no-batch-probe --no-kernel-timing --steps 50 --legs update_flux
 trace events_c2 python3 scripts/bench_events.py --events 1e6 --steps 20
 trace events_c5 python3 scripts/bench_events.py --events 1.25e7 --nsi --steps 6
 trace events_c5_full python3 scripts/bench_events.py --events 1e8 --nsi --steps 3 --on-device

@@ -359,7 +359,7 @@ def _bench_worker(rank, world, port, out_path):
     import bench
 
     got = {}
-    bench.main(["--gpus", str(world), "--events", "360", "--steps", "3", "--warmup", "1", "--min-timed-s", "0",
+    bench.main(["--gpus", str(world), "--full", "--events", "360", "--steps", "3", "--warmup", "1", "--min-timed-s", "0",
                 "--grid", "12x8", "--legs", "all"],
                hooks=dict(device_state=_make_bench_state, legs=("multi_point", "point_parallel", "fit_c4_engine"), result=got.update))
     if rank == 0:
@@ -472,6 +472,51 @@ def test_point_groups_deal_points_and_keep_the_single_rank_bits(tmp_path, n_grou
     assert [pg.block(7, g) for g in range(2)] == [(0, 3), (3, 7)]
 
 
+def test_bench_plain_run_times_exactly_the_steps_and_dumps_the_last_one(tmp_path):
+    """`bench.py` without --full on one rank (host stand-in engine): the pseudo-data, W warm-up and exactly K timed
+    evaluations reach the engine and nothing else does; `ms_per_step` is the time of that one block per step; the
+    extras of --full are absent; --dump-outputs writes the LLH of the last timed step, the same on a second run"""
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    import bench
+    from pisa_amd import synthetic
+
+    def run(out_dir):
+        evals, got = [], {}
+
+        def make_state(wl, **kw):
+            st = _make_bench_state(wl, **kw)
+            inner = st.eval_host
+
+            def counted(params, kind="llh"):
+                evals.append(params)
+                return inner(params, kind)
+
+            st.eval_host = counted
+            return st
+
+        bench.main(["--events", "360", "--steps", "7", "--warmup", "2", "--grid", "12x8", "--detail-out", "-",
+                    "--dump-outputs", str(out_dir)], hooks=dict(device_state=make_state, result=got.update))
+        return evals, got
+
+    evals, line = run(tmp_path / "a")
+    assert len(evals) == 1 + 2 + 7
+    assert line["steps"] == 7 and line["warmup"] == 2 and line["timed_blocks"] == 1
+    assert abs(line["value"] * line["ms_per_step"] * 1e-3 - 1.0) < 1e-9
+    assert line["legs"] == {} and "cpu_baseline" not in line and line["weak"] is None
+    assert line["unbinned_events_dropped"] is None and line["setup"]["warm_process"] is None
+    llh = np.load(str(tmp_path / "a" / "llh.npy"))
+    assert llh.dtype == np.float64 and llh.tolist() == [line["last_llh"]]
+    wl = synthetic.Workload(n_events=360, grid=(12, 8), out_binning="dragon", seed=0)
+    single = _make_bench_state(wl)
+    single.make_pseudo_data(wl.osc_params(), seed=0)
+    assert single.eval_host(bench.param_list(wl, 9)[-1], "llh") == line["last_llh"]
+    run(tmp_path / "b")
+    assert np.load(str(tmp_path / "b" / "llh.npy")).tolist() == llh.tolist()
+
+
 def bench_hooks():
     """what `PISA_BENCH_HOOKS=tests.test_distributed_cpu:bench_hooks` hands to bench.main in every rank"""
     return dict(device_state=_make_bench_state, legs=("multi_point",))
@@ -488,7 +533,7 @@ def test_bench_gpus_2_launches_its_own_ranks(tmp_path):
     import time
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--events", "360", "--steps", "3",
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--full", "--events", "360", "--steps", "3",
            "--warmup", "1", "--min-timed-s", "0", "--grid", "12x8", "--legs", "multi_point",
            "--detail-out", str(tmp_path / "detail.json")]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}

@@ -31,7 +31,7 @@ def _bench(gpus, hooks=True, legs="none"):
     import tempfile
 
     detail = os.path.join(tempfile.mkdtemp(prefix="pisa_bench_"), "detail.json")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--events", "2400000", "--steps", "6",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--full", "--events", "2400000", "--steps", "6",
            "--warmup", "2", "--min-timed-s", "0", "--legs", legs, "--no-cpu-baseline", "--no-drop-probe", "--no-batch-probe",
            "--detail-out", detail]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}

@@ -400,7 +400,7 @@ def test_bench_multi_rank_code_path_on_one_rank(tmp_path):
         port = sk.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(root, "bench.py"),
-           "--gpus", "1", "--force-dist", "--events", "1.2e6", "--steps", "40", "--warmup", "5",
+           "--gpus", "1", "--force-dist", "--full", "--events", "1.2e6", "--steps", "40", "--warmup", "5",
            "--no-cpu-baseline", "--no-drop-probe", "--legs", "multi_point,fit_c4_engine,l3_exceeding",
            "--detail-out", str(tmp_path / "detail.json")]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
@@ -615,7 +615,7 @@ def test_bench_line_contract_single_gpu(tmp_path):
     import sys
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--events", "1.2e6", "--steps", "30", "--warmup", "5",
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--full", "--events", "1.2e6", "--steps", "30", "--warmup", "5",
            "--legs", "none", "--no-drop-probe", "--no-batch-probe", "--detail-out", str(tmp_path / "detail.json")]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -638,6 +638,35 @@ def test_bench_line_contract_single_gpu(tmp_path):
     assert c["value"] < d["value"]
     assert abs(c["llh_rel_diff"]) < 1e-9 and d["llh_gate"]["referee_met"] is True
     assert "thread_scan" in detail["cpu_baseline"] and "thread_scan" not in c
+
+
+def test_bench_plain_run_and_its_outputs(tmp_path):
+    """`python bench.py` without --full: the contract's line over exactly --steps timed steps, none of the extras; twice
+    with --dump-outputs, the same float64 outputs bit for bit: the LLH of the last timed step (the line's `last_llh`)
+    and the maps it was computed from"""
+    import os
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    outs = []
+    for run in ("a", "b"):
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--events", "1.2e6", "--steps", "12", "--warmup", "3",
+               "--detail-out", str(tmp_path / ("detail_%s.json" % run)), "--dump-outputs", str(tmp_path / run)]
+        out = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=root)
+        assert out.returncode == 0, out.stderr[-2000:]
+        d, detail = bench_result(out.stdout, str(tmp_path / ("detail_%s.json" % run)))
+        assert d["steps"] == 12 and d["warmup"] == 3 and d["timed_blocks"] == 1 and d["n_gpus"] == 1
+        assert d["unit"] == "evals/s" and d["higher_is_better"] is True and d["dtype"] == "f64"
+        assert abs(d["value"] * d["ms_per_step"] * 1e-3 - 1.0) < 1e-6
+        assert "cpu_baseline" not in d and d["legs_run"] == [] and detail["setup"]["warm_process"] is None
+        got = {k: np.load(str(tmp_path / run / (k + ".npy"))) for k in ("llh", "hist", "sumw2")}
+        assert all(a.dtype == np.float64 for a in got.values())
+        assert got["llh"].tolist() == [detail["last_llh"]]
+        assert got["hist"].shape == got["sumw2"].shape == (12, 128) and got["hist"].sum() > 0
+        outs.append(got)
+    for k in outs[0]:
+        np.testing.assert_array_equal(outs[0][k], outs[1][k])
 
 
 @pytest.mark.parametrize("index16", [True, False])
