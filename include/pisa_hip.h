@@ -687,6 +687,54 @@ int pisa_hip_kde_configure(int32_t use_expansion);
 #define PISA_HIP_METRIC_MCLLH_EFF 7             /* stats.py:384-438 (a = 1) */
 #define PISA_HIP_METRIC_CONV_LLH 8              /* stats.py:440-596 */
 
+/* The generalized Poisson-gamma likelihood (stats.py:792-879, arXiv:1902.08831 eq. 91): the identifier of the kind
+ * in the bindings.  pisa_hip_metric / pisa_hip_finalize_metric* do NOT accept it (it needs per-container alpha, beta
+ * and MC counts, and a workgroup per bin): its entry points are pisa_hip_generalized_poisson_llh and
+ * pisa_hip_finalize_gpllh below. */
+#define PISA_HIP_METRIC_GENERALIZED_POISSON_LLH 9
+/* mixture bins keep their recursion (2 (k + 1) doubles) in LDS up to this data count, beyond it in d_scratch */
+#define PISA_HIP_GPLLH_LDS_K 1536
+#define PISA_HIP_GPLLH_MAX_CONTAINERS 1024
+
+/* generalized_llh_params (stages/likelihood): Sigma w and Sigma w^2 of the events of every bin, the events of
+ * bin b being d_weights[d_index[d_offsets[b] .. d_offsets[b + 1])] (a bin's list may share events with another's).
+ * d_status = PISA_HIP_ERR_NEGATIVE if a listed weight is negative. */
+int pisa_hip_gpllh_bin_sums(const double *d_weights, const int64_t *d_index, const int64_t *d_offsets,
+                            int64_t n_bins, double *d_sumw, double *d_sumw2, int32_t *d_status, void *stream);
+
+/* generalized_llh_params.apply_function per (container, bin), all arrays [n_containers][n_bins] but
+ * d_adjust[n_containers] (the containers' mean adjustments): an empty bin (n_mc = 0) gets one pseudo-weight
+ * 0.001; mean = Sigma w / n, var_z = Sigma w^2 / n; beta = mean / var_z, alpha = (n + adj) mean^2 / var_z
+ * (var_z = 0: beta = 1, alpha = (n + adj) 0.001).  d_weights: the weight sums with the pseudo-weight.
+ * d_status = PISA_HIP_ERR_NEGATIVE for a negative input. */
+int pisa_hip_gpllh_params(const double *d_sumw, const double *d_sumw2, const double *d_n_mc, const double *d_adjust,
+                          int32_t n_containers, int64_t n_bins, double *d_alpha, double *d_beta, double *d_weights,
+                          int32_t *d_status, void *stream);
+
+/* generalized_poisson_llh per bin (d_per_bin[n_bins], required) and its plain sum (d_total[1]), from
+ * d_weights / d_alpha / d_beta / d_n_mc [n_containers][n_bins] and the data d_actual[n_bins] (k = (int64) data).
+ * d_empty[n_bins] (uint8, may be NULL): the bins of the reference's `empty_bins`.  A mixture bin with data count
+ * k needs k <= scratch_k; for scratch_k > PISA_HIP_GPLLH_LDS_K, d_scratch holds n_bins * 2 (scratch_k + 1)
+ * doubles.  d_status: PISA_HIP_ERR_NEGATIVE (negative data or weights), PISA_HIP_ERR_INVALID (alpha or beta
+ * <= 0, k > scratch_k).  d_done[1] (uint32, zero before the first call): the arrival counter of the fixed-order
+ * reduction of the total, left at zero again; calls that may run concurrently need counters of their own. */
+int pisa_hip_generalized_poisson_llh(const double *d_actual, const double *d_weights, const double *d_alpha,
+                                     const double *d_beta, const double *d_n_mc, int32_t n_containers, int64_t n_bins,
+                                     const uint8_t *d_empty, double *d_scratch, int64_t scratch_k, double *d_per_bin,
+                                     uint32_t *d_done, double *d_total, int32_t *d_status, void *stream);
+
+/* The fused tail of an evaluation with the generalized likelihood, n_points sets of limbs (as
+ * pisa_hip_finalize_metric_multi): pisa_hip_hist_finalize + pisa_hip_gpllh_params (d_n_mc [n_containers][n_bins],
+ * d_adjust [n_containers], fixed at set-up) + pisa_hip_generalized_poisson_llh in ONE launch, bit for bit the
+ * same values.  d_per_bin [n_points][n_bins]; d_scratch: n_points * n_bins * 2 (scratch_k + 1) doubles when
+ * scratch_k > PISA_HIP_GPLLH_LDS_K; d_done[n_points] as in pisa_hip_generalized_poisson_llh; total[n_points]. */
+int pisa_hip_finalize_gpllh(int64_t *d_limbs, int32_t n_points, int32_t n_containers, int64_t n_bins,
+                            double *d_hist, double *d_sumw2, const double *d_actual, const double *d_n_mc,
+                            const double *d_adjust, const uint8_t *d_empty, double *d_per_bin, double *d_scratch,
+                            int64_t scratch_k, uint32_t *d_done, double *total, int32_t *d_status,
+                            int32_t *d_metric_status,
+                            int32_t clear_limbs, void *stream);
+
 /* Map.metric / metric_total (pisa/core/map.py:1572-1604): per-bin metric of
  * (actual, expected[, sigma2]) and its nansum.  If n_maps > 1 the expectation
  * and variance are first summed over maps in index order

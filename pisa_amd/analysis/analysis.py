@@ -49,8 +49,8 @@ class HypoFitResult:
     def get_detailed_metric_info(data_dist, hypo_maker, hypo_asimov_dist, params, metric, other_metrics=None,
                                  detector_name=None, include_maps_binned=False):
         """per metric (the fit's and `other_metrics`): its value map by map, the priors' penalties parameter by
-        parameter and, if asked for, the per-bin values as maps (analysis.py:373-459; generalized_poisson_llh and
-        weighted_chi2 are not built)"""
+        parameter and, if asked for, the per-bin values as maps (analysis.py:373-459; weighted_chi2 is not built,
+        generalized_poisson_llh is `Map.generalized_poisson_llh` and not a metric of this call)"""
         from pisa_amd.core.map import Map, MapSet
 
         others = [] if other_metrics is None else ([other_metrics] if isinstance(other_metrics, str) else list(other_metrics))

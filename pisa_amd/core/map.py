@@ -20,7 +20,8 @@ from pisa_amd.core.binning import MultiDimBinning, OneDimBinning, _round_sig
 
 __all__ = ["Map", "MapSet", "ALL_METRICS", "rebin"]
 
-# stats.py:43-51 without barlow_llh, generalized_poisson_llh and weighted_chi2 (not built)
+# stats.py:43-51 without barlow_llh and weighted_chi2 (not built) and generalized_poisson_llh (its own method:
+# `Map.generalized_poisson_llh`, it takes the containers' maps rather than one expectation)
 ALL_METRICS = ("llh", "poisson_llh", "conv_llh", "mcllh_mean", "mcllh_eff", "chi2", "mod_chi2", "correct_chi2",
                "signed_sqrt_mod_chi2")
 FLUCTUATE_METHODS = ("poisson", "scaled_poisson", "gauss", "gauss+poisson")
@@ -597,6 +598,15 @@ class Map:
 
     def conv_llh(self, expected_values, binned=False):
         return self.metric(expected_values, "conv_llh", binned)
+
+    def generalized_poisson_llh(self, expected_values=None, empty_bins=None, binned=False):
+        """the generalized Poisson-gamma likelihood of this map's counts (map.py:1667-1691): `expected_values` an
+        OrderedDict of MapSets ("weights", "llh_alphas", "llh_betas", "n_mc_events"; see
+        `stats.generalized_poisson_llh`); the flat per-bin values if `binned`, else their sum"""
+        from pisa_amd.utils import stats
+
+        total, per_bin = stats.generalized_poisson_total(self.hist, expected_values, empty_bins)
+        return per_bin if binned else total
 
     def __repr__(self):
         if self._lazy is not None:

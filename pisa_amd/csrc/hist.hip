@@ -31,6 +31,7 @@
 
 #include "common.hpp"
 #include "metric_device.hpp"
+#include "gpllh_device.hpp"
 
 namespace pisa {
 
@@ -1819,6 +1820,78 @@ PISA_API int pisa_hip_hist_finalize(const int64_t *d_limbs, int32_t n_containers
     hipLaunchKernelGGL(hist_finalize_kernel, grid, block, 0, as_stream(stream),
                        (const long long *)d_limbs, total, d_hist, d_sumw2, d_status);
     PISA_CHECK_LAUNCH("hist_finalize_kernel");
+    return PISA_HIP_OK;
+}
+
+// The fused tail of an evaluation with the generalized Poisson-gamma likelihood: limbs -> maps (written as
+// histogrammed, limbs cleared) -> alpha, beta of every container (gpllh_params) -> the bin (gpllh_bin) -> the total
+// (gpllh_publish_and_total).  One 64-thread workgroup per (bin, point): the same values, in the same order, as
+// pisa_hip_hist_finalize + pisa_hip_gpllh_params + pisa_hip_generalized_poisson_llh.
+__global__ void __launch_bounds__(64)
+finalize_gpllh_kernel(long long *__restrict__ limbs, int n_cont, int n_bins, double *__restrict__ hist,
+                      double *__restrict__ q1, const double *__restrict__ actual, const double *__restrict__ n_mc,
+                      const double *__restrict__ adjust, const uint8_t *__restrict__ empty,
+                      double *__restrict__ per_bin, double *__restrict__ scratch, int64_t cap,
+                      unsigned int *__restrict__ done, double *__restrict__ total, int32_t *__restrict__ status, int32_t *__restrict__ mstatus,
+                      int clear, int64_t limb_stride) {
+    extern __shared__ __attribute__((aligned(16))) double s_tab[];   // [4][n_cont] + s, delta
+    const int b = blockIdx.x, pt = blockIdx.y;
+    const int64_t n_tot = (int64_t)n_cont * n_bins;
+    limbs += pt * limb_stride;
+    hist += pt * n_tot;
+    q1 += pt * n_tot;
+    double *c_w = s_tab, *c_a = s_tab + n_cont, *c_b = s_tab + 2 * n_cont, *c_n = s_tab + 3 * n_cont;
+    bool ovf = false, neg = false;
+    for (int c = threadIdx.x; c < n_cont; c += 64) {
+        const int64_t i = (int64_t)c * n_bins + b;
+        long long *L = limbs + i * 2 * NL;
+        const double sw = limbs_to_double(L, ovf), sw2 = limbs_to_double(L + NL, ovf);
+        if (clear) {
+#pragma unroll
+            for (int k = 0; k < 2 * NL; k++) L[k] = 0;
+        }
+        hist[i] = sw;
+        q1[i] = sw2;
+        const double n = n_mc[i];
+        neg = gpllh_params(sw, sw2, n, adjust[c], c_a[c], c_b[c], c_w[c]) || neg;
+        c_n[c] = n;
+    }
+    if (ovf && status) atomicOr(status, 1);
+    if (neg) mstatus[0] = PISA_HIP_ERR_NEGATIVE;
+    __syncthreads();
+    const double kd = actual[b];
+    const int64_t lds_k = gpllh_lds_k(cap);
+    double *sbuf = s_tab + 4 * n_cont;
+    int64_t bcap = lds_k;
+    if (kd > (double)lds_k && scratch) {
+        sbuf = scratch + ((int64_t)pt * n_bins + b) * 2 * (cap + 1);
+        bcap = cap;
+    }
+    int err = 0;
+    const double v = gpllh_bin(kd, empty && empty[b], n_cont, c_w, c_a, c_b, c_n, sbuf, bcap, err);
+    if (err && threadIdx.x == 0) mstatus[0] = err;
+    gpllh_publish_and_total(v, b, n_bins, per_bin + (int64_t)pt * n_bins, done + pt, total + pt);
+}
+
+PISA_API int pisa_hip_finalize_gpllh(int64_t *d_limbs, int32_t n_points, int32_t n_containers, int64_t n_bins,
+                                     double *d_hist, double *d_sumw2, const double *d_actual, const double *d_n_mc,
+                                     const double *d_adjust, const uint8_t *d_empty, double *d_per_bin,
+                                     double *d_scratch, int64_t scratch_k, uint32_t *d_done, double *total,
+                                     int32_t *d_status,
+                                     int32_t *d_metric_status, int32_t clear_limbs, void *stream) {
+    if (!d_limbs || !d_hist || !d_sumw2 || !d_actual || !d_n_mc || !d_adjust || !d_per_bin || !d_done || !total ||
+        !d_metric_status || n_containers < 1 || n_containers > PISA_HIP_GPLLH_MAX_CONTAINERS || n_bins < 1 ||
+        n_bins > 0x7FFFFFFF || n_points < 1 || n_points > PISA_HIP_MAX_POINTS || scratch_k < 0)
+        return PISA_HIP_ERR_INVALID;
+    if (scratch_k > PISA_HIP_GPLLH_LDS_K && !d_scratch) return PISA_HIP_ERR_INVALID;
+    const int64_t limb_stride = (int64_t)n_containers * n_bins * 2 * NL;
+    hipLaunchKernelGGL(finalize_gpllh_kernel, dim3((unsigned)n_bins, (unsigned)n_points), dim3(64),
+                       gpllh_lds_bytes(n_containers, scratch_k), as_stream(stream), (long long *)d_limbs,
+                       (int)n_containers, (int)n_bins, d_hist, d_sumw2, d_actual, d_n_mc, d_adjust, d_empty,
+                       d_per_bin, scratch_k > PISA_HIP_GPLLH_LDS_K ? d_scratch : nullptr, scratch_k, (unsigned int *)d_done, total,
+                       d_status,
+                       d_metric_status, (int)clear_limbs, limb_stride);
+    PISA_CHECK_LAUNCH("finalize_gpllh_kernel");
     return PISA_HIP_OK;
 }
 

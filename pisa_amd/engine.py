@@ -537,6 +537,9 @@ def configured_points():
     return _POINT_GROUPS["obj"]
 
 
+GPLLH = K.GPLLH
+
+
 class HotPathEngine:
     """See module docstring.  `containers` is a list of dicts with keys
     name, flav, nubar, true_energy, true_coszen, nu_flux[n,2], weighted_aeff,
@@ -611,6 +614,10 @@ class HotPathEngine:
         self.index16 = index16
         self.n_local = 0
         shards = local_slices([len(c["true_energy"]) for c in containers], rank, world_size)
+        # MC events per output bin of every container's shard (all of them, those the resident order leaves out
+        # included: the reference's bin masks count them), counted where the events are digitised; read only by
+        # `configure_gpllh`
+        self._n_mc_local, self._gpllh = [], None
         # workgroups the fused kernel will give each container (a layout hint for the partitioned order)
         import ctypes as C
 
@@ -708,6 +715,7 @@ class HotPathEngine:
                     # divergence in the layer loop)
                     e_true = e_col
                     obin = K.event_indices(cols, out_binning)
+                    self._n_mc_local.append(self._bin_counts(obin))
                     if sort_events and hi - lo > 1:
                         perm = torch.argsort(cz, stable=True)
                         gx, gy, flux_d, aeff_d, w0_d, e_true, cz = (
@@ -728,6 +736,7 @@ class HotPathEngine:
                     # coordinates never change between evaluations: digitise once
                     node = K.event_indices([gx, gy], grid.binning)
                     obin = K.event_indices(cols, out_binning)
+                    self._n_mc_local.append(self._bin_counts(obin))
                     _phase("digitise")
                     if sort_events and hi - lo > 1:
                         # Event order inside a container is arbitrary and the exact
@@ -790,6 +799,8 @@ class HotPathEngine:
                         node, obin = node[perm].contiguous(), obin[perm].contiguous()
                         self.n_local += int(perm.numel()) - d.n_events
                         d.n_events = int(perm.numel())
+                if not indexed and not self.osc_events:
+                    self._n_mc_local.append(self._bin_counts(K.event_indices(cols, out_binning)))
                 if not indexed and not self.osc_events and sort_events and hi - lo > 1 and not self.node_flux:
                     # coordinate form (both digitisations in the kernel, 72 B/event): the resident ORDER is still
                     # free, so the events are stored sorted by the calc-grid node they will fall on -- digitised here once, for
@@ -1279,7 +1290,7 @@ class HotPathEngine:
     def _split_ok(self, kind):
         """the tail in its four-workgroup form (partial sums joined here): whenever the value is polled from
         pinned memory anyway; not for chi2 (its all-bins-equal rule, stats.py:160-161, needs every bin)"""
-        return self.split_tail and self.spin_wait > 0 and kind != "chi2"
+        return self.split_tail and self.spin_wait > 0 and kind not in ("chi2", GPLLH)
 
     TAIL_PARTS = 16   # workgroups of the split tail (`pisa_hip_finalize_metric_parts`)
 
@@ -1312,6 +1323,13 @@ class HotPathEngine:
         `scale` [n_cont, n_bins] / `extra` [2, n_bins] (device tensors): per-bin factors of a stage after
         the histogram and maps of other pipelines added to the template
         (`pisa_hip_finalize_metric_scaled`); only with the fused tail (`can_fuse_tail()`)."""
+        if kind == GPLLH:
+            if scale is not None or extra is not None:
+                raise ValueError("generalized_poisson_llh: no post-histogram scale or added maps in the tail "
+                                 "(alpha and beta are formed from the histogrammed sums)")
+            self._tail(kind, self.metric_host)
+            torch.cuda.current_stream().synchronize()
+            return float(self.metric_host[0])
         if self.can_fuse_tail():
             import ctypes as C
 
@@ -1370,6 +1388,9 @@ class HotPathEngine:
         One launch (`pisa_hip_finalize_metric`, which also leaves the limbs zeroed
         for the next accumulate) when a single workgroup can hold the maps; the
         separate finalize and metric kernels otherwise.  Same bits either way."""
+        if kind == GPLLH:
+            self._gpllh_tail(out)
+            return out
         if (self.fused_tail and not self._maps_valid
                 and len(self.cont) * self.n_bins <= K.FINALIZE_METRIC_MAX):
             K.finalize_metric(self.ws, kind, self.data, out, self.metric_status, clear_limbs=True)
@@ -1403,7 +1424,7 @@ class HotPathEngine:
                 and self.data is not None
                 and len(self.cont) * self.n_bins <= K.FINALIZE_METRIC_MAX):
             if self.spin_wait:
-                ev = self._evaluator_for() if self.one_call else None
+                ev = self._evaluator_for() if self.one_call and kind != GPLLH else None
                 if ev is not None:
                     return self._eval_one_call(ev, params, kind)
                 # The tail kernel's store into pinned host memory is visible a few us before the
@@ -1467,7 +1488,9 @@ class HotPathEngine:
         self._limbs_zero = self._maps_valid = False
         if rc == 0:
             self.allreduce()
-            if split:
+            if kind == GPLLH:
+                rc = self._gpllh_launch(1, a["limbs"], a["hist"], a["sumw2"], a["out"], s)
+            elif split:
                 rc = lib.pisa_hip_finalize_metric_parts(a["limbs"], 1, a["n_cont"], self.n_bins, a["hist"],
                                                         a["sumw2"], K.METRIC_KIND[kind], a["data"], None, 0, None,
                                                         a["out"], self.TAIL_PARTS, a["status"], a["mstatus"], 1, s)
@@ -1644,6 +1667,16 @@ class HotPathEngine:
         lib, s = _lib.lib(), K._stream()
         h = w["host_np"]
         h[:] = np.nan
+        if kind == GPLLH:
+            _lib.check(self._gpllh_launch(n, C.c_void_p(w["limbs"].data_ptr()), C.c_void_p(w["hist"].data_ptr()),
+                                          C.c_void_p(w["sumw2"].data_ptr()), C.c_void_p(w["host"].data_ptr()), s))
+            w["zero"] = True
+            h = h[:n]
+            for _ in range(self.spin_wait):
+                if not np.isnan(h).any():
+                    return [float(v) for v in h]
+            torch.cuda.current_stream().synchronize()
+            return [float(v) for v in h]
         if self._split_ok(kind):
             _lib.check(lib.pisa_hip_finalize_metric_split(
                 C.c_void_p(w["limbs"].data_ptr()), n, len(self.cont), self.n_bins, C.c_void_p(w["hist"].data_ptr()),
@@ -1671,6 +1704,100 @@ class HotPathEngine:
                 return [float(v) for v in h]
         torch.cuda.current_stream().synchronize()
         return [float(v) for v in h]
+
+    # -- the generalized Poisson-gamma likelihood (kind "generalized_poisson_llh") -----------------------
+    def configure_gpllh(self, empty_bins=None):
+        """count the MC events of every container in every output bin once (all events of the container, those
+        the resident order leaves out included, as the reference's bin masks count them; the ranks' counts
+        all-reduced), form the mean adjustments (generalized_llh_params setup) and upload the tables the
+        tail of kind "generalized_poisson_llh" reads.  `empty_bins`: the bin indices of the reference's
+        argument of that name."""
+        from pisa_amd.stages.likelihood.generalized_llh_params import mean_adjustment
+
+        counts = torch.stack(self._n_mc_local).to(torch.float64) if self._n_mc_local else \
+            torch.zeros((len(self.cont), self.n_bins), dtype=torch.float64, device=self.dev)
+        if self.world_size > 1:
+            import torch.distributed as dist
+
+            if dist.get_backend(self.group) == "gloo":
+                host = counts.cpu()
+                dist.all_reduce(host, group=self.group)
+                counts.copy_(host)
+            else:
+                dist.all_reduce(counts, group=self.group)
+        n_mc = counts.cpu().numpy()
+        adjust = np.array([mean_adjustment(row) for row in n_mc], dtype=np.float64)
+        empty = None
+        if empty_bins is not None and len(empty_bins):
+            idx = np.asarray(empty_bins, dtype=np.int64).ravel()
+            if idx.min() < 0 or idx.max() >= self.n_bins:
+                raise IndexError("empty_bins: bin index out of range")
+            empty = np.zeros(self.n_bins, dtype=np.uint8)
+            empty[idx] = 1
+        self._gpllh = dict(
+            n_mc=counts.contiguous(), n_mc_host=n_mc, adjust=K.to_device(adjust),
+            empty=None if empty is None else K.to_device(empty, dtype=np.uint8), empty_host=empty,
+            per_bin=torch.empty((_lib.MAX_POINTS, self.n_bins), dtype=torch.float64, device=self.dev),
+            done=torch.zeros(_lib.MAX_POINTS, dtype=torch.int32, device=self.dev),   # arrival counters of the totals
+            data_t=None, scratch=None, scratch_k=0, scratch_points=0)
+        return n_mc, adjust
+
+    def _bin_counts(self, obin):
+        """events per output bin (int64 [n_bins]) of one shard's digitised column; asynchronous"""
+        n = self.n_bins
+        c = torch.zeros(n + 1, dtype=torch.int64, device=obin.device)
+        c.scatter_add_(0, torch.where(obin >= 0, obin.long(), n), torch.ones(obin.numel(), dtype=torch.int64,
+                                                                             device=obin.device))
+        return c[:n]
+
+    def _gpllh_tables(self, n_points=1):
+        g = self._gpllh
+        if g is None:
+            raise RuntimeError("kind 'generalized_poisson_llh' needs HotPathEngine.configure_gpllh() first")
+        if self.data is None:
+            raise RuntimeError("kind 'generalized_poisson_llh' needs data (set_data)")
+        if g["data_t"] is not self.data:
+            # the longest recursion a mixture bin of this data can need
+            g["scratch_k"], g["scratch"], g["scratch_points"] = K.gpllh_scratch_k(self.data, g["n_mc"], g["empty"]), None, 0
+            g["data_t"] = self.data
+        if g["scratch_k"] > _lib.GPLLH_LDS_K and g["scratch_points"] < n_points:
+            # global scratch for the recursions beyond the LDS, for the points of this call
+            g["scratch"] = None
+            g["scratch"] = K.gpllh_scratch(n_points, self.n_bins, g["scratch_k"], self.dev)
+            g["scratch_points"] = n_points
+        return g
+
+    def _gpllh_launch(self, n_points, limbs, hist, sumw2, out, stream):
+        """the fused tail (`pisa_hip_finalize_gpllh`) of n_points limb sets; leaves the limbs zeroed"""
+        import ctypes as C
+
+        g = self._gpllh_tables(n_points)
+        return _lib.lib().pisa_hip_finalize_gpllh(
+            limbs, n_points, len(self.cont), self.n_bins, hist, sumw2, C.c_void_p(self.data.data_ptr()),
+            C.c_void_p(g["n_mc"].data_ptr()), C.c_void_p(g["adjust"].data_ptr()), K._ptr(g["empty"]),
+            C.c_void_p(g["per_bin"].data_ptr()), K._ptr(g["scratch"]), g["scratch_k"],
+            C.c_void_p(g["done"].data_ptr()), out, C.c_void_p(self.ws.status.data_ptr()),
+            C.c_void_p(self.metric_status.data_ptr()), 1, stream)
+
+    def _gpllh_tail(self, out):
+        """value of the current sums into `out` (device or pinned host tensor): the fused tail while the limbs
+        hold them, else alpha / beta / metric from the finalized maps (the same bits)"""
+        import ctypes as C
+
+        out_p = C.c_void_p(out.data_ptr())
+        if not self._maps_valid:
+            rc = self._gpllh_launch(1, C.c_void_p(self.ws.limbs.data_ptr()), C.c_void_p(self.ws.hist.data_ptr()),
+                                    C.c_void_p(self.ws.sumw2.data_ptr()), out_p, K._stream())
+            self._limbs_zero = self._maps_valid = rc == 0    # the engine's own limbs: consumed and zeroed
+            _lib.check(rc)
+            return
+        g = self._gpllh_tables()
+        alpha, beta, wsum = K.gpllh_params(self.ws.hist, self.ws.sumw2, g["n_mc"], g["adjust"])
+        _lib.check(_lib.lib().pisa_hip_generalized_poisson_llh(
+            C.c_void_p(self.data.data_ptr()), K._ptr(wsum), K._ptr(alpha), K._ptr(beta), K._ptr(g["n_mc"]),
+            len(self.cont), self.n_bins, K._ptr(g["empty"]), K._ptr(g["scratch"]), g["scratch_k"],
+            C.c_void_p(g["per_bin"].data_ptr()), C.c_void_p(g["done"].data_ptr()), out_p,
+            C.c_void_p(self.metric_status.data_ptr()), K._stream()))
 
     def metric_status_host(self):
         """status word of the metric kernels (negative inputs) -- one 4-byte read"""

@@ -466,6 +466,10 @@ class KdeEstimator:
 
 # --------------------------------------------------------------- metric
 METRIC_KIND = {"llh": 0, "poisson_llh": 1, "chi2": 2, "mod_chi2": 3}          # the fused tails of an evaluation
+# the generalized Poisson-gamma likelihood: a kind of the engine (`HotPathEngine.configure_gpllh`) with entry points of
+# its own (`pisa_hip_finalize_gpllh`, `pisa_hip_generalized_poisson_llh`), not one of the finalize_metric* kinds above
+GPLLH = "generalized_poisson_llh"
+GPLLH_KIND = 9
 # `metric()` on maps takes these too (PISA_HIP_METRIC_* of include/pisa_hip.h)
 MAP_METRIC_KIND = dict(METRIC_KIND, correct_chi2=4, signed_sqrt_mod_chi2=5, mcllh_mean=6, mcllh_eff=7, conv_llh=8)
 VARIANCE_METRICS = ("mod_chi2", "correct_chi2", "signed_sqrt_mod_chi2", "mcllh_mean", "mcllh_eff", "conv_llh")
@@ -594,6 +598,79 @@ def metric(kind, actual, expected, sigma2=None, per_bin=False, total_out=None, s
         if st != 0:
             _lib.check(st)
     return (total_out, pb) if per_bin else total_out
+
+
+# --------------------------------------------------- generalized Poisson-gamma likelihood
+def _check_status(status):
+    st = int(status.item())
+    if st != 0:
+        _lib.check(st)
+
+
+def gpllh_bin_sums(weights, index, offsets):
+    """(Sigma w, Sigma w^2) per bin, bin b's events being weights[index[offsets[b]:offsets[b + 1]]]
+    (`pisa_hip_gpllh_bin_sums`); a negative weight among them raises"""
+    n_bins = int(offsets.numel()) - 1
+    dev = weights.device
+    sw = torch.empty(n_bins, dtype=F8, device=dev)
+    sw2 = torch.empty(n_bins, dtype=F8, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    _lib.check(_lib.lib().pisa_hip_gpllh_bin_sums(_ptr(weights), _ptr(index), _ptr(offsets), n_bins, _ptr(sw),
+                                                  _ptr(sw2), _ptr(status), _stream()))
+    _check_status(status)
+    return sw, sw2
+
+
+def gpllh_params(sumw, sumw2, n_mc, adjust):
+    """generalized_llh_params per (container, bin): [n_cont, n_bins] sums and MC counts, [n_cont] mean
+    adjustments -> (alpha, beta, weight sums with the pseudo-weight) (`pisa_hip_gpllh_params`)"""
+    n_cont, n_bins = sumw.shape
+    dev = sumw.device
+    out = [torch.empty((n_cont, n_bins), dtype=F8, device=dev) for _ in range(3)]
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    _lib.check(_lib.lib().pisa_hip_gpllh_params(_ptr(sumw), _ptr(sumw2), _ptr(n_mc), _ptr(adjust), n_cont, n_bins,
+                                                _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(status), _stream()))
+    _check_status(status)
+    return tuple(out)
+
+
+def gpllh_scratch_k(actual, n_mc, empty=None):
+    """the largest data count among the bins that may take the eq. 91 mixture (some container with at most 100
+    MC events, not listed empty): the recursion length the metric must make room for"""
+    mix = (n_mc <= 100.0).any(dim=0)
+    if empty is not None:
+        mix &= empty == 0
+    if not bool(mix.any()):
+        return 0
+    k = actual[mix]
+    k = k[torch.isfinite(k)]
+    return int(k.max().item()) if k.numel() else 0
+
+
+def gpllh_scratch(n_points, n_bins, scratch_k, dev):
+    """the global scratch of mixture bins beyond the LDS (None when every one fits there)"""
+    if scratch_k <= _lib.GPLLH_LDS_K:
+        return None
+    return torch.empty(n_points * n_bins * 2 * (scratch_k + 1), dtype=F8, device=dev)
+
+
+def generalized_poisson_llh(actual, weights, alpha, beta, n_mc, empty=None):
+    """stats.generalized_poisson_llh on device (`pisa_hip_generalized_poisson_llh`): actual [n_bins],
+    weights / alpha / beta / n_mc [n_cont, n_bins], empty [n_bins] uint8 or None -> (total [1], per-bin [n_bins])"""
+    n_cont, n_bins = weights.shape
+    dev = actual.device
+    scratch_k = gpllh_scratch_k(actual, n_mc, empty)
+    scratch = gpllh_scratch(1, n_bins, scratch_k, dev)
+    per_bin = torch.empty(n_bins, dtype=F8, device=dev)
+    total = torch.empty(1, dtype=F8, device=dev)
+    status = torch.zeros(2, dtype=torch.int32, device=dev)     # [status, arrival counter of the total]
+    _lib.check(_lib.lib().pisa_hip_generalized_poisson_llh(
+        _ptr(actual), _ptr(weights), _ptr(alpha), _ptr(beta), _ptr(n_mc), n_cont, n_bins, _ptr(empty),
+        _ptr(scratch), scratch_k, _ptr(per_bin), C.c_void_p(status.data_ptr() + 4), _ptr(total), _ptr(status),
+        _stream()))
+    status = status[:1]
+    _check_status(status)
+    return total, per_bin
 
 
 def bin_scale(x, scale=None, scalar=1.0, floor=None, out=None):

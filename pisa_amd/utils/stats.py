@@ -3,7 +3,9 @@
 :651-695, `correct_chi2` :697-730, `signed_sqrt_mod_chi2` :762-786) for code that calls them on arrays rather than
 through `Map.metric`.  Each returns the PER-BIN values in the shape of its inputs (the caller sums, `np.nansum` in
 `Map.metric`, map.py:1601-1604); the arithmetic is `pisa_hip_metric`'s on the GPU -- there is no host
-implementation.  `barlow_llh`, `generalized_poisson_llh` and `weighted_chi2` are not built.
+implementation.  `generalized_poisson_llh` (stats.py:792-879) runs on `pisa_hip_generalized_poisson_llh`; it is not
+one of `ALL_METRICS`, as in the reference it takes the containers' maps rather than one expectation.  `barlow_llh`
+and `weighted_chi2` are not built.
 
 Where the reference reads expected values AND their standard deviations out of an `uncertainties` array
 (every metric here but chi2 / llh / poisson_llh), pass a `Map`, or the values and `sigma=`.
@@ -13,7 +15,8 @@ import numpy as np
 from pisa_amd import FTYPE
 
 __all__ = ["SMALL_POS", "CHI2_METRICS", "LLH_METRICS", "ALL_METRICS", "chi2", "llh", "poisson_llh", "mod_chi2",
-           "correct_chi2", "signed_sqrt_mod_chi2", "mcllh_mean", "mcllh_eff", "conv_llh"]
+           "correct_chi2", "signed_sqrt_mod_chi2", "mcllh_mean", "mcllh_eff", "conv_llh",
+           "generalized_poisson_llh"]
 
 SMALL_POS = 1e-10       # expected values are clipped to [SMALL_POS, inf) before logarithms and divisions (stats.py:74)
 CHI2_METRICS = ("chi2", "mod_chi2", "correct_chi2", "signed_sqrt_mod_chi2")
@@ -92,3 +95,67 @@ def conv_llh(actual_values, expected_values, sigma=None):
     """Poisson smeared with a normal of width sigma (101 steps over +-3 sigma), normalised to the value at
     N_actual = N_exp, minus the same at N_exp := N_actual"""
     return _per_bin("conv_llh", actual_values, expected_values, sigma)
+
+
+GPLLH_KEYS = ("weights", "llh_alphas", "llh_betas", "n_mc_events")
+
+
+def _gpllh_tables(actual_values, expected_values):
+    """[n_cont, n_bins] host arrays of the four MapSets of `expected_values`, checked before any device call"""
+    from collections import OrderedDict
+
+    if not isinstance(expected_values, OrderedDict):
+        raise TypeError("expected_values must be an OrderedDict of MapSet objects")
+    for key in GPLLH_KEYS:
+        if key not in expected_values:
+            raise KeyError('expected_values need a key named "%s"' % key)
+    n_bins = int(np.asarray(actual_values).size)
+    tabs = []
+    n_cont = None
+    for key in GPLLH_KEYS:
+        ms = expected_values[key]
+        maps = getattr(ms, "maps", None)
+        if maps is None:
+            raise TypeError('expected_values["%s"] must be a MapSet' % key)
+        rows = [np.asarray(m.hist, dtype=FTYPE).ravel() for m in maps]
+        if not rows or any(r.size != n_bins for r in rows):
+            raise ValueError('expected_values["%s"]: every map needs the %d bins of actual_values' % (key, n_bins))
+        if n_cont is not None and len(rows) != n_cont:
+            raise ValueError("expected_values: the MapSets hold different numbers of maps")
+        n_cont = len(rows)
+        tabs.append(np.ascontiguousarray(np.stack(rows)))
+    return tabs
+
+
+def _gpllh_empty(empty_bins, n_bins):
+    if empty_bins is None or len(empty_bins) == 0:
+        return None
+    idx = np.asarray(empty_bins, dtype=np.int64).ravel()
+    if idx.min() < 0 or idx.max() >= n_bins:
+        raise IndexError("empty_bins: bin index out of range")
+    m = np.zeros(n_bins, dtype=np.uint8)
+    m[idx] = 1
+    return m
+
+
+def generalized_poisson_total(actual_values, expected_values=None, empty_bins=None):
+    """(total, per-bin values) of `generalized_poisson_llh`; the total is the kernel's fixed-order sum"""
+    from pisa_amd import kernels as K
+
+    a = np.ascontiguousarray(np.asarray(actual_values, dtype=FTYPE).ravel())
+    w, alpha, beta, n_mc = _gpllh_tables(a, expected_values)
+    empty = _gpllh_empty(empty_bins, a.size)
+    total, per_bin = K.generalized_poisson_llh(
+        K.to_device(a), K.to_device(w), K.to_device(alpha), K.to_device(beta), K.to_device(n_mc),
+        None if empty is None else K.to_device(empty, dtype=np.uint8))
+    return float(total.item()), per_bin.cpu().numpy()
+
+
+def generalized_poisson_llh(actual_values, expected_values=None, empty_bins=None):
+    """The generalized Poisson-gamma likelihood of arXiv:1902.08831 per bin (stats.py:792-879): `expected_values` an
+    OrderedDict of MapSets (one map per container) under "weights", "llh_alphas", "llh_betas" and "n_mc_events" (as
+    the likelihood.generalized_llh_params service leaves them), `empty_bins` None or bin indices.  Per bin, k = the
+    data count truncated to an integer: listed empty bins give log(1e-10) if k > 0, else 0; bins where every
+    container has more than 100 MC events give k ln(sum w) - sum w - (k ln k - k) (-sum w at k = 0: the limit, where
+    the reference returns NaN); the others eq. 91 over the containers with finite alpha and beta.  Flat array."""
+    return generalized_poisson_total(actual_values, expected_values, empty_bins)[1]
