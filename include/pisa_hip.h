@@ -964,6 +964,35 @@ int pisa_hip_barr_fold_multi(const pisa_hip_barr_fold_set *h_sets, int32_t n_set
                              double nu_nubar_ratio, double delta_index, double Barr_uphor_ratio,
                              double Barr_nu_nubar_ratio, void *stream);
 
+/* ------------------------------------------------------- Fisher matrix and pulls */
+/* Replaces the arithmetic of pisa/utils/fisher_matrix.py build_fisher_matrix (:41-75, with get_fisher_matrix
+ * :78-116 as its caller) and of pisa/utils/pull_method.py get_derivative_map (:48-86) and calculate_pulls
+ * (:131-193, the vector d before the product with the covariance).
+ * d_hist / d_sumw2 [n_points][n_rows][n_bins]: n_points templates of n_rows maps each (the rows
+ * pisa_hip_hist_finalize writes for n_points * n_containers containers; n_rows = 1: totals already summed).
+ * Point 0 is the fiducial.  Per parameter p < n_params <= PISA_HIP_FISHER_MAX_PARAMS (host arrays):
+ * the points h_lo[p] < h_hi[p] of its sorted test values and h_dx[p] = hi - lo (finite, non-zero).
+ *   T_k[b]    = rows of point k added in ascending index order, starting from row 0 (MapSet.total())
+ *   sigma[b]  = sqrt(variances of point 0 added the same way) (Map.std_devs; NOT a variance, as the reference)
+ *   g_p[b]    = (T_hi[b] - T_lo[b]) / dx_p                                    -> d_grad [n_params][n_bins]
+ *   F_ij      = sum over b with T_0[b] != 0, ascending, from +0.0, of (g_i[b] g_j[b]) / sigma[b]
+ *               (one sequential chain per entry: the reference's loop, bit for bit; mirrored, exactly
+ *               symmetric)                                                    -> d_matrix [n_params][n_params]
+ *   d_p       = the same sum of ((truth[b] - T_0[b]) g_p[b]) / sigma[b]       -> d_pull [n_params]
+ *               (d_truth [n_bins] and d_pull both given or both NULL; the reference sums pairwise)
+ * d_totals [n_points][n_bins] (may be NULL): the T_k; d_var0 [n_bins] (may be NULL): point 0's variances;
+ * d_nonempty[1]: the number of bins with T_0 != 0; d_status[1]: 0, or PISA_HIP_FISHER_ZERO_SIGMA if a nonempty
+ * bin has sigma = 0 (maps without errors).  Both are written by the call.  One workgroup: any n_bins.
+ * PISA_HIP_ERR_INVALID: an index outside [0, n_points), dx zero or not finite, n_params outside
+ * [1, PISA_HIP_FISHER_MAX_PARAMS], n_bins outside [1, 2^31 - 1], sizes that overflow, NULL outputs. */
+#define PISA_HIP_FISHER_MAX_PARAMS 32
+#define PISA_HIP_FISHER_ZERO_SIGMA 1
+int pisa_hip_fisher(const double *d_hist, const double *d_sumw2, int32_t n_points, int32_t n_rows,
+                    int64_t n_bins, int32_t n_params, const int32_t *h_lo, const int32_t *h_hi,
+                    const double *h_dx, const double *d_truth, double *d_grad, double *d_matrix,
+                    double *d_pull, double *d_totals, double *d_var0, int64_t *d_nonempty,
+                    int32_t *d_status, void *stream);
+
 /* ------------------------------------------------------- raw device memory */
 /* Thin wrappers so hosts without torch (a cgo/ctypes binding of the
  * reference) can own device buffers. */

@@ -389,6 +389,27 @@ class FastPlan:
         eng.set_data_cached(np.ascontiguousarray(data_hist, dtype=np.float64).ravel())
         if not eng.multi_capable(g["plan"]):
             return None
+        pts = self._collect_points(set_point, n_points)
+        if pts is None:
+            return None
+        params_list, scales = pts
+        vals = eng.eval_many(params_list, kind, np.asarray(scales, dtype=np.float64), plan=g["plan"],
+                             energy=g["energy"])
+        if any(v != v for v in vals):
+            st = eng.metric_status_host()
+            if st != 0:
+                _lib.check(st)
+        # the engine's own per-container scales may have been moved by a point-by-point fallback
+        self.pipeline._containers_stale = True
+        return vals
+
+    def _collect_points(self, set_point, n_points):
+        """moves the parameters to each of `n_points` INDEPENDENT points in turn (`set_point(i)`) and collects
+        the point's oscillation parameter block and the containers' aeff scales: ([Prob3Params], [[scale per
+        container]]), or None when a stage other than osc.prob3 / aeff.aeff moved or Ye moved (the counters are
+        then forgotten, so that the next evaluation goes through the Stage protocol).  The parameters are left
+        at the last point."""
+        osc = self.osc
         params_list, scales = [], []
         self._dirty = True           # from here on the change counters are consumed point by point
         # the containers' aeff scales, recomputed when an aeff parameter moved since they were made (kept from
@@ -423,15 +444,34 @@ class FastPlan:
             scales.append(self._many_scales)
         osc.param_hash = None
         self.clock = Param.clock
-        vals = eng.eval_many(params_list, kind, np.asarray(scales, dtype=np.float64), plan=g["plan"],
-                             energy=g["energy"])
-        if any(v != v for v in vals):
-            st = eng.metric_status_host()
-            if st != 0:
-                _lib.check(st)
-        # the engine's own per-container scales may have been moved by a point-by-point fallback
+        return params_list, scales
+
+    def maps_many(self, set_point, n_points):
+        """The maps of all containers at `n_points` INDEPENDENT parameter points in one sweep of the events
+        (`HotPathEngine.maps_many`; two or more for more than MAX_POINTS points), for the Fisher matrix of a
+        `DistributionMaker`.  `set_point(i)` moves the pipeline's parameters to point i.  Per point the rows
+        are the bits `run()` gives there.  Returns dict(hist, sumw2 [n_points, n_containers, n_bins] device
+        tensors -- sumw2 zero when the pipeline's maps carry no errors --, sweeps), or None when the points
+        cannot be taken together (as `metric_many`); the caller then goes point by point.  The parameters are
+        left at the last point."""
+        osc, eng = self.osc, self.engine
+        if self.post or self.flux_stages or self.hist._engine is not eng or osc.pepmu is None:
+            return None
+        g = osc.grid
+        if (self._writes() != self.container_clock or n_points < 2
+                or bool(g["e_major"]) != bool(eng.grid.energy_first)):
+            return None
+        if not eng.sweep_capable(g["plan"]):
+            return None
+        pts = self._collect_points(set_point, n_points)
+        if pts is None:
+            return None
+        params_list, scales = pts
+        out = eng.maps_many(params_list, np.asarray(scales, dtype=np.float64), plan=g["plan"], energy=g["energy"])
+        if not self.with_errors:
+            out["sumw2"].zero_()     # output_key 'weights': the maps carry no errors
         self.pipeline._containers_stale = True
-        return vals
+        return out
 
     def run(self):
         """device-backed output MapSet, or None: take the ordinary path"""

@@ -1544,14 +1544,19 @@ class HotPathEngine:
         return out
 
     # -- several independent parameter points in one sweep of the events ---------------------------
-    def multi_capable(self, plan=None):
-        """whether `eval_many` can take its one-sweep path: planned grid oscillation (the engine's own
-        plan or the caller's, e.g. the osc.prob3 stage's), 16-bit index columns read through the shared
-        grid tables, all maps in one tail workgroup, LDS room for at least two points"""
+    def sweep_capable(self, plan=None):
+        """whether several points can share one sweep of the events (`pisa_hip_reweight_hist_multi`):
+        planned grid oscillation (the engine's own plan or the caller's, e.g. the osc.prob3 stage's), 16-bit
+        index columns read through the shared grid tables, no flux on the grid nodes, LDS room for at least
+        two points"""
         return ((plan or self.plan) is not None and self.indexed and self.index16 and not self.osc_events
-                and not self.node_flux and self.fused_tail and self.data is not None
-                and len(self.cont) * self.n_bins <= K.FINALIZE_METRIC_MAX
-                and _lib.lib().pisa_hip_multi_points_per_pass(self.n_bins) >= 2)
+                and not self.node_flux and _lib.lib().pisa_hip_multi_points_per_pass(self.n_bins) >= 2)
+
+    def multi_capable(self, plan=None):
+        """whether `eval_many` can take its one-sweep path: `sweep_capable`, data set and all maps in one
+        tail workgroup"""
+        return (self.sweep_capable(plan) and self.fused_tail and self.data is not None
+                and len(self.cont) * self.n_bins <= K.FINALIZE_METRIC_MAX)
 
     def _multi_ws(self, k):
         ws = getattr(self, "_multi", None)
@@ -1622,6 +1627,13 @@ class HotPathEngine:
         w = self._multi_ws(n)
         self._release_outputs()
         self._many_sweep(w, params_list, scales, plan, energy)
+        self._many_allreduce(w)
+        out = self._many_tail(w, n, kind)
+        self.last_many = w
+        return out
+
+    def _many_allreduce(self, w):
+        """int64 SUM of the K limb sets of a sweep over the ranks (as `allreduce`)"""
         if self.world_size > 1:
             if self._rccl is None:
                 self.allreduce_setup()
@@ -1629,9 +1641,68 @@ class HotPathEngine:
                 self._rccl.all_reduce_(w["limbs"], K._stream())
             else:
                 allreduce_limbs(w["limbs"], self.world_size, self.group)
-        out = self._many_tail(w, n, kind)
-        self.last_many = w
-        return out
+
+    def maps_many(self, params_list, scales=None, plan=None, energy=None):
+        """The maps of all containers at K INDEPENDENT points, for `fisher_many`: per chunk of at most MAX_POINTS
+        points one sweep of the events (`pisa_hip_reweight_hist_multi`), the limb all-reduce across ranks (as
+        `eval_many`) and `pisa_hip_hist_finalize` of the chunk's K * n_containers rows into one buffer.  No data
+        histogram is needed and the metric tail's one-workgroup bound does not apply.  Where the sweep does not
+        (`sweep_capable`), every point goes through the engine's single-point evaluation (the maps `eval_host`
+        computes).  Point groups (`configure_point_groups`) are not dealt to: every group computes all points.
+        `scales` [K][n_containers], `plan` / `energy`: as `eval_many`.  Returns dict(hist, sumw2 device tensors
+        [K, n_containers, n_bins], sweeps: the number of sweeps, 0 point by point)."""
+        n = len(params_list)
+        if n == 0:
+            raise ValueError("maps_many: no points")
+        n_c = len(self.cont)
+        plan = plan or self.plan
+        energy = energy if energy is not None else getattr(self, "energy_d", None)
+        hist = torch.empty((n, n_c, self.n_bins), dtype=torch.float64, device=self.dev)
+        sumw2 = torch.empty_like(hist)
+        sweeps = 0
+        if (n == 1 and self.plan is not None) or not self.sweep_capable(plan):
+            assert self.plan is not None, "point-by-point evaluation needs the engine's own oscillation tables"
+            for i, p in enumerate(params_list):
+                if scales is not None:
+                    for name, sc in zip(self.names, scales[i]):
+                        self.set_scale(name, sc)
+                self.accumulate(p)
+                self.allreduce()
+                h, s2 = self.finalize()
+                hist[i].copy_(h)
+                sumw2[i].copy_(s2)
+        else:
+            import ctypes as C
+
+            self._release_outputs()
+            lib = _lib.lib()
+            for i in range(0, n, _lib.MAX_POINTS):
+                k = min(_lib.MAX_POINTS, n - i)
+                w = self._multi_ws(k)
+                self._many_sweep(w, params_list[i:i + k], None if scales is None else scales[i:i + k], plan, energy)
+                self._many_allreduce(w)
+                rc = lib.pisa_hip_hist_finalize(
+                    C.c_void_p(w["limbs"].data_ptr()), k * n_c, self.n_bins, C.c_void_p(hist[i].data_ptr()),
+                    C.c_void_p(sumw2[i].data_ptr()), C.c_void_p(self.ws.status.data_ptr()), K._stream())
+                w["zero"] = False      # the limbs keep their sums: the next sweep clears them first
+                _lib.check(rc)
+                sweeps += 1
+        return dict(hist=hist, sumw2=sumw2, sweeps=sweeps)
+
+    def fisher_many(self, params_list, pairs, dx, scales=None, plan=None, energy=None, truth=None):
+        """Fisher matrix, per-bin gradients and (with `truth`, a flat data map) pull vector of the templates at K
+        INDEPENDENT points (pisa/utils/fisher_matrix.py get_fisher_matrix): point 0 is the fiducial, parameter p's
+        gradient is (T[hi] - T[lo]) / dx[p] with (lo, hi) = pairs[p].  Like `eval_many`, but ending in maps
+        (`maps_many`: one sweep per chunk of MAX_POINTS points, or point by point where the sweep does not
+        apply), then ONE `pisa_hip_fisher` launch.  Returns the dict of `kernels.fisher` plus those of
+        `maps_many`."""
+        out = self.maps_many(params_list, scales, plan, energy)
+        if truth is not None:
+            truth = K.to_device(np.asarray(truth, dtype=np.float64).ravel())
+        res = K.fisher(out["hist"], out["sumw2"], [q[0] for q in pairs], [q[1] for q in pairs], dx, truth)
+        self.check_status()
+        res.update(out)
+        return res
 
     def _many_sweep(self, w, params_list, scales, plan, energy):
         """prob3 of all points + ONE pass over the events into the points' limb sets (asynchronous)"""

@@ -673,6 +673,43 @@ def generalized_poisson_llh(actual, weights, alpha, beta, n_mc, empty=None):
     return total, per_bin
 
 
+# --------------------------------------------------------------- Fisher matrix and pulls
+def fisher(hist, sumw2, lo, hi, dx, truth=None):
+    """Fisher matrix, gradients and pull vector of n_points templates on device (`pisa_hip_fisher`):
+    hist / sumw2 [n_points, n_rows, n_bins] (or [n_points, n_bins]: totals), point 0 the fiducial; per parameter
+    the point indices lo / hi of its sorted test values and dx = hi - lo; truth [n_bins] or None.
+    Returns a dict of device tensors grad [P, n_bins], matrix [P, P], pull [P] (None without truth),
+    totals [n_points, n_bins], var0 [n_bins], and host ints nonempty (bins with a nonzero fiducial) and status
+    (0, or `_lib.FISHER_ZERO_SIGMA`: a nonempty bin without error)."""
+    if hist.dim() == 2:
+        hist, sumw2 = hist.unsqueeze(1), sumw2.unsqueeze(1)
+    assert hist.shape == sumw2.shape and hist.dtype == sumw2.dtype == F8
+    hist, sumw2 = hist.contiguous(), sumw2.contiguous()
+    n_points, n_rows, n_bins = hist.shape
+    n_par = len(dx)
+    if not (len(lo) == len(hi) == n_par):
+        raise ValueError("fisher: lo, hi and dx need one entry per parameter")
+    dev = hist.device
+    grad = torch.empty((max(n_par, 1), n_bins), dtype=F8, device=dev)
+    matrix = torch.empty((max(n_par, 1), max(n_par, 1)), dtype=F8, device=dev)
+    pull = torch.empty(max(n_par, 1), dtype=F8, device=dev) if truth is not None else None
+    totals = torch.empty((n_points, n_bins), dtype=F8, device=dev)
+    var0 = torch.empty(n_bins, dtype=F8, device=dev)
+    info = torch.zeros(2, dtype=torch.int64, device=dev)      # [nonempty, status (low 4 bytes)]
+    if truth is not None:
+        truth = truth.to(device=dev, dtype=F8).contiguous()
+    a_lo = (C.c_int32 * max(n_par, 1))(*[int(i) for i in lo])
+    a_hi = (C.c_int32 * max(n_par, 1))(*[int(i) for i in hi])
+    a_dx = (C.c_double * max(n_par, 1))(*[float(x) for x in dx])
+    _lib.check(_lib.lib().pisa_hip_fisher(
+        _ptr(hist), _ptr(sumw2), n_points, n_rows, n_bins, n_par, a_lo, a_hi, a_dx, _ptr(truth), _ptr(grad),
+        _ptr(matrix), _ptr(pull), _ptr(totals), _ptr(var0), C.c_void_p(info.data_ptr()),
+        C.c_void_p(info.data_ptr() + 8), _stream()))
+    nonempty, status = (int(v) for v in info.cpu())
+    return dict(grad=grad, matrix=matrix, pull=pull, totals=totals, var0=var0, nonempty=nonempty,
+                status=status & 0xFFFFFFFF)
+
+
 def bin_scale(x, scale=None, scalar=1.0, floor=None, out=None):
     """out = x * scale * scalar [floored]; see `pisa_hip_bin_scale`."""
     lib = _lib.lib()
