@@ -124,9 +124,15 @@ class Workload:
 
     def __init__(self, n_events=1200000, grid=(200, 100), out_binning="dragon", seed=0,
                  earth_model="osc/PREM_12layer.dat", detector_depth=2.0, prop_height=20.0,
-                 ye=(0.4656, 0.4656, 0.4957), on_device=False):
-        self.n_per = int(n_events) // len(NAMES)
-        self.n_events = self.n_per * len(NAMES)
+                 ye=(0.4656, 0.4656, 0.4957), on_device=False, names=NAMES):
+        # `names`: the containers, in order (default: the 12 of osc_example.cfg); `flav_nubar` reads flavour and
+        # sign from substrings, so names such as "numu_cc_s3" serve analyses with per-sample splits
+        names = tuple(names)
+        if not names or len(set(names)) != len(names):
+            raise ValueError("Workload: container names must be unique and at least one")
+        self.names = names
+        self.n_per = int(n_events) // len(names)
+        self.n_events = self.n_per * len(names)
         self.grid = GridSpec((1.0, 1000.0), grid[0], (-1.0, 1.0), grid[1], energy_first=True)
         self.ob = BINNINGS[out_binning]
         self.out_binning = _lib.make_binning(self.ob["mins"], self.ob["maxs"], self.ob["nbins"])
@@ -134,7 +140,8 @@ class Workload:
         self.layers = Layers(earth_model, detector_depth, prop_height)
         self.layers.setElecFrac(*ye)  # (YeI, YeO, YeM)
         self.on_device = bool(on_device)
-        self.events = make_events_device(self.n_per, seed) if on_device else make_events(self.n_per, seed)
+        self.events = (make_events_device(self.n_per, seed, names) if on_device
+                       else make_events(self.n_per, seed, names))
         cols = ("reco_energy", "reco_coszen", "pid")[: len(self.ob["nbins"])]
         for ev in self.events:
             if on_device:

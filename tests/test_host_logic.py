@@ -868,3 +868,33 @@ def test_partition_accounting_adds_up():
             assert sum(dep_blocks) + sum(share) in (n // 256, n // 256 - 1)
         seen_aligned += n_wg is not None
     assert seen_none > 0 and seen_aligned > 50
+
+
+def test_synthetic_workload_default_is_unchanged_and_names_can_be_chosen():
+    """`synthetic.Workload` (bench.py, smoke, the suite) draws its 12 default containers exactly as before `names=`
+    existed: the toy generator's energies and cos(zenith) from ONE RandomState(seed), container after container, and
+    the default call equals the call with the 12 names spelt out.  Other name lists split the events evenly and take
+    flavour and sign from substrings."""
+    from pisa_amd import synthetic
+
+    a = synthetic.Workload(n_events=12 * 50 + 7, grid=(8, 6))
+    b = synthetic.Workload(n_events=12 * 50 + 7, grid=(8, 6), names=list(synthetic.NAMES))
+    assert a.names == synthetic.NAMES and a.n_per == 50 and a.n_events == 600
+    rs = np.random.RandomState(0)
+    keys = ("true_energy", "true_coszen", "reco_energy", "reco_coszen", "pid", "nu_flux", "weighted_aeff",
+            "initial_weights")
+    for ea, eb, name in zip(a.events, b.events, synthetic.NAMES):
+        assert ea["name"] == eb["name"] == name
+        assert (ea["flav"], ea["nubar"]) == (eb["flav"], eb["nubar"]) == synthetic.flav_nubar(name)
+        assert np.array_equal(ea["true_energy"], np.power(10, rs.rand(50) * 3))
+        assert np.array_equal(ea["true_coszen"], rs.rand(50) * 2 - 1)
+        for k in keys:
+            assert np.array_equal(ea[k], eb[k]), (name, k)
+        assert all(np.array_equal(x, y) for x, y in zip(ea["sample"], eb["sample"]))
+        assert ea["scale"] == eb["scale"] == synthetic.aeff_scale_for(name)
+    c = synthetic.Workload(n_events=100, grid=(8, 6), names=("numu_cc_s3", "nuebar_nc_s0", "nutau_cc_s1"))
+    assert c.n_per == 33 and c.n_events == 99 and len(c.events) == 3
+    assert [(ev["flav"], ev["nubar"]) for ev in c.events] == [(1, 1), (0, -1), (2, 1)]
+    assert all(len(ev["true_energy"]) == 33 for ev in c.events)
+    with pytest.raises(ValueError):
+        synthetic.Workload(n_events=100, grid=(8, 6), names=("numu_cc", "numu_cc"))
