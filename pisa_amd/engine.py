@@ -16,6 +16,7 @@ the shape  loader -> [flux] -> osc.prob3 -> aeff.aeff -> utils.hist
 (pisa/core/pipeline.py:537-558 runs those stages one after another on host
 numpy arrays; here the three apply_functions are one pass over HBM).
 """
+import ctypes as C
 import os
 
 import numpy as np
@@ -249,8 +250,6 @@ def window_partition_order_native(obin, node, n_bins, width, n_nodes, n_wg=None)
     the window kernel, every output position's source in closed form; the block accounting in between is
     `_partition_accounting`, on the host, as in the torch formulation.  The SAME (permutation, part_start)
     (tests/test_gpu_engine.py compares them element by element), or None under the same condition."""
-    import ctypes as C
-
     lib = _lib.lib()
     n = int(obin.numel())
     n_part = max(1, -(-int(n_bins) // int(width)))
@@ -364,8 +363,6 @@ def deposit_block_order_native(obin, node, n_nodes):
     stable radix sort, one workgroup per 4 096-event window for the bank order, the block interleave in closed form -- the
     SAME permutation as the torch formulation above (tests/test_gpu_engine.py compares them element by element), without
     its ~40 launches, four sorts and two host synchronisations per container."""
-    import ctypes as C
-
     lib = _lib.lib()
     n = int(obin.numel())
     perm = torch.empty(n, dtype=torch.int64, device=obin.device)
@@ -388,8 +385,6 @@ def pack_resident_columns(perm, gx, gy, flux, aeff, w0, cols, node, obin):
     16-bit index layout, in ONE native launch (`pisa_hip_pack_resident_columns`, csrc/order.hip) -- element for element what
     the tensor operations of `HotPathEngine.__init__` produce (tests/test_gpu_engine.py compares them bit for bit).
     Returns (gx, gy, flux, aeff, w0, cols, node, obin, node_bin [n, 2], aeff_w0 [n, 2], static_w [n], node_bin16 [n_pad])."""
-    import ctypes as C
-
     n = int(perm.numel())
     n_pad = -(-n // 256) * 256
     dev = perm.device
@@ -619,8 +614,6 @@ class HotPathEngine:
         # `configure_gpllh`
         self._n_mc_local, self._gpllh = [], None
         # workgroups the fused kernel will give each container (a layout hint for the partitioned order)
-        import ctypes as C
-
         n_arr = (C.c_int64 * len(shards))(*[hi - lo for lo, hi in shards])
         hist_wgs = (C.c_int32 * len(shards))()
         if not (torch.cuda.is_available() and _lib.lib().pisa_hip_hist_workgroups(n_arr, len(shards), hist_wgs) == 0):
@@ -894,7 +887,7 @@ class HotPathEngine:
             self.setup_ms["total"] = sum(self.setup_ms.values())
         self.metric_out = torch.zeros(1, dtype=torch.float64, device=self.dev)
         self.metric_status = torch.zeros(1, dtype=torch.int32, device=self.dev)
-        # [0]: the metric as the tail kernel leaves it; [0:4]: the four partial sums of its split form
+        # [0]: the metric as the tail kernel leaves it; [0:16]: the sixteen partial sums of its split form
         # (`pisa_hip_finalize_metric_parts`, 16 workgroups: joined along the kernel's own reduction tree, bit for bit)
         self.metric_host = torch.zeros(16, dtype=torch.float64).pin_memory()
         self._metric_host_np = self.metric_host.numpy()
@@ -902,7 +895,7 @@ class HotPathEngine:
         self.spin_wait = 50000  # polls of the pinned result (~7 ms) before falling back to a stream sync
         self.fused_tail = True
         self._limbs_zero = self._maps_valid = False
-        self._lean = None
+        self._args = None          # pointers of the engine's buffers as the C ABI takes them (`_arg_block`)
         self._evaluator = None     # pisa_hip_evaluator of the standard shape (`_evaluator_for`)
         self.one_call = True       # eval_host through it; False: the three separate C-ABI calls (tests compare both)
         self.data = None
@@ -1033,9 +1026,7 @@ class HotPathEngine:
             cur.copy_(t)
 
     def _flux_tables(self, pepmu):
-        """per-container gather tables flux x probability from the shared (P_e, P_mu) tables"""
-        import ctypes as C
-
+        """per-container gather tables flux x probability from the shared (P_e, P_mu) tables (`pepmu`: their pointer)"""
         a = self._flux_tab_args
         if a is None:
             n = len(self.cont)
@@ -1044,8 +1035,7 @@ class HotPathEngine:
                 nubar=(C.c_int32 * n)(*[int(d.nubar) for d in self.cont]),
                 flav=(C.c_int32 * n)(*[int(d.flav) for d in self.cont]), n=n,
                 out=C.c_void_p(self._own_tables.data_ptr()), fn=_lib.lib().pisa_hip_flux_prob_tables)
-        return a["fn"](a["ptrs"], a["nubar"], a["flav"], a["n"], C.c_void_p(pepmu.data_ptr()),
-                       self.grid.size, a["out"], K._stream())
+        return a["fn"](a["ptrs"], a["nubar"], a["flav"], a["n"], pepmu, self.grid.size, a["out"], K._stream())
 
     @staticmethod
     def _fill_wflux(out, static_w, flux):
@@ -1082,8 +1072,6 @@ class HotPathEngine:
         buffers it was made from has been replaced; None where the shape does not apply (flux on the
         grid nodes: a launch of its own between prob3 and the accumulation; several ranks without the
         direct RCCL communicator: the all-reduce is torch.distributed's)"""
-        import ctypes as C
-
         if self.node_flux or not self.spin_wait:
             return None
         # fast path (this sits between the LLH read-back and the first launch of the next point): the very tensor OBJECTS
@@ -1115,9 +1103,7 @@ class HotPathEngine:
         ev = self._evaluator
         if ev is not None and ev["key"] == key:
             return ev
-        if ev is not None:
-            _lib.lib().pisa_hip_evaluator_destroy(ev["handle"])
-            self._evaluator = None
+        self._release_evaluator()
         d = _lib.EvaluatorDesc()
         d.h_containers = C.cast(self._cont_arr, C.c_void_p)
         d.n_containers, d.n_e, d.e_major = len(self._cont_arr), self.energy_d.numel(), 1 if self.grid.energy_first else 0
@@ -1174,50 +1160,47 @@ class HotPathEngine:
         self._release_outputs()
         if params is not None:
             self.compute_probs(params)
-        if self.node_flux:
-            _lib.check(self._flux_tables(self.pepmu))
-        K.reweight_hist(self._cont_arr, self.grid.binning, self.prob_nu, self.prob_nubar,
-                        self.pepmu if (self.indexed and not self.osc_events) else None,
-                        self.out_binning, self.ws, clear=not self._limbs_zero)
-        self._limbs_zero = self._maps_valid = False
+        a = self._arg_block()
+        # (no gather table where the events are oscillated one by one or the columns are not indexed)
+        _lib.check(self._launch_acc(a, a["nu"], a["nubar"], a["pepmu"] if (self.indexed and not self.osc_events) else None))
 
-    def allreduce(self):
-        """int64 SUM of the limbs over the ranks: RCCL called directly on the launch stream where
-        the group runs on RCCL (`pisa_amd/rccl.py`; all ranks agree on it at the first call),
-        `torch.distributed` otherwise (gloo in the CPU tests, or PISA_HIP_DIRECT_RCCL=0)."""
+    def allreduce(self, limbs=None):
+        """int64 SUM of the limbs (the engine's own, or the K limb sets of a sweep) over the ranks: RCCL called
+        directly on the launch stream where the group runs on RCCL (`pisa_amd/rccl.py`; all ranks agree on it at
+        the first call), `torch.distributed` otherwise (gloo in the CPU tests, or PISA_HIP_DIRECT_RCCL=0)."""
         if self.world_size <= 1:
             return
+        if limbs is None:
+            limbs = self.ws.limbs
         if self._rccl is None:
             self.allreduce_setup()
         if self._rccl:
-            self._rccl.all_reduce_(self.ws.limbs, K._stream())
+            self._rccl.all_reduce_(limbs, K._stream())
         else:
-            allreduce_limbs(self.ws.limbs, self.world_size, self.group)
+            allreduce_limbs(limbs, self.world_size, self.group)
 
     def allreduce_setup(self):
         """direct RCCL communicator where the group runs on RCCL (all ranks agree), else False"""
-        import os
-
         from . import rccl
 
         self._rccl = False
         if int(os.environ.get("PISA_HIP_DIRECT_RCCL", "1")):
             self._rccl = rccl.LimbAllReduce.create(self.dev, self.group) or False
 
-    def __del__(self):
-        ev = getattr(self, "_evaluator", None)
+    def _release_evaluator(self):
+        ev, self._evaluator = self._evaluator, None
         if ev is not None:
-            try:
-                _lib.lib().pisa_hip_evaluator_destroy(ev["handle"])
-            except Exception:  # interpreter shutdown
-                pass
-            self._evaluator = None
+            _lib.lib().pisa_hip_evaluator_destroy(ev["handle"])
+
+    def __del__(self):
+        try:
+            self._release_evaluator()
+        except Exception:  # interpreter shutdown
+            pass
 
     def close(self):
-        """release the direct RCCL communicator (before the process group is destroyed)"""
-        if getattr(self, "_evaluator", None) is not None:
-            _lib.lib().pisa_hip_evaluator_destroy(self._evaluator["handle"])
-            self._evaluator = None
+        """release the evaluator and the direct RCCL communicator (before the process group is destroyed)"""
+        self._release_evaluator()
         if self._rccl:
             self._rccl.destroy()
         self._rccl = None
@@ -1251,150 +1234,155 @@ class HotPathEngine:
             self._extra_src = np.array(extra, dtype=np.float64, copy=True)
         return self._extra_d
 
+    # -- the launches every evaluation path shares -----------------------------------------------
+    def _arg_block(self, tables=None):
+        """the `ctypes` pointers of the engine's own buffers, as the C ABI takes them: built at the first use and
+        again when the probability tables have been replaced (`eval_batch` swaps its two sets, a stage hands in
+        its own `pepmu`), judged by object identity -- the block keeps the tensors, so an identity cannot be
+        recycled.  This sits between the LLH read-back and the first launch of the next point: a `data_ptr()` +
+        `c_void_p` costs ~0.5 us, a launch takes a dozen.  The current `self.data` and the caller's `tables` of
+        `front` are refreshed here, by identity as well."""
+        a = self._args
+        if a is None or a["pepmu_t"] is not self.pepmu or a["nu_t"] is not self.prob_nu:
+            energy = getattr(self, "energy_d", None)
+            a = self._args = dict(
+                lib=_lib.lib(), cont=self._cont_arr, n_cont=len(self._cont_arr),
+                plan=None if self.plan is None else self.plan.handle, energy=K._ptr(energy),
+                n_e=0 if energy is None else energy.numel(), e_major=1 if self.grid.energy_first else 0,
+                nu=K._ptr(self.prob_nu), nubar=K._ptr(self.prob_nubar), pepmu=K._ptr(self.pepmu),
+                nu_t=self.prob_nu, pepmu_t=self.pepmu, tables=None, tables_t=None,
+                grid=C.byref(self.grid.binning), outb=C.byref(self.out_binning), limbs=K._ptr(self.ws.limbs),
+                status=K._ptr(self.ws.status), hist=K._ptr(self.ws.hist), sumw2=K._ptr(self.ws.sumw2),
+                data=None, data_t=None, out=C.c_void_p(self.metric_host.data_ptr()),
+                mstatus=K._ptr(self.metric_status))
+        if a["data_t"] is not self.data:  # new pseudo-data
+            a["data"], a["data_t"] = K._ptr(self.data), self.data
+        if tables is not None and a["tables_t"] is not tables:
+            a["tables"], a["tables_t"] = K._ptr(tables), tables
+        return a
+
+    def _launch_acc(self, a, nu, nubar, pepmu):
+        """the fused lookup + reweight + histogram launch from the probability tables behind the three pointers
+        (the `node_flux` gather tables made of them first), on top of the limbs where the last tail has left them
+        zeroed, clearing them otherwise; returns the status"""
+        rc = self._flux_tables(pepmu) if self.node_flux else 0
+        if rc == 0:
+            lib = a["lib"]
+            fn = lib.pisa_hip_reweight_hist_acc if self._limbs_zero else lib.pisa_hip_reweight_hist
+            rc = fn(a["cont"], a["n_cont"], a["grid"], nu, nubar, pepmu, a["outb"], a["limbs"], a["status"], K._stream())
+        self._limbs_zero = self._maps_valid = False
+        return rc
+
+    TAIL_PARTS = 16   # workgroups of the split tail (`pisa_hip_finalize_metric_parts`)
+
+    def _launch_tail(self, kind, out=None, n_parts=1, scale=None, extra=None, w=None, n_points=1):
+        """the fused tail, one launch: maps + metric against `self.data` of the engine's limbs, or of the `n_points`
+        limb sets of the sweep workspace `w`, into `out` (a pointer; the pinned `metric_host` by default); it leaves
+        the limbs zeroed for the next accumulation.  `n_parts`: the workgroups per point the caller can join
+        (`_join_parts`).  They are used whenever the value is polled from pinned memory anyway; not for chi2 (its
+        all-bins-equal rule, stats.py:160-161, needs every bin) nor for generalized_poisson_llh.  `scale`
+        [n_cont, n_bins] / `extra` [2, n_bins] (device tensors): as `tail_host`.  Returns the parts per point
+        that `out` receives."""
+        a = self._arg_block()
+        limbs, hist, sumw2 = (a["limbs"], a["hist"], a["sumw2"]) if w is None else \
+            (K._ptr(w["limbs"]), K._ptr(w["hist"]), K._ptr(w["sumw2"]))
+        if out is None:
+            out = a["out"]
+        if kind == GPLLH:
+            if scale is not None or extra is not None:
+                raise ValueError("generalized_poisson_llh: no post-histogram scale or added maps in the tail "
+                                 "(alpha and beta are formed from the histogrammed sums)")
+            g = self._gpllh_tables(n_points)
+            n_parts = 1
+            rc = a["lib"].pisa_hip_finalize_gpllh(
+                limbs, n_points, a["n_cont"], self.n_bins, hist, sumw2, a["data"], K._ptr(g["n_mc"]), K._ptr(g["adjust"]),
+                K._ptr(g["empty"]), K._ptr(g["per_bin"]), K._ptr(g["scratch"]), g["scratch_k"], K._ptr(g["done"]), out,
+                a["status"], a["mstatus"], 1, K._stream())
+        else:
+            if not (self.split_tail and self.spin_wait > 0) or kind == "chi2":
+                n_parts = 1
+            # one native function behind both entry points (`finalize_metric_impl`): one workgroup per point, or n_parts
+            fn, parts = (a["lib"].pisa_hip_finalize_metric_multi, ()) if n_parts == 1 else \
+                (a["lib"].pisa_hip_finalize_metric_parts, (n_parts,))
+            rc = fn(limbs, n_points, a["n_cont"], self.n_bins, hist, sumw2, K.METRIC_KIND[kind], a["data"],
+                    K._ptr(scale), 0, K._ptr(extra), out, *parts, a["status"], a["mstatus"], 1, K._stream())
+        if w is None:
+            self._limbs_zero = self._maps_valid = rc == 0
+        else:
+            w["zero"] = rc == 0
+        _lib.check(rc)
+        return n_parts
+
+    def _wait(self, h):
+        """`h`: the view of pinned host memory a tail writes, filled with NaN before the launch.  The kernel's store
+        is visible a few us before the stream-completion signal has travelled through the runtime: poll it, NaN
+        being the "not yet" marker (a genuine NaN result ends in the stream synchronisation and is returned)."""
+        add = np.add.reduce
+        for _ in range(self.spin_wait):
+            v = add(h)          # NaN while one value is missing (one numpy call per poll)
+            if v == v:
+                return h
+        torch.cuda.current_stream().synchronize()
+        return h
+
+    @staticmethod
+    def _join_parts(p):
+        """the metric kernel's reduction tree, its last levels, for the parts of one point or (one row per point) of
+        several: p[..., i] += p[..., i + w] for w = n/2 ... 1"""
+        w = p.shape[-1] // 2
+        while w >= 1:
+            p = p[..., :w] + p[..., w:2 * w]
+            w //= 2
+        return p[..., 0]
+
+    def _fits_tail(self):
+        """the maps of all containers fit the one workgroup (per part) of the fused tail"""
+        return self.fused_tail and len(self.cont) * self.n_bins <= K.FINALIZE_METRIC_MAX
+
+    def can_fuse_tail(self, kind="llh"):
+        """whether the tail of `kind` is the one fused launch: the limbs still hold the sums, and one workgroup the
+        maps (generalized_poisson_llh: its fused tail has no such bound)"""
+        return not self._maps_valid and (kind == GPLLH or self._fits_tail())
+
     # -- two-phase evaluation for callers that hand out maps before a metric is asked for ------
     def front(self, tables=None):
         """phase A: fused lookup + reweight + histogram (+ all-reduce) with the probability
         tables of the caller; asynchronous.  Device-backed maps of the previous evaluation that
         are still referenced are brought to the host first (the launch overwrites them)."""
         self._release_outputs()
-        import ctypes as C
-
-        a = self._lean
-        if a is None or a.get("kind") != "front" or a.get("front_pepmu") is not tables:
-            lib = _lib.lib()
-            pep = tables if tables is not None else self.pepmu
-            a = self._lean = dict(
-                kind="front", front_pepmu=tables, tabs=None, lib=lib, cont=self._cont_arr, n_cont=len(self._cont_arr),
-                nu=C.c_void_p(self.prob_nu.data_ptr()) if self.prob_nu is not None else None,
-                nubar=C.c_void_p(self.prob_nubar.data_ptr()) if self.prob_nubar is not None else None,
-                pepmu=C.c_void_p(pep.data_ptr()), grid=C.byref(self.grid.binning),
-                outb=C.byref(self.out_binning), limbs=C.c_void_p(self.ws.limbs.data_ptr()),
-                status=C.c_void_p(self.ws.status.data_ptr()), hist=C.c_void_p(self.ws.hist.data_ptr()),
-                sumw2=C.c_void_p(self.ws.sumw2.data_ptr()), data=None, data_t=None,
-                out=C.c_void_p(self.metric_host.data_ptr()),
-                mstatus=C.c_void_p(self.metric_status.data_ptr()), keep=pep)
-        lib = a["lib"]
-        if self.node_flux:
-            _lib.check(self._flux_tables(a["keep"]))
-        fn = lib.pisa_hip_reweight_hist_acc if self._limbs_zero else lib.pisa_hip_reweight_hist
-        rc = fn(a["cont"], a["n_cont"], a["grid"], a["nu"], a["nubar"], a["pepmu"], a["outb"],
-                a["limbs"], a["status"], K._stream())
-        self._limbs_zero = self._maps_valid = False
-        _lib.check(rc)
+        a = self._arg_block(tables)
+        _lib.check(self._launch_acc(a, a["nu"], a["nubar"], a["pepmu"] if tables is None else a["tables"]))
         self.allreduce()
-
-    def can_fuse_tail(self):
-        return (self.fused_tail and not self._maps_valid
-                and len(self.cont) * self.n_bins <= K.FINALIZE_METRIC_MAX)
-
-    def _split_ok(self, kind):
-        """the tail in its four-workgroup form (partial sums joined here): whenever the value is polled from
-        pinned memory anyway; not for chi2 (its all-bins-equal rule, stats.py:160-161, needs every bin)"""
-        return self.split_tail and self.spin_wait > 0 and kind not in ("chi2", GPLLH)
-
-    TAIL_PARTS = 16   # workgroups of the split tail (`pisa_hip_finalize_metric_parts`)
-
-    @staticmethod
-    def _join_parts(p):
-        """the metric kernel's reduction tree, its last levels: p[i] += p[i + w] for w = n/2 ... 1"""
-        p = [float(v) for v in p]
-        w = len(p) // 2
-        while w >= 1:
-            for i in range(w):
-                p[i] = p[i] + p[i + w]
-            w //= 2
-        return p[0]
-
-    def _poll_split(self):
-        """the split tail's partial sums joined as the kernel's own tree joins them, as soon as all have arrived"""
-        h = self._metric_host_np
-        n = self.TAIL_PARTS
-        hn = h[:n]
-        add = np.add.reduce
-        for _ in range(self.spin_wait):
-            v = add(hn)          # NaN while one of them is missing (one numpy call per poll)
-            if v == v:
-                return self._join_parts(hn)
-        torch.cuda.current_stream().synchronize()
-        return self._join_parts(hn)
 
     def tail_host(self, kind, scale=None, extra=None):
         """phase B: maps + metric against `self.data` of the accumulated limbs, value on the host.
         `scale` [n_cont, n_bins] / `extra` [2, n_bins] (device tensors): per-bin factors of a stage after
-        the histogram and maps of other pipelines added to the template
-        (`pisa_hip_finalize_metric_scaled`); only with the fused tail (`can_fuse_tail()`)."""
-        if kind == GPLLH:
-            if scale is not None or extra is not None:
-                raise ValueError("generalized_poisson_llh: no post-histogram scale or added maps in the tail "
-                                 "(alpha and beta are formed from the histogrammed sums)")
-            self._tail(kind, self.metric_host)
-            torch.cuda.current_stream().synchronize()
-            return float(self.metric_host[0])
-        if self.can_fuse_tail():
-            import ctypes as C
-
-            a = self._lean
-            if a is None:   # first use without `front` / `eval_host` having built the argument block
-                lib = _lib.lib()
-                a = object()   # matches no table: `front` / `_lean_eval` build their full block
-                a = self._lean = dict(
-                    kind="tail", front_pepmu=a, tabs=a, lib=lib, cont=self._cont_arr, n_cont=len(self._cont_arr),
-                    limbs=C.c_void_p(self.ws.limbs.data_ptr()), status=C.c_void_p(self.ws.status.data_ptr()),
-                    hist=C.c_void_p(self.ws.hist.data_ptr()), sumw2=C.c_void_p(self.ws.sumw2.data_ptr()),
-                    data=None, data_t=None, out=C.c_void_p(self.metric_host.data_ptr()),
-                    mstatus=C.c_void_p(self.metric_status.data_ptr()))
-            if a["data_t"] is not self.data:
-                a["data"], a["data_t"] = C.c_void_p(self.data.data_ptr()), self.data
-            h = self._metric_host_np
-            if self._split_ok(kind):
-                h[:] = np.nan
-                rc = a["lib"].pisa_hip_finalize_metric_parts(
-                    a["limbs"], 1, a["n_cont"], self.n_bins, a["hist"], a["sumw2"], K.METRIC_KIND[kind], a["data"],
-                    None if scale is None else C.c_void_p(scale.data_ptr()), 0,
-                    None if extra is None else C.c_void_p(extra.data_ptr()),
-                    a["out"], self.TAIL_PARTS, a["status"], a["mstatus"], 1, K._stream())
-                self._limbs_zero = self._maps_valid = rc == 0
-                _lib.check(rc)
-                return self._poll_split()
-            h[0] = np.nan
-            if scale is None and extra is None:
-                rc = a["lib"].pisa_hip_finalize_metric(a["limbs"], a["n_cont"], self.n_bins, a["hist"],
-                                                       a["sumw2"], K.METRIC_KIND[kind], a["data"], a["out"],
-                                                       a["status"], a["mstatus"], 1, K._stream())
-            else:
-                rc = a["lib"].pisa_hip_finalize_metric_scaled(
-                    a["limbs"], a["n_cont"], self.n_bins, a["hist"], a["sumw2"], K.METRIC_KIND[kind], a["data"],
-                    None if scale is None else C.c_void_p(scale.data_ptr()),
-                    None if extra is None else C.c_void_p(extra.data_ptr()),
-                    a["out"], a["status"], a["mstatus"], 1, K._stream())
-            self._limbs_zero = self._maps_valid = rc == 0
-            _lib.check(rc)
-            for _ in range(self.spin_wait):
-                v = h[0]
-                if v == v:
-                    return float(v)
-        else:
-            assert scale is None and extra is None, "scaled tail needs the fused tail kernel"
-            self._tail(kind, self.metric_host)
+        the histogram and maps of other pipelines added to the template; only with the fused tail
+        (`can_fuse_tail()`)."""
+        h = self._metric_host_np
+        if self.can_fuse_tail(kind):
+            h[:] = np.nan
+            n_parts = self._launch_tail(kind, None, self.TAIL_PARTS, scale, extra)
+            return float(self._join_parts(self._wait(h[:n_parts])))
+        if scale is not None or extra is not None:
+            raise ValueError("a post-histogram scale or added maps need the fused tail kernel")
+        self._tail(kind, self.metric_host)
         torch.cuda.current_stream().synchronize()
-        return float(self.metric_host[0])
+        return float(h[0])
 
     def metric(self, kind="llh"):
         return K.metric(kind, self.data, self.ws.hist, self.ws.sumw2, total_out=self.metric_out,
                         status=self.metric_status)
 
     def _tail(self, kind, out):
-        """maps + metric of the accumulated (and all-reduced) limbs into `out`.
-        One launch (`pisa_hip_finalize_metric`, which also leaves the limbs zeroed
-        for the next accumulate) when a single workgroup can hold the maps; the
-        separate finalize and metric kernels otherwise.  Same bits either way."""
-        if kind == GPLLH:
-            self._gpllh_tail(out)
-            return out
-        if (self.fused_tail and not self._maps_valid
-                and len(self.cont) * self.n_bins <= K.FINALIZE_METRIC_MAX):
-            K.finalize_metric(self.ws, kind, self.data, out, self.metric_status, clear_limbs=True)
-            self._limbs_zero = self._maps_valid = True
+        """maps + metric of the accumulated (and all-reduced) limbs into `out` (device or pinned host tensor).
+        One launch (`_launch_tail`, which also leaves the limbs zeroed for the next accumulate) while the limbs
+        hold the sums and a single workgroup can hold the maps; the separate finalize and metric kernels
+        otherwise.  Same bits either way."""
+        if self.can_fuse_tail(kind):
+            self._launch_tail(kind, C.c_void_p(out.data_ptr()))
+        elif kind == GPLLH:
+            self._gpllh_from_maps(out)
         else:
             self.finalize()
             K.metric(kind, self.data, self.ws.hist, self.ws.sumw2, total_out=out,
@@ -1415,90 +1403,35 @@ class HotPathEngine:
         writes the metric into pinned, device-mapped host memory, so the host only
         waits for the stream (no device->host copy operation).  Returns a float.
 
-        For the standard shape (planned grid, packed columns, fused tail) the four
-        launches go through `_lean_eval`: the same C-ABI calls as the generic
+        For the standard shape (planned grid, packed columns, fused tail) the whole
+        evaluation is one C-ABI call (`_evaluator_for`) or, where that does not apply,
+        the launches of `_lean_front`: the same C-ABI calls as the generic
         methods, minus their per-call Python (tensor -> pointer conversions,
         contiguity asserts, keyword handling) -- this sits between the LLH
-        read-back and the first kernel of the next point."""
-        if (self.plan is not None and self.indexed and not self.osc_events and self.fused_tail
-                and self.data is not None
-                and len(self.cont) * self.n_bins <= K.FINALIZE_METRIC_MAX):
-            if self.spin_wait:
-                ev = self._evaluator_for() if self.one_call and kind != GPLLH else None
-                if ev is not None:
-                    return self._eval_one_call(ev, params, kind)
-                # The tail kernel's store into pinned host memory is visible a few us before the
-                # stream-completion signal has travelled through the runtime: poll it.  NaN is
-                # the "not yet" marker (a genuine NaN result falls through to the stream sync).
-                h = self._metric_host_np
-                if self._split_ok(kind):
-                    h[:] = np.nan
-                    self._lean_eval(params, kind, split=True)
-                    return self._poll_split()
-                h[0] = np.nan
-                self._lean_eval(params, kind)
-                for _ in range(self.spin_wait):
-                    v = h[0]
-                    if v == v:
-                        return float(v)
-            else:
-                self._lean_eval(params, kind)
+        read-back and the first kernel of the next point.  Any other shape (event-by-event
+        oscillations, unplanned grids) goes through `accumulate`; the tail and the wait
+        for its value are `tail_host`'s either way."""
+        if (self.plan is not None and self.indexed and not self.osc_events and self.data is not None
+                and self._fits_tail()):
+            ev = self._evaluator_for() if self.one_call and kind != GPLLH else None
+            if ev is not None:
+                return self._eval_one_call(ev, params, kind)
+            self._lean_front(params)
         else:
             self.accumulate(params)
-            self.allreduce()
-            if self.spin_wait and self.data is not None and self.can_fuse_tail():
-                # (event-by-event oscillations, unplanned grids: the same tail and the same polled value)
-                return self.tail_host(kind)
-            self._tail(kind, self.metric_host)
-        torch.cuda.current_stream().synchronize()
-        return float(self.metric_host[0])
+        self.allreduce()
+        return self.tail_host(kind)
 
-    def _lean_eval(self, params, kind, split=False):
-        import ctypes as C
-
-        a = self._lean
-        tabs = (self.prob_nu, self.prob_nubar, self.pepmu)
-        if a is None or a.get("kind") != "eval" or a["tabs"] is not tabs[2]:
-            lib = _lib.lib()
-            a = self._lean = dict(
-                kind="eval", tabs=self.pepmu, lib=lib, cont=self._cont_arr, n_cont=len(self._cont_arr),
-                plan=self.plan.handle, energy=C.c_void_p(self.energy_d.data_ptr()),
-                n_e=self.energy_d.numel(), e_major=1 if self.grid.energy_first else 0,
-                nu=C.c_void_p(self.prob_nu.data_ptr()), nubar=C.c_void_p(self.prob_nubar.data_ptr()),
-                pepmu=C.c_void_p(self.pepmu.data_ptr()), grid=C.byref(self.grid.binning),
-                outb=C.byref(self.out_binning), limbs=C.c_void_p(self.ws.limbs.data_ptr()),
-                status=C.c_void_p(self.ws.status.data_ptr()), hist=C.c_void_p(self.ws.hist.data_ptr()),
-                sumw2=C.c_void_p(self.ws.sumw2.data_ptr()), data=C.c_void_p(self.data.data_ptr()),
-                data_t=self.data, out=C.c_void_p(self.metric_host.data_ptr()),
-                mstatus=C.c_void_p(self.metric_status.data_ptr()))
-        if a["data_t"] is not self.data:  # new pseudo-data
-            a["data"], a["data_t"] = C.c_void_p(self.data.data_ptr()), self.data
+    def _lean_front(self, params):
+        """prob3 on the grid + the accumulation, through the argument block"""
+        a = self._arg_block()
         self._release_outputs()
-        lib, s = a["lib"], K._stream()
         # the fused kernel reads the (P_e, P_mu) gather tables only: the full P[3][3] tables (72 B per
         # node, poorly coalesced stores) are not written on this path (`compute_probs` writes them)
-        rc = lib.pisa_hip_prob3_grid_planned(C.byref(params), a["plan"], a["energy"], a["n_e"],
-                                             a["e_major"], None, None, a["pepmu"], s)
-        if rc == 0 and self.node_flux:
-            rc = self._flux_tables(self.pepmu)
+        rc = a["lib"].pisa_hip_prob3_grid_planned(C.byref(params), a["plan"], a["energy"], a["n_e"],
+                                                  a["e_major"], None, None, a["pepmu"], K._stream())
         if rc == 0:
-            fn = lib.pisa_hip_reweight_hist_acc if self._limbs_zero else lib.pisa_hip_reweight_hist
-            rc = fn(a["cont"], a["n_cont"], a["grid"], a["nu"], a["nubar"], a["pepmu"], a["outb"],
-                    a["limbs"], a["status"], s)
-        self._limbs_zero = self._maps_valid = False
-        if rc == 0:
-            self.allreduce()
-            if kind == GPLLH:
-                rc = self._gpllh_launch(1, a["limbs"], a["hist"], a["sumw2"], a["out"], s)
-            elif split:
-                rc = lib.pisa_hip_finalize_metric_parts(a["limbs"], 1, a["n_cont"], self.n_bins, a["hist"],
-                                                        a["sumw2"], K.METRIC_KIND[kind], a["data"], None, 0, None,
-                                                        a["out"], self.TAIL_PARTS, a["status"], a["mstatus"], 1, s)
-            else:
-                rc = lib.pisa_hip_finalize_metric(a["limbs"], a["n_cont"], self.n_bins, a["hist"],
-                                                  a["sumw2"], K.METRIC_KIND[kind], a["data"], a["out"],
-                                                  a["status"], a["mstatus"], 1, s)
-            self._limbs_zero = self._maps_valid = rc == 0
+            rc = self._launch_acc(a, a["nu"], a["nubar"], a["pepmu"])
         _lib.check(rc)
 
     def eval_batch(self, params_list, kind="llh"):
@@ -1510,6 +1443,7 @@ class HotPathEngine:
         end.  Returns a device tensor with one metric value per point."""
         assert not self.osc_events and self.plan is not None and self.data is not None
         self._release_outputs()   # device-backed maps of the previous evaluation: home before the limbs are reused
+        a = self._arg_block()
         n = len(params_list)
         out = torch.empty(n, dtype=torch.float64, device=self.dev)
         if not hasattr(self, "_osc_stream"):
@@ -1531,13 +1465,9 @@ class HotPathEngine:
                                      out_nu=tab[0], out_nubar=tab[1], out_pepmu=tab[2])
                 osc_done[k].record(self._osc_stream)
             main.wait_event(osc_done[k])
-            if self.node_flux:
-                _lib.check(self._flux_tables(tab[2]))
-            K.reweight_hist(self._cont_arr, self.grid.binning, tab[0], tab[1], tab[2],
-                            self.out_binning, self.ws, clear=not self._limbs_zero)
+            _lib.check(self._launch_acc(a, K._ptr(tab[0]), K._ptr(tab[1]), K._ptr(tab[2])))
             used[k % 2] = torch.cuda.Event()
             used[k % 2].record(main)
-            self._limbs_zero = self._maps_valid = False
             self.allreduce()
             self._tail(kind, out[k:k + 1])
         self.prob_nu, self.prob_nubar, self.pepmu = self._tables[(n - 1) % 2] if n else self._tables[0]
@@ -1555,8 +1485,7 @@ class HotPathEngine:
     def multi_capable(self, plan=None):
         """whether `eval_many` can take its one-sweep path: `sweep_capable`, data set and all maps in one
         tail workgroup"""
-        return (self.sweep_capable(plan) and self.fused_tail and self.data is not None
-                and len(self.cont) * self.n_bins <= K.FINALIZE_METRIC_MAX)
+        return self.sweep_capable(plan) and self.data is not None and self._fits_tail()
 
     def _multi_ws(self, k):
         ws = getattr(self, "_multi", None)
@@ -1564,8 +1493,6 @@ class HotPathEngine:
             ws = self._multi = {}
         w = ws.get(k)
         if w is None:
-            import ctypes as C
-
             n_c = len(self.cont)
             w = ws[k] = dict(
                 tables=torch.empty((2, 3, self.grid.size, k, 2), dtype=torch.float64, device=self.dev),
@@ -1588,8 +1515,6 @@ class HotPathEngine:
         containers' aeff scales per point.  `plan` / `energy`: grid plan and node energies of the caller when the
         oscillation tables are not the engine's own (a Pipeline: osc.prob3 holds them).  Returns a list of K floats; the maps of the points stay in
         `last_many` (device tensors hist / sumw2 [K, n_cont, n_bins])."""
-        import ctypes as C
-
         n = len(params_list)
         if n == 0:
             return []
@@ -1605,8 +1530,6 @@ class HotPathEngine:
             finally:
                 self.points = pg
             return pg.gather(mine, n, self.dev)
-        plan = plan or self.plan
-        energy = energy if energy is not None else getattr(self, "energy_d", None)
         # (a single point goes point by point where the engine has oscillation tables of its own; with the caller's plan
         # -- a stage-built engine whose group was dealt one point of a stencil -- it takes the sweep path with K = 1)
         if (n == 1 and self.plan is not None) or not self.multi_capable(plan):
@@ -1614,8 +1537,7 @@ class HotPathEngine:
             out = []
             for i, p in enumerate(params_list):
                 if scales is not None:
-                    for name, sc in zip(self.names, scales[i]):
-                        self.set_scale(name, sc)
+                    self._set_scales(scales[i])
                 out.append(self.eval_host(p, kind))
             return out
         if n > _lib.MAX_POINTS:
@@ -1627,20 +1549,15 @@ class HotPathEngine:
         w = self._multi_ws(n)
         self._release_outputs()
         self._many_sweep(w, params_list, scales, plan, energy)
-        self._many_allreduce(w)
+        self.allreduce(w["limbs"])
         out = self._many_tail(w, n, kind)
         self.last_many = w
         return out
 
-    def _many_allreduce(self, w):
-        """int64 SUM of the K limb sets of a sweep over the ranks (as `allreduce`)"""
-        if self.world_size > 1:
-            if self._rccl is None:
-                self.allreduce_setup()
-            if self._rccl:
-                self._rccl.all_reduce_(w["limbs"], K._stream())
-            else:
-                allreduce_limbs(w["limbs"], self.world_size, self.group)
+    def _set_scales(self, row):
+        """the containers' aeff scales of one point: a row of the `scales` of `eval_many` / `maps_many`"""
+        for name, sc in zip(self.names, row):
+            self.set_scale(name, sc)
 
     def maps_many(self, params_list, scales=None, plan=None, energy=None):
         """The maps of all containers at K INDEPENDENT points, for `fisher_many`: per chunk of at most MAX_POINTS
@@ -1655,8 +1572,6 @@ class HotPathEngine:
         if n == 0:
             raise ValueError("maps_many: no points")
         n_c = len(self.cont)
-        plan = plan or self.plan
-        energy = energy if energy is not None else getattr(self, "energy_d", None)
         hist = torch.empty((n, n_c, self.n_bins), dtype=torch.float64, device=self.dev)
         sumw2 = torch.empty_like(hist)
         sweeps = 0
@@ -1664,23 +1579,20 @@ class HotPathEngine:
             assert self.plan is not None, "point-by-point evaluation needs the engine's own oscillation tables"
             for i, p in enumerate(params_list):
                 if scales is not None:
-                    for name, sc in zip(self.names, scales[i]):
-                        self.set_scale(name, sc)
+                    self._set_scales(scales[i])
                 self.accumulate(p)
                 self.allreduce()
                 h, s2 = self.finalize()
                 hist[i].copy_(h)
                 sumw2[i].copy_(s2)
         else:
-            import ctypes as C
-
             self._release_outputs()
             lib = _lib.lib()
             for i in range(0, n, _lib.MAX_POINTS):
                 k = min(_lib.MAX_POINTS, n - i)
                 w = self._multi_ws(k)
                 self._many_sweep(w, params_list[i:i + k], None if scales is None else scales[i:i + k], plan, energy)
-                self._many_allreduce(w)
+                self.allreduce(w["limbs"])
                 rc = lib.pisa_hip_hist_finalize(
                     C.c_void_p(w["limbs"].data_ptr()), k * n_c, self.n_bins, C.c_void_p(hist[i].data_ptr()),
                     C.c_void_p(sumw2[i].data_ptr()), C.c_void_p(self.ws.status.data_ptr()), K._stream())
@@ -1705,9 +1617,10 @@ class HotPathEngine:
         return res
 
     def _many_sweep(self, w, params_list, scales, plan, energy):
-        """prob3 of all points + ONE pass over the events into the points' limb sets (asynchronous)"""
-        import ctypes as C
-
+        """prob3 of all points + ONE pass over the events into the points' limb sets (asynchronous); `plan` /
+        `energy` default to the engine's own"""
+        plan = plan or self.plan
+        energy = energy if energy is not None else getattr(self, "energy_d", None)
         n = len(params_list)
         lib, s = _lib.lib(), K._stream()
         arr = w["params"]
@@ -1731,50 +1644,12 @@ class HotPathEngine:
         _lib.check(rc)
 
     def _many_tail(self, w, n, kind):
-        """maps + metric of the (all-reduced) limb sets, one workgroup per point; the values arrive in
-        pinned host memory"""
-        import ctypes as C
-
-        lib, s = _lib.lib(), K._stream()
+        """maps + metric of the (all-reduced) limb sets, one workgroup per point or four (the split tail); the
+        values arrive in pinned host memory"""
         h = w["host_np"]
         h[:] = np.nan
-        if kind == GPLLH:
-            _lib.check(self._gpllh_launch(n, C.c_void_p(w["limbs"].data_ptr()), C.c_void_p(w["hist"].data_ptr()),
-                                          C.c_void_p(w["sumw2"].data_ptr()), C.c_void_p(w["host"].data_ptr()), s))
-            w["zero"] = True
-            h = h[:n]
-            for _ in range(self.spin_wait):
-                if not np.isnan(h).any():
-                    return [float(v) for v in h]
-            torch.cuda.current_stream().synchronize()
-            return [float(v) for v in h]
-        if self._split_ok(kind):
-            _lib.check(lib.pisa_hip_finalize_metric_split(
-                C.c_void_p(w["limbs"].data_ptr()), n, len(self.cont), self.n_bins, C.c_void_p(w["hist"].data_ptr()),
-                C.c_void_p(w["sumw2"].data_ptr()), K.METRIC_KIND[kind], C.c_void_p(self.data.data_ptr()), None, 0, None,
-                C.c_void_p(w["host"].data_ptr()), C.c_void_p(self.ws.status.data_ptr()),
-                C.c_void_p(self.metric_status.data_ptr()), 1, s))
-            w["zero"] = True
-            h4 = h[:4 * n]
-            for _ in range(self.spin_wait):
-                if not np.isnan(h4).any():
-                    break
-            else:
-                torch.cuda.current_stream().synchronize()
-            p = h4.reshape(n, 4)
-            return [(float(q[0]) + float(q[2])) + (float(q[1]) + float(q[3])) for q in p]
-        h = h[:n]
-        _lib.check(lib.pisa_hip_finalize_metric_multi(
-            C.c_void_p(w["limbs"].data_ptr()), n, len(self.cont), self.n_bins, C.c_void_p(w["hist"].data_ptr()),
-            C.c_void_p(w["sumw2"].data_ptr()), K.METRIC_KIND[kind], C.c_void_p(self.data.data_ptr()), None, 0, None,
-            C.c_void_p(w["host"].data_ptr()), C.c_void_p(self.ws.status.data_ptr()),
-            C.c_void_p(self.metric_status.data_ptr()), 1, s))
-        w["zero"] = True      # the tail leaves the limbs zeroed for the next sweep
-        for _ in range(self.spin_wait):
-            if not np.isnan(h).any():
-                return [float(v) for v in h]
-        torch.cuda.current_stream().synchronize()
-        return [float(v) for v in h]
+        n_parts = self._launch_tail(kind, C.c_void_p(w["host"].data_ptr()), 4, w=w, n_points=n)
+        return self._join_parts(self._wait(h[:n * n_parts]).reshape(n, n_parts)).tolist()
 
     # -- the generalized Poisson-gamma likelihood (kind "generalized_poisson_llh") -----------------------
     def configure_gpllh(self, empty_bins=None):
@@ -1838,36 +1713,15 @@ class HotPathEngine:
             g["scratch_points"] = n_points
         return g
 
-    def _gpllh_launch(self, n_points, limbs, hist, sumw2, out, stream):
-        """the fused tail (`pisa_hip_finalize_gpllh`) of n_points limb sets; leaves the limbs zeroed"""
-        import ctypes as C
-
-        g = self._gpllh_tables(n_points)
-        return _lib.lib().pisa_hip_finalize_gpllh(
-            limbs, n_points, len(self.cont), self.n_bins, hist, sumw2, C.c_void_p(self.data.data_ptr()),
-            C.c_void_p(g["n_mc"].data_ptr()), C.c_void_p(g["adjust"].data_ptr()), K._ptr(g["empty"]),
-            C.c_void_p(g["per_bin"].data_ptr()), K._ptr(g["scratch"]), g["scratch_k"],
-            C.c_void_p(g["done"].data_ptr()), out, C.c_void_p(self.ws.status.data_ptr()),
-            C.c_void_p(self.metric_status.data_ptr()), 1, stream)
-
-    def _gpllh_tail(self, out):
-        """value of the current sums into `out` (device or pinned host tensor): the fused tail while the limbs
-        hold them, else alpha / beta / metric from the finalized maps (the same bits)"""
-        import ctypes as C
-
-        out_p = C.c_void_p(out.data_ptr())
-        if not self._maps_valid:
-            rc = self._gpllh_launch(1, C.c_void_p(self.ws.limbs.data_ptr()), C.c_void_p(self.ws.hist.data_ptr()),
-                                    C.c_void_p(self.ws.sumw2.data_ptr()), out_p, K._stream())
-            self._limbs_zero = self._maps_valid = rc == 0    # the engine's own limbs: consumed and zeroed
-            _lib.check(rc)
-            return
+    def _gpllh_from_maps(self, out):
+        """value of the finalized maps into `out` (device or pinned host tensor): alpha / beta / metric, the same
+        bits as the fused tail (`_launch_tail`) leaves while the limbs hold the sums"""
         g = self._gpllh_tables()
         alpha, beta, wsum = K.gpllh_params(self.ws.hist, self.ws.sumw2, g["n_mc"], g["adjust"])
         _lib.check(_lib.lib().pisa_hip_generalized_poisson_llh(
             C.c_void_p(self.data.data_ptr()), K._ptr(wsum), K._ptr(alpha), K._ptr(beta), K._ptr(g["n_mc"]),
             len(self.cont), self.n_bins, K._ptr(g["empty"]), K._ptr(g["scratch"]), g["scratch_k"],
-            C.c_void_p(g["per_bin"].data_ptr()), C.c_void_p(g["done"].data_ptr()), out_p,
+            C.c_void_p(g["per_bin"].data_ptr()), C.c_void_p(g["done"].data_ptr()), C.c_void_p(out.data_ptr()),
             C.c_void_p(self.metric_status.data_ptr()), K._stream()))
 
     def metric_status_host(self):

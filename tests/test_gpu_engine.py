@@ -727,19 +727,27 @@ def test_accumulate_launch_shape_does_not_change_a_bit(n_events):
     run_dev_case("launch_shape", n_events)
 
 
-@pytest.mark.parametrize("kw", [dict(compact=True), dict(compact=False), dict(compact=True, index16=False)],
-                         ids=["20B", "40B", "24B"])
+@pytest.mark.parametrize("kw", [dict(compact=True), dict(compact=False), dict(compact=True, index16=False),
+                                dict(compact=True, spin_wait=0), dict(compact=True, split_tail=False)],
+                         ids=["20B", "40B", "24B", "20B-stream-sync", "20B-one-workgroup"])
 def test_one_call_evaluation_equals_the_separate_calls(kw):
     """`pisa_hip_evaluator_eval` (prob3 -> accumulate -> tail enqueued and awaited inside ONE C-ABI call) against
     the three separate calls of the same entry points: the same launches, so the same bits -- llh / mod_chi2 through
     the four-workgroup tail, chi2 through the one-workgroup tail, after a change of a container's scale
-    (aeff.py:78-86), after new pseudo-data, and with the maps read back in between (limbs not zero)."""
+    (aeff.py:78-86), after new pseudo-data, and with the maps read back in between (limbs not zero).  The separate
+    calls also with their tail in one workgroup, its value polled (`split_tail = False`) or awaited by a stream
+    synchronisation (`spin_wait = 0`), and as the two phases `front` + `tail_host`."""
     from pisa_amd import synthetic
+
+    kw = dict(kw)
+    tail = {k: kw.pop(k) for k in ("spin_wait", "split_tail") if k in kw}
 
     wl = synthetic.Workload(n_events=120_000, grid=(40, 30), out_binning="dragon", seed=4)
     a = synthetic.DeviceState(wl, **kw)
     b = synthetic.DeviceState(wl, **kw)
     b.one_call = False
+    for k, v in tail.items():
+        setattr(b, k, v)
     data = a.make_pseudo_data(wl.osc_params(), seed=0)
     b.set_data(data)
     rs = np.random.RandomState(2)
@@ -748,6 +756,8 @@ def test_one_call_evaluation_equals_the_separate_calls(kw):
         for p in pts[:3]:
             va, vb = a.eval_host(p, kind), b.eval_host(p, kind)
             assert va == vb and np.isfinite(va), (kind, va, vb)
+        b.front()        # the two phases on the tables of the last point: the same launches once more
+        assert b.tail_host(kind) == vb, kind
     assert a._evaluator is not None and b._evaluator is None
     ha, hb = a.maps(), b.maps()
     assert np.array_equal(ha[0], hb[0]) and np.array_equal(ha[1], hb[1]) and ha[0].sum() > 0
