@@ -51,10 +51,11 @@ constexpr int64_t LDS_ACC_BYTES_MAX = 64 * 1024;
 //   digit[jj] = (|x| / 2^-116 >> 32 jj) & 0xffffffff,  jj = j, j-1, j-2,  j = slab of the leading bit,
 // each handed to add(jj, +-digit) as a signed 64-bit count of units 2^(32jj-116).  Integer additions are
 // associative, so sums of these counts are exact in any order as long as they fit 64 bits (2^31 events
-// per accumulator).  Two 64-bit shifts instead of three rounded add/subtract pairs: a third of the
-// instructions of `deposit`, which is what bounds the multi-point kernel.  |x| < 2^-116 deposits nothing;
-// digits below slab 0 are dropped (truncation towards zero; `deposit` rounds to nearest there -- the two
-// differ by less than 2^-116 per event).
+// per accumulator).  Two 64-bit shifts: a third of the instructions of the rounded add/subtract pairs that
+// cut a summand in csrc/kde.hip (`deposit` there), which is what bounds the multi-point kernel.  Every
+// histogram kernel of this file -- single point, several points, generic -- cuts with these two functions,
+// so all of them hold the same exact sums.  |x| < 2^-116 deposits nothing; digits below slab 0 are dropped
+// (truncation towards zero: x contributes sign(x) floor(|x| 2^116) units; tests/test_gpu_exact_accumulator.py).
 // LDS and global integer atomics with their own memory scopes: apart from being what is meant, the
 // different scopes keep the optimiser from merging an `in LDS ? ... : ...` pair of atomics into one
 // atomic on a generic pointer (which this compiler then fails to select).
@@ -794,9 +795,9 @@ hist_accumulate_kernel(const HistArgs a, unsigned long long *__restrict__ g_limb
 // as well).  The 20 B per event of the 16-bit index form do not depend on the point: this kernel reads
 // them ONCE, fetches the event's (P_e, P_mu) pairs of all KP points in one contiguous run of the
 // interleaved tables [sign][flavour][node][point], and deposits KP weights into KP sets of LDS
-// accumulators.  Per point the weight and its exact three-piece deposit are the single-point kernel's
-// (`deposit`, `slab_to_units`), so the limbs of every point are bit-identical to a
-// pisa_hip_reweight_hist call at that point (tests/test_gpu_multipoint.py).
+// accumulators.  Per point the weight and its exact three-digit deposit are the single-point kernel's
+// (`deposit_units`), so the limbs of every point hold the same sums as a pisa_hip_reweight_hist call
+// at that point (tests/test_gpu_multipoint.py, tests/test_gpu_exact_accumulator.py).
 constexpr int MULTI_KP_MAX = 8;   // points per launch (a larger batch is split into passes)
 
 struct MultiCont {

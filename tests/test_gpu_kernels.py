@@ -569,38 +569,9 @@ def test_limb_decoder_is_correctly_rounded_on_adversarial_accumulators(K, L):
 
     from pisa_amd.engine import limbs_to_float
 
-    rs = np.random.RandomState(9)
-    cases = []
-    cases.append([0] * 6)
-    cases.append([1, 0, 0, 0, 0, 0])                     # 2^-116
-    cases.append([-1, 0, 0, 0, 0, 0])
-    cases.append([0, 0, 0, 0, 0, 1 << 30])               # near the top of the range
-    cases.append([0, 0, 0, 0, 0, -(1 << 30)])
-    cases.append([0xFFFFFFFF] * 5 + [0])                 # carries everywhere
-    cases.append([-0xFFFFFFFF] * 5 + [1])                # borrows everywhere
-    cases.append([(1 << 62) - 1] * 6)                    # heavily un-normalised sums
-    cases.append([-(1 << 62)] * 5 + [1 << 20])
-    # ties: a 54-bit pattern whose lowest bit is exactly half an ulp, placed at several offsets
-    for shift in (0, 5, 31, 32, 40, 63, 64, 77, 100):
-        for mant in ((1 << 53) | 1, (1 << 53) | 3, (1 << 54) - 1, (1 << 53) + 2 + 1):
-            for sticky in (0, 1):
-                for sign in (1, -1):
-                    total = sign * ((mant << (shift + 1)) + (sticky if shift > 0 else 0))
-                    limbs, t = [], total
-                    for _ in range(5):
-                        limbs.append(t & 0xFFFFFFFF)
-                        t >>= 32
-                    limbs.append(t)
-                    if abs(limbs[5]) < (1 << 62):
-                        cases.append(limbs)
-    for _ in range(3000):
-        bits = rs.randint(1, 63, size=6)
-        vals = [int(rs.randint(0, 2 ** 31)) << 31 | int(rs.randint(0, 2 ** 31)) for _ in range(6)]
-        limbs = [(v & ((1 << int(b)) - 1)) * (1 if rs.rand() < 0.6 else -1) for v, b in zip(vals, bits)]
-        if rs.rand() < 0.3:
-            for k in rs.choice(6, size=rs.randint(1, 5), replace=False):
-                limbs[k] = 0
-        cases.append(limbs)
+    from tests.limb_cases import adversarial_accumulators
+
+    cases = adversarial_accumulators()
     n = len(cases)
     want = np.array([limbs_to_float(c) for c in cases])
     ok = np.isfinite(want) & (np.abs(want) < 2.0 ** 76)      # the accumulators' range: 6 x 32 - 116 bits

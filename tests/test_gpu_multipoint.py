@@ -8,20 +8,9 @@ import numpy as np
 import pytest
 import torch
 
+from tests.limb_cases import canonical as _canonical
+
 pytestmark = pytest.mark.gpu
-
-
-def _canonical(limbs):
-    """carry-normalised digits of every accumulator: limbs [..., 6] int64 (un-normalised sums of signed
-    digits) -> the unique representation with digits 0 .. 2^32 - 1 below a signed top digit.  Two limb
-    sets describe the same exact sums iff these agree (the sweep kernel and the single-point kernel cut a
-    weight into digits differently: truncated shifts against rounded add/subtract pairs)."""
-    out = limbs.clone()
-    for j in range(out.shape[-1] - 1):
-        carry = out[..., j] >> 32          # arithmetic shift: floor division
-        out[..., j] -= carry << 32
-        out[..., j + 1] += carry
-    return out
 
 
 def _points(wl, n, seed=11, **kw):
