@@ -943,7 +943,7 @@ int pisa_hip_barr_simple_multi(const pisa_hip_barr_set *h_sets, int32_t n_sets,
  * pisa_hip_barr_factors (once per event set): the parts of apply_sys_vectorized (:147-233) that depend on
  *   (E, coszen) only -- d_factors[5][n] = ModFlux(nue), ModFlux(numu), the energy and the zenith factor of
  *   the up/horizontal Gaussian, log(E / E_pivot); d_status (int32, may be NULL) is set if an energy is not
- *   positive (such a set must use the two-pass calls, which keep the reference's answers there).
+ *   positive and finite (such a set must use the two-pass calls, which keep the reference's answers there).
  * pisa_hip_barr_fold_multi (per moved systematic): every array of a set in the SAME order and layout as
  *   d_out -- the engine's resident order, e.g. the quad-blocked d_weighted_flux_q --
  *   d_out[p] = d_static_w[p] * apply_sys(nominal fluxes[p], factors[p]; parameters): the bits of the two

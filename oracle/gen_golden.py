@@ -17,6 +17,7 @@ Outputs (all numpy .npz, inputs + expected outputs only -- no reference text):
   lookup_ref.npz          reference lookup_regular_* outputs
   stats_ref.npz           reference stats.llh/poisson_llh/chi2/mod_chi2
   barr_ref.npz            reference barr_simple.apply_sys_kernel
+  barr_wide_ref.npz       the same at 0.1 GeV .. 100 TeV: the clamp of modRatioNuBar, the NaN flux pairs
   hist_ref.npz            np.histogramdd recipe of translation.test_histogram
   stats_wide_ref.npz      reference stats.mcllh_mean / mcllh_eff / correct_chi2 / signed_sqrt_mod_chi2 / conv_llh
   side_stages_ref.npz     the services around the path: reference two_nu_osc.apply_probs_vectorized,
@@ -350,6 +351,35 @@ def gen_barr():
                 bs.apply_sys_kernel(e[i], cz[i], nu[i], nub[i], nubar, *ps, o[i])
             out["out%d_%s" % (ip, "nu" if nubar > 0 else "nubar")] = o
     save("barr_ref.npz", **out)
+    # beyond 1 TeV, where modRatioNuBar's max(0, .) clamps (Barr_nu_nubar_ratio = -2: from about 5 TeV), the
+    # flux pairs that give NaN, parameter values of 0.  Positive finite energies only: run as plain Python a
+    # negative base to a fractional power is not what the compiled reference gives.
+    rs = np.random.RandomState(12)
+    n = 1024
+    e = 10 ** (rs.rand(n) * 6 - 1)                       # 0.1 GeV .. 100 TeV
+    cz = rs.rand(n) * 2 - 1
+    cz[:3] = [-1.0, 0.0, 1.0]
+    nu = rs.rand(n, 2) * 10
+    nub = rs.rand(n, 2) * 10
+    nu[:5] = [(0, 0), (0, 1), (1, 0), (1, 0), (0, 0)]
+    nub[:5] = [(0, 0), (0, 1), (0, 0), (1, 0), (1, 1)]
+    out = dict(true_energy=e, true_coszen=cz, nu_flux_nominal=nu, nubar_flux_nominal=nub)
+    psets = [
+        (1.2, 0.7, 0.3, 2.0, -2.0),      # reaches the clamp
+        (0.5, 2.0, -0.3, -2.0, 2.0),
+        (1.03, 0.9, 0.05, 0.0, -0.4),    # Barr_uphor_ratio = 0
+        (0.0, 1.1, -0.1, 0.7, 1.0),      # nue_numu_ratio = 0
+        (0.9, 1.0, 0.1, -0.6, -1.3),
+        (1.0, 1.0, 0.0, 0.0, 0.0),
+    ]
+    out["params"] = np.array(psets)
+    for ip, ps in enumerate(psets):
+        for nubar in (1, -1):
+            o = np.zeros((n, 2))
+            for i in range(n):
+                bs.apply_sys_kernel(e[i], cz[i], nu[i], nub[i], nubar, *ps, o[i])
+            out["out%d_%s" % (ip, "nu" if nubar > 0 else "nubar")] = o
+    save("barr_wide_ref.npz", **out)
 
 
 def gen_hist():

@@ -327,8 +327,8 @@ __device__ __forceinline__ double2 barr_from_factors(const BarrFactors &F, doubl
     apply_ratio_scale(nue_numu_ratio, fb.x, fb.y, nb0, nb1);
     // (E / E_pivot)^delta_index (barr_simple.py:39-45): exp(delta log x) for the energies that exist
     // (same value to two ulp, a third cheaper than the general pow); pow keeps the reference's answers
-    // for E <= 0 and NaN
-    double idx_scale = x_piv > 0.0 ? exp(delta_index * F.lx) : pow(x_piv, delta_index);
+    // for E <= 0, NaN and +inf (inf^0 = 1, where exp(0 * log(inf)) is NaN)
+    double idx_scale = (x_piv > 0.0 && x_piv < HUGE_VAL) ? exp(delta_index * F.lx) : pow(x_piv, delta_index);
     nu0 *= idx_scale; nu1 *= idx_scale; nb0 *= idx_scale; nb1 *= idx_scale;
     double e0, e1, m0, m1;
     apply_ratio_scale(nu_nubar_ratio, nu0, nb0, e0, e1);  // nue: (nu, nubar)
@@ -370,7 +370,7 @@ barr_factors_kernel(const double *__restrict__ e, const double *__restrict__ cz,
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const double ei = e[i];
-    if (!(ei > 0.0) && status) atomicOr(status, 1);   // the one-pass form is for energies that exist
+    if (!(ei > 0.0 && ei < HUGE_VAL) && status) atomicOr(status, 1);   // the one-pass form is for energies that exist
     const BarrFactors f = barr_factors(ei, cz[i]);
     out[i] = f.mf0; out[n + i] = f.mf1; out[2 * n + i] = f.ll_uh; out[3 * n + i] = f.ex_uh; out[4 * n + i] = f.lx;
 }

@@ -1000,7 +1000,7 @@ class HotPathEngine:
             d.nubar = int(self.cont[i].nubar)
             keep += [nu_b, nub_b, fac, w_b]
         if int(status.item()) != 0:
-            raise ValueError("true_energy must be positive for the one-pass flux refresh")
+            raise ValueError("true_energy must be positive and finite for the one-pass flux refresh")
         self._barr = dict(arr=arr, keep=keep, fn=lib.pisa_hip_barr_fold_multi)
 
     def update_flux_barr(self, nue_numu_ratio, nu_nubar_ratio, delta_index, Barr_uphor_ratio, Barr_nu_nubar_ratio):

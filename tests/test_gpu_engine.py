@@ -712,6 +712,10 @@ def test_one_pass_flux_refresh_is_the_two_pass_refresh(index16):
     bad[0] = (e0,) + cols[0][1:]
     with pytest.raises(ValueError):
         b.enable_barr(bad)
+    # nor has an infinite one: exp(delta log inf) is not the reference's pow(inf, delta) at delta = 0
+    e0[3] = float("inf")
+    with pytest.raises(ValueError, match="positive and finite"):
+        b.enable_barr(bad)
 
 
 @pytest.mark.parametrize("n_events", [13, 4099, 250_007])
