@@ -32,9 +32,10 @@ inline int check_hip(hipError_t e, const char *what) {
     } while (0)
 
 // Development probes.  The product library reads NO environment variable and has no switch that makes a kernel do
-// less work: every run-time selection of a kernel form used while developing (scripts/dev/*) exists only in builds
-// made with `make EXTRA=-DPISA_DEV_PROBES`.  In the default build PISA_DEV_INT(name, dflt) is the constant `dflt`
-// (the name never reaches the binary: tests/test_abi.py checks `strings libpisa_hip.so`).
+// less work: every run-time selection of a kernel form or launch shape (tests/dev_cases.py, scripts/dev/*) exists
+// only in the development library (`make dev`: -DPISA_DEV_PROBES).  In the default build PISA_DEV_INT(name, dflt) is
+// the constant `dflt` (the name never reaches the binary: tests/test_abi.py checks `strings libpisa_hip.so`).
+// A switch is kept only while a test or a kept script sets it: a form that nothing selects is deleted, not switched off.
 #ifdef PISA_DEV_PROBES
 #include <stdlib.h>
 inline long long dev_env_ll(const char *name, long long dflt) {
@@ -52,22 +53,6 @@ inline const char *dev_env_str(const char *name) { return getenv(name); }
 #endif
 
 inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
-
-// Cross-kernel hand-over of the oscillation tables (development builds only, evaluator.hip: the round-6 experiment
-// "accumulate kernel resident and polling while the chain kernel runs", EXPERIMENTS R6-3).  The evaluator sets
-// `g_chain_signal` before the one-point chain launch -- one lane of each of its workgroups then adds 1 to counter
-// (linear workgroup index mod HANDOVER_SLOTS) behind an agent-scope release, the launch code leaves its workgroup count in
-// `n_wg` -- and `g_hist_wait` before the accumulate launch, whose workgroups poll all counters for epoch x (workgroups of
-// that slot) between their first column loads and their first table gathers.
-constexpr int HANDOVER_SLOTS = 64;
-struct HandOver {
-    unsigned long long *flags;   // HANDOVER_SLOTS counters, never reset
-    unsigned long long epoch;    // chain launches that have signalled so far (this one included)
-    int n_wg;                    // workgroups of one chain launch
-};
-#ifdef PISA_DEV_PROBES
-extern thread_local HandOver g_chain_signal, g_hist_wait;
-#endif
 
 // Regular (linear, equal-width) binning as the kernels see it
 // (fast_histogram rule / translation.py:417-456): bin = (int)((x - min) * norm)

@@ -208,13 +208,8 @@ struct HistArgs {
     int32_t cont_chunk[MAX_CONT];   // > 0: events per workgroup of this container / 256 (instead of `chunk`)
     int32_t copies;       // LDS replicas of the accumulators (power of two), lane-interleaved
     int32_t opts;         // 1: the caller has no use for the second quantity (plain histogram without counts).
-                          // Builds with -DPISA_DEV_PROBES only (PISA_HIP_HIST_DBG): 2 no deposits, 4 no flush
+                          // Development library only (PISA_HIP_HIST_DBG): 2 no deposits, 4 no flush
     int32_t window;       // > 0: LDS holds this many bins starting at the chunk's lowest bin
-    // development builds (common.hpp, HandOver): the tables this launch gathers from are being written by a kernel that
-    // runs BESIDE it; poll these counters before the first gather
-    const unsigned long long *wait_flags;
-    unsigned long long wait_epoch;
-    int32_t wait_wgs;
 };
 
 // MODE 0: generic histogram (weights or counts; quantities (w, 1))
@@ -347,27 +342,6 @@ hist_accumulate_kernel(const HistArgs a, unsigned long long *__restrict__ g_limb
         __syncthreads();
     }
     bool bad = false;
-#ifdef PISA_DEV_PROBES
-    if (a.wait_flags) {
-        // consumer side of the hand-over (guide, "valid forms"): relaxed agent-scope polls by the first wavefront (one counter
-        // per lane), ONE agent acquire, its wait, workgroup barrier, then plain loads of the tables
-        if (threadIdx.x < HANDOVER_SLOTS) {
-            const int k = (int)threadIdx.x;
-            const unsigned long long need = a.wait_epoch * (unsigned long long)(a.wait_wgs / HANDOVER_SLOTS + (k < a.wait_wgs % HANDOVER_SLOTS ? 1 : 0));
-            const unsigned long long t0 = wall_clock64();
-            while (__hip_atomic_load(a.wait_flags + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < need) {
-                if (wall_clock64() - t0 > 100000000ull) {   // ~1 s of the 100 MHz counter: the producer is not coming
-                    if (status) atomicOr(status, 8);
-                    break;
-                }
-                __builtin_amdgcn_s_sleep(2);
-            }
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-        __syncthreads();
-    }
-#endif
     STAMP(2);
 
     auto accumulate = [&](int bin, double w, double w2) {
@@ -1341,7 +1315,7 @@ static int run_hist(const ContDev *conts, int n_cont, int mode, const DevBinning
     int64_t lds_bytes = lds_acc_bytes(n_bins);
     bool lds = lds_bytes <= LDS_ACC_BYTES_MAX;
     int window = 0;
-    if (!lds && (mode == 3 || mode == 5 || mode == 7) && !PISA_DEV_INT("HIST_NO_WINDOW", 0)) {
+    if (!lds && (mode == 3 || mode == 5 || mode == 7)) {
         // binning too large for LDS: accumulate a window of it (see the kernel)
         // a multiple of 32 bins: the LDS bank pair of an accumulator is then (bin - bin_lo) mod 32
         // whatever the slab and quantity, which the bank-aware event order relies on
@@ -1372,16 +1346,6 @@ static int run_hist(const ContDev *conts, int n_cont, int mode, const DevBinning
         a.prob[1] = prob_nubar;
         a.pepmu = reinterpret_cast<const double2 *>(pepmu);
         a.opts = (PISA_DEV_INT("HIST_DBG", 0) & ~1) | (second_quantity ? 0 : 1);
-        a.wait_flags = nullptr;
-        a.wait_epoch = 0;
-        a.wait_wgs = 0;
-#ifdef PISA_DEV_PROBES
-        if (g_hist_wait.flags) {
-            a.wait_flags = g_hist_wait.flags;
-            a.wait_epoch = g_hist_wait.epoch;
-            a.wait_wgs = g_hist_wait.n_wg;
-        }
-#endif
         int64_t nev[MAX_CONT];
         for (int c = 0; c < nc; c++) {
             a.cont[c] = conts[base + c];
@@ -1433,8 +1397,8 @@ static int run_hist(const ContDev *conts, int n_cont, int mode, const DevBinning
         if (g_prof_start) PISA_TRY_HIP(hipEventRecord(g_prof_start, s));
 #define LAUNCH(M, L) hipLaunchKernelGGL((hist_accumulate_kernel<M, L>), grid_dim, block, shmem, s, a, out, d_status)
         if (mode == 7) LAUNCH(7, true);
-        else if (mode == 5) { if (lds) LAUNCH(5, true); else LAUNCH(5, false); }
-        else if (mode == 3) { if (lds) LAUNCH(3, true); else LAUNCH(3, false); }
+        else if (mode == 5) LAUNCH(5, true);    // (modes 3, 5 and 7: all bins or a window of them in LDS, see above)
+        else if (mode == 3) LAUNCH(3, true);
         else if (mode == 2) { if (lds) LAUNCH(2, true); else LAUNCH(2, false); }
         else if (mode == 1) {
             // dimensions as template parameters (uniform branches around the loads and 64-bit index
@@ -1531,8 +1495,7 @@ static int reweight_hist_impl(const pisa_hip_container *h_containers, int32_t n_
     bool all_compact = any_table;
     // the 16-bit index form needs 16-bit node / bin numbers; where it does not apply its columns
     // are ignored (the other forms, if given, are used)
-    const bool ok16 = n_nodes < 0xffff && n_bins < 0xffff &&
-                      (lds_acc_bytes(n_bins) <= LDS_ACC_BYTES_MAX || !PISA_DEV_INT("HIST_NO_WINDOW", 0));
+    const bool ok16 = n_nodes < 0xffff && n_bins < 0xffff;
     bool all_idx16 = any_table && ok16;
     for (int c = 0; c < n_containers; c++) {
         const pisa_hip_container &h = h_containers[c];
@@ -1624,7 +1587,7 @@ static int launch_multi(const MultiArgs &a, int nblocks, size_t shmem, unsigned 
 
 PISA_API int pisa_hip_multi_points_per_pass(int64_t n_bins) {
     if (n_bins < 1) return 0;
-    int64_t lds_max = (int64_t)PISA_DEV_INT("MULTI_LDS_KB", 128) * 1024;
+    int64_t lds_max = 128 * 1024;
     if (lds_max > device_lds_bytes() - 256) lds_max = device_lds_bytes() - 256;   // a part with 64 KiB LDS: fewer points per pass
     int64_t kp = lds_max / lds_acc_bytes(n_bins);
     if (kp > MULTI_KP_MAX) kp = MULTI_KP_MAX;
@@ -1661,7 +1624,7 @@ PISA_API int pisa_hip_reweight_hist_multi(const pisa_hip_container *h_containers
         const int kp = (n_points - k0 + (n_pass - pass) - 1) / (n_pass - pass);   // passes of equal size
         // workgroups: what is resident at once.  From two points on the kernel needs more than 64 VGPRs,
         // a CU holds ONE 1024-thread workgroup, and a second round of workgroups would only add a tail
-        const int64_t target_blocks = PISA_DEV_INT("MULTI_BLOCKS", device_cus());
+        const int64_t target_blocks = device_cus();
         for (int base = 0; base < n_containers; base += MAX_CONT) {
             const int nc = n_containers - base < MAX_CONT ? n_containers - base : MAX_CONT;
             MultiArgs a;

@@ -32,9 +32,11 @@
 // and pair of queries).
 //
 // On top of the cell list, in 2-D with a cut-off (the KDE stage's case):
-// * the PILOT is a fast Gauss transform: Hermite series of every non-empty cell (`kde_hermite_coef_kernel`),
-//   translated into one local expansion per target cell in two separable passes over the cell grid
-//   (`kde_h2l4_kernel<P, 0 / 1>`), evaluated with P^2 multiply-adds per target (`kde_local_pilot_kernel`);
+// * the PILOT is a fast Gauss transform: Hermite series of every non-empty cell, translated into one local
+//   expansion per target cell in two separable passes over the cell grid, evaluated with P^2 multiply-adds per
+//   target.  Series order P <= 16: on the matrix cores (`kde_hermite_coef_mfma_kernel`, `kde_h2l_mfma_kernel<0 / 1>`,
+//   `kde_local_pilot_wave_kernel`); P > 16: on the vector units (`kde_hermite_coef_kernel`,
+//   `kde_h2l4_kernel<P, 0 / 1>`, `kde_local_pilot_kernel`);
 // * a map is evaluated on the LATTICE of its points (`pisa_hip_kde_evaluate_lattice`, `kde_lattice_kernel`): along a
 //   lattice line the kernel values of a source follow g_{c+-k} = g_c r^k Q_k, one multiply and one multiply-add each;
 // * the estimators of one evaluation of the stage run as one job list on the library's own threads and streams
@@ -1479,136 +1481,19 @@ constexpr int H2L_MAX_REACH = 12;
 // The translation is done in two separable passes over the cell grid (like a separable
 // convolution), with the SQUARE |d1|, |d2| <= reach of source cells instead of the disc -- the cells
 // of the square outside the cut-off disc only add their (correct, below-tolerance) contributions:
-//   pass 0   V[cy_C][cx_B] = sum_{cy_B} A^(cx_B, cy_B) H(d2)^T          one workgroup per (cx_B, cy_C)
-//   pass 1   L[C]          = D (sum_{cx_B} H(d1) V[cy_C][cx_B]) D       one workgroup per target cell
+//   pass 0   V[cy_C][cx_B] = sum_{cy_B} A^(cx_B, cy_B) H(d2)^T          per (cx_B, cy_C)
+//   pass 1   L[C]          = D (sum_{cx_B} H(d1) V[cy_C][cx_B]) D       per target cell
 // 2 (2 reach + 1) P^3 multiply-adds per cell instead of (cells in the disc + columns) P^3.
-// Each thread owns a 2 x 2 tile of the P x P result ((P/2)^2 threads of a 128-thread workgroup): a
-// multiply-add then costs 0.75 LDS reads instead of 2 (one element per thread: the kernel waited for
-// the LDS pipe, 3 TFLOP/s).  Every element is still summed in the same order (offsets ascending, inner
-// index ascending): same bits.
-constexpr int H2L_THREADS = 128;
-template <int P, int PASS>
-__global__ void __launch_bounds__(H2L_THREADS)
-kde_h2l_kernel(KdeGeom g, const int32_t *__restrict__ tcells, const int32_t *__restrict__ slot,
-               const double *__restrict__ herm, const double *__restrict__ hankel, int reach,
-               double *__restrict__ V, uint8_t *__restrict__ vflag, double *__restrict__ local) {
-    static_assert(P % 2 == 0, "2 x 2 tiles");
-    constexpr int NH = 2 * P - 1, H = P / 2, PP = P * P;
-    constexpr int PER = (PP + H2L_THREADS - 1) / H2L_THREADS;   // matrix elements a thread stages
-    __shared__ double sA[PP];
-    __shared__ double sH[(2 * H2L_MAX_REACH + 1) * NH];
-    const int t = threadIdx.x;
-    const bool act = t < H * H;
-    const int ti = act ? t / H : 0, tj = act ? t % H : 0;
-    for (int i = t; i < (2 * reach + 1) * NH; i += H2L_THREADS) sH[i] = hankel[i];
-    const int nx = g.nc[0], ny = g.nc[1];
-    const int c = PASS == 0 ? (int)blockIdx.x : tcells[blockIdx.x];
-    const int cx = c % nx, cy = c / nx;
-    double a00 = 0.0, a01 = 0.0, a10 = 0.0, a11 = 0.0;
-    bool any = false;
-    // source matrix of offset o, or nullptr (workgroup-uniform)
-    auto source = [&](int o) -> const double * {
-        if (o > reach) return nullptr;
-        if (PASS == 0) {                 // source cell (cx, cy - o): d2 = o * cell_u
-            const int cyB = cy - o;
-            if (cyB < 0 || cyB >= ny) return nullptr;
-            const int sl = slot[(int64_t)cyB * nx + cx];
-            return sl < 0 ? nullptr : herm + (int64_t)sl * PP;
-        }
-        const int cxB = cx - o;          // column cx - o of row cy: d1 = o * cell_u
-        if (cxB < 0 || cxB >= nx) return nullptr;
-        const int64_t cb = (int64_t)cy * nx + cxB;
-        return vflag[cb] ? V + cb * PP : nullptr;
-    };
-    auto fetch = [&](const double *src, double (&buf)[PER]) {
-#pragma unroll
-        for (int u = 0; u < PER; u++) {
-            const int e = t + u * H2L_THREADS;
-            buf[u] = (src && e < PP) ? src[e] : 0.0;
-        }
-    };
-    // The matrices are 3.2 KB each and come from the L2 / HBM: the next one is requested before the
-    // current one is multiplied.
-    int o = -reach;
-    const double *src = source(o);
-    while (!src && o <= reach) src = source(++o);
-    double mine[PER], ahead[PER];
-    fetch(src, mine);
-    while (src) {
-        int on = o + 1;
-        const double *nxt = source(on);
-        while (!nxt && on <= reach) nxt = source(++on);
-        fetch(nxt, ahead);
-        any = true;                      // workgroup-uniform
-        __syncthreads();
-#pragma unroll
-        for (int u = 0; u < PER; u++) {
-            const int e = t + u * H2L_THREADS;
-            if (e < PP) sA[e] = mine[u];
-        }
-        __syncthreads();
-        if (act) {
-            const double *hk = sH + (o + reach) * NH;
-            if (PASS == 0) {             // W[alpha][l] += sum_beta A[alpha][beta] h_{beta + l}(d2)
-                const double *r0 = sA + (2 * ti) * P, *r1 = r0 + P, *h = hk + 2 * tj;
-#pragma unroll
-                for (int b = 0; b < P; b++) {
-                    const double A0 = r0[b], A1 = r1[b], h0 = h[b], h1 = h[b + 1];
-                    a00 = __builtin_fma(A0, h0, a00);
-                    a01 = __builtin_fma(A0, h1, a01);
-                    a10 = __builtin_fma(A1, h0, a10);
-                    a11 = __builtin_fma(A1, h1, a11);
-                }
-            } else {                     // L[k][l] += sum_alpha h_{alpha + k}(d1) V[alpha][l]
-                const double *h = hk + 2 * ti, *v = sA + 2 * tj;
-#pragma unroll
-                for (int a = 0; a < P; a++) {
-                    const double h0 = h[a], h1 = h[a + 1], v0 = v[a * P], v1 = v[a * P + 1];
-                    a00 = __builtin_fma(h0, v0, a00);
-                    a01 = __builtin_fma(h0, v1, a01);
-                    a10 = __builtin_fma(h1, v0, a10);
-                    a11 = __builtin_fma(h1, v1, a11);
-                }
-            }
-        }
-        src = nxt;
-        o = on;
-#pragma unroll
-        for (int u = 0; u < PER; u++) mine[u] = ahead[u];
-    }
-    const double acc[2][2] = {{a00, a01}, {a10, a11}};
-    if (PASS == 0) {
-        if (t == 0) vflag[c] = any ? 1 : 0;
-        if (act && any) {
-#pragma unroll
-            for (int di = 0; di < 2; di++)
-#pragma unroll
-                for (int dj = 0; dj < 2; dj++)
-                    V[(int64_t)c * PP + (2 * ti + di) * P + 2 * tj + dj] = acc[di][dj];
-        }
-    } else if (act) {
-#pragma unroll
-        for (int di = 0; di < 2; di++)
-#pragma unroll
-            for (int dj = 0; dj < 2; dj++) {
-                const int r0 = 2 * ti + di, r1 = 2 * tj + dj;
-                // D_k D_l = (-1)^(k+l) / (k! l!)
-                double fk = 1.0, fl = 1.0;
-                for (int i = 2; i <= r0; i++) fk *= (double)i;
-                for (int i = 2; i <= r1; i++) fl *= (double)i;
-                const double sgn = ((r0 + r1) & 1) ? -1.0 : 1.0;
-                local[(int64_t)blockIdx.x * PP + r0 * P + r1] = sgn * acc[di][dj] / (fk * fl);
-            }
-    }
-}
-
-// The same two passes with FOUR consecutive targets of the convolution direction per workgroup and a 4 x 4
-// register tile per thread (25 tiles x 4 targets = 100 of 128 threads): a source matrix is staged to LDS once
-// for the up to four targets that use it (with four different Hankel rows), and a thread reads 5 LDS values per
-// 16 multiply-adds (the Hankel window slides in registers) instead of 3 per 4.  Every element is summed in the
-// order of the kernel above (offsets ascending = sources descending, inner index ascending): same bits.
+// Every element is summed in ONE order whatever the launch shape (offsets ascending = sources descending,
+// inner index ascending): same bits.
+//
+// A workgroup takes FOUR consecutive targets of the convolution direction, a thread a 4 x 4 register tile
+// (25 tiles x 4 targets = 100 of 128 threads): a source matrix is staged to LDS once for the up to four
+// targets that use it (with four different Hankel rows), and a thread reads 5 LDS values per 16 multiply-adds
+// (the Hankel window slides in registers).
 //   pass 0   grid (nx, ceil(ny / 4)):  V[cy_C][cx] for cy_C = 4 q .. 4 q + 3
 //   pass 1   grid (ceil(nx / 4), ny):  L[head of (cx_C, cy)] for cx_C = 4 q .. 4 q + 3 (cells with sources only)
+constexpr int H2L_THREADS = 128;
 constexpr int H2L4_T = 4;
 template <int P, int PASS>
 __global__ void __launch_bounds__(H2L_THREADS)
@@ -2460,8 +2345,7 @@ PISA_API int pisa_hip_kde_create(int32_t dim, const double *d_x, const double *d
     while (bits < 32 && ((int64_t)1 << bits) < k->n_cells) bits++;
     // cell and source index in one 32-bit word where both fit ((cell << pack) | index): the sort moves keys only -- half the
     // bytes per pass --, sorted on the cell's bits; the order is the stable order of the pair sort (the indices ascend)
-    static const int pack_ok = PISA_DEV_INT("KDE_SORT_PACK", 1);
-    const int pack = (pack_ok && bits < 32 && n <= ((int64_t)1 << (32 - bits))) ? (int)(32 - bits) : 0;
+    const int pack = (bits < 32 && n <= ((int64_t)1 << (32 - bits))) ? (int)(32 - bits) : 0;
     KDE_D(kde_whiten_flat_kernel, dim3(nb), dim3(256), 0, s, d_x, d_w, n, g, rec, flat_a, idx_a, pack);
 #ifdef PISA_DEV_PROBES
     {   // development (EXPERIMENTS R6-7): N empty launches per estimator -- is the evaluation bound by the number of runtime calls?
@@ -2550,7 +2434,7 @@ PISA_API int pisa_hip_kde_create(int32_t dim, const double *d_x, const double *d
         // target, so every non-empty cell gets one; evaluated target by target (no local expansions) a
         // series pays from ~24 sources
         const int dense_min = local_ok ? hermite_min() : std::max(hermite_min(), HERMITE_MIN_SERIES);
-        static const int64_t expansion_min_n = (int64_t)PISA_DEV_LL("KDE_EXPANSION_MIN_N", 1000);
+        constexpr int64_t expansion_min_n = 1000;
         // (1 000: C3-shaped evaluations of 1e5 / 3e5 events take 11.5 / 27.5 ms with the round-2 threshold of 20 000 sources per
         //  estimator -- direct pair sums below it --, 5.7 / 5.9 ms with this one)
         if (g_kde_expansion && dim == 2 && cut && n >= expansion_min_n) {
@@ -2570,10 +2454,10 @@ PISA_API int pisa_hip_kde_create(int32_t dim, const double *d_x, const double *d
             // Hermite / local coefficients live in a grow-only scratch of the library (up to
             // 3.2 KB per cell: sized by what this call needs, not by the workspace's worst case)
             const size_t pp = (size_t)(P * P);
-            // translation passes in H2L_SPLIT parts of the source positions (see kde_h2l4_kernel): V, its flags and the local
-            // expansions once per part
-            // translation passes: 2 = on the matrix cores where the series order allows (<= 16), 1 = four targets per
-            // workgroup on the vector units, 0 = one target per workgroup
+            // translation passes: on the matrix cores where the series order allows (<= 16), in one part; else four targets
+            // per workgroup on the vector units, in two parts of the source positions (see kde_h2l4_kernel): V, its flags
+            // and the local expansions once per part
+            const int h2l_split = P <= 16 ? 1 : 2;
             unsigned long long *pstamps = nullptr;
 #ifdef PISA_DEV_PROBES
             const size_t n_pstamps = (size_t)n_blocks * (Q_CHUNK / 64);
@@ -2583,11 +2467,6 @@ PISA_API int pisa_hip_kde_create(int32_t dim, const double *d_x, const double *d
                 KDE_TRY_HIP(hipMemsetAsync(pstamps, 0, n_pstamps * 32, s));
             }
 #endif
-            static const int pilot_form = PISA_DEV_INT("KDE_PILOT_FORM", 1);   // 1 = the local expansions a wavefront per block (where they are all there is)
-            static const int h2l_form_cfg = PISA_DEV_INT("KDE_H2L_FORM", 2);
-            const int h2l_form = h2l_form_cfg == 2 && P > 16 ? 1 : h2l_form_cfg;
-            static const int h2l_split_cfg = PISA_DEV_INT("KDE_H2L_SPLIT", 2);
-            const int h2l_split = h2l_form == 2 ? 1 : (h2l_split_cfg >= 1 && h2l_split_cfg <= 8 ? h2l_split_cfg : 2);
             const size_t need = (nd * pp + (local_exp ? h2l_split * (n_heads + (size_t)k->n_cells) * pp + (2 * reach + 1) * (2 * P - 1) : 0))
                                 * sizeof(double) + (local_exp ? (size_t)h2l_split * k->n_cells : 0) + 8192;
             double *herm = nullptr;
@@ -2646,49 +2525,57 @@ PISA_API int pisa_hip_kde_create(int32_t dim, const double *d_x, const double *d
                 }
             }
             dim3 grid((unsigned)n_blocks, (unsigned)n_split);
-#define KDE_FGT(PP) do { \
-                if (local_exp && h2l_form == 2) /* (the matrix-core translation reads the coefficients transposed: the two go together) */ \
-                    hipLaunchKernelGGL(kde_hermite_coef_mfma_kernel, dim3((unsigned)nd), dim3(64 * FGT_WAVES), 0, s, g, d_dense, nd, \
-                                       k->cell_start, k->ys, n, k->coef, PP, herm); \
+            // no local expansions: the Hermite series evaluated target by target
+#define KDE_SERIES(PP) do { \
+                hipLaunchKernelGGL(kde_hermite_coef_kernel<PP>, dim3((unsigned)nd), dim3(HC_THREADS), 0, s, g, d_dense, \
+                                   k->cell_start, k->ys, n, k->coef, herm); \
+                hipLaunchKernelGGL(kde_hermite_pilot_kernel<PP>, grid, dim3(KDE_THREADS), 0, s, g, d_blocks, \
+                                   k->ys, n, k->coef, k->cell_start, slot, herm, n_split, part, k->pair_count); \
+            } while (0)
+            // P <= 16 (the matrix-core translation reads the coefficients transposed: the two go together); where the local
+            // expansions are all there is, a wavefront per block evaluates them
+#define KDE_LOCAL_MFMA(PP) do { \
+                hipLaunchKernelGGL(kde_hermite_coef_mfma_kernel, dim3((unsigned)nd), dim3(64 * FGT_WAVES), 0, s, g, d_dense, nd, \
+                                   k->cell_start, k->ys, n, k->coef, PP, herm); \
+                hipLaunchKernelGGL(kde_h2l_mfma_kernel<0>, dim3((unsigned)g.nc[0], (unsigned)((g.nc[1] + H2LM_T - 1) / H2LM_T)), \
+                                   dim3(64 * FGT_WAVES), 0, s, g, hslot, slot, herm, d_hankel, reach, PP, d_V, d_vflag, local); \
+                hipLaunchKernelGGL(kde_h2l_mfma_kernel<1>, dim3((unsigned)((g.nc[0] + H2LM_T - 1) / H2LM_T), (unsigned)g.nc[1]), \
+                                   dim3(64 * FGT_WAVES), 0, s, g, hslot, slot, herm, d_hankel, reach, PP, d_V, d_vflag, local); \
+                if (nd == n_heads) { \
+                    hipLaunchKernelGGL(kde_local_pilot_wave_kernel<PP>, dim3((unsigned)n_blocks, (unsigned)(Q_CHUNK / (64 * FGT_WAVES))), dim3(64 * FGT_WAVES), 0, s, g, \
+                                       d_blocks, k->ys, n, local, pilot, pstamps); \
+                    pilot_host_pairs = (unsigned long long)(PP * PP / 23 + 1) * (unsigned long long)n; \
+                } else \
+                    hipLaunchKernelGGL((kde_local_pilot_kernel<PP, true>), dim3((unsigned)n_blocks), dim3(KDE_THREADS), 0, s, g, \
+                                       d_blocks, k->ys, n, k->coef, k->cell_start, slot, local, n_heads, h2l_split, pilot, k->pair_count); \
+            } while (0)
+            // P > 16
+#define KDE_LOCAL_VALU(PP) do { \
+                hipLaunchKernelGGL(kde_hermite_coef_kernel<PP>, dim3((unsigned)nd), dim3(HC_THREADS), 0, s, g, d_dense, \
+                                   k->cell_start, k->ys, n, k->coef, herm); \
+                hipLaunchKernelGGL((kde_h2l4_kernel<PP, 0>), dim3((unsigned)g.nc[0], (unsigned)((g.nc[1] + H2L4_T - 1) / H2L4_T), (unsigned)h2l_split), \
+                                   dim3(H2L_THREADS), 0, s, g, hslot, slot, herm, d_hankel, reach, d_V, d_vflag, local, n_heads); \
+                hipLaunchKernelGGL((kde_h2l4_kernel<PP, 1>), dim3((unsigned)((g.nc[0] + H2L4_T - 1) / H2L4_T), (unsigned)g.nc[1], (unsigned)h2l_split), \
+                                   dim3(H2L_THREADS), 0, s, g, hslot, slot, herm, d_hankel, reach, d_V, d_vflag, local, n_heads); \
+                if (nd < n_heads) \
+                    hipLaunchKernelGGL((kde_local_pilot_kernel<PP, true>), dim3((unsigned)n_blocks), dim3(KDE_THREADS), 0, s, g, \
+                                       d_blocks, k->ys, n, k->coef, k->cell_start, slot, local, n_heads, h2l_split, pilot, k->pair_count); \
                 else \
-                    hipLaunchKernelGGL(kde_hermite_coef_kernel<PP>, dim3((unsigned)nd), dim3(HC_THREADS), 0, s, g, d_dense, \
-                                       k->cell_start, k->ys, n, k->coef, herm); \
-                if (local_exp) { \
-                    if (h2l_form == 2) { \
-                        hipLaunchKernelGGL(kde_h2l_mfma_kernel<0>, dim3((unsigned)g.nc[0], (unsigned)((g.nc[1] + H2LM_T - 1) / H2LM_T)), \
-                                           dim3(64 * FGT_WAVES), 0, s, g, hslot, slot, herm, d_hankel, reach, PP, d_V, d_vflag, local); \
-                        hipLaunchKernelGGL(kde_h2l_mfma_kernel<1>, dim3((unsigned)((g.nc[0] + H2LM_T - 1) / H2LM_T), (unsigned)g.nc[1]), \
-                                           dim3(64 * FGT_WAVES), 0, s, g, hslot, slot, herm, d_hankel, reach, PP, d_V, d_vflag, local); \
-                    } else if (h2l_form == 1) { \
-                        hipLaunchKernelGGL((kde_h2l4_kernel<PP, 0>), dim3((unsigned)g.nc[0], (unsigned)((g.nc[1] + H2L4_T - 1) / H2L4_T), (unsigned)h2l_split), \
-                                           dim3(H2L_THREADS), 0, s, g, hslot, slot, herm, d_hankel, reach, d_V, d_vflag, local, n_heads); \
-                        hipLaunchKernelGGL((kde_h2l4_kernel<PP, 1>), dim3((unsigned)((g.nc[0] + H2L4_T - 1) / H2L4_T), (unsigned)g.nc[1], (unsigned)h2l_split), \
-                                           dim3(H2L_THREADS), 0, s, g, hslot, slot, herm, d_hankel, reach, d_V, d_vflag, local, n_heads); \
-                    } else { \
-                        hipLaunchKernelGGL((kde_h2l_kernel<PP, 0>), dim3((unsigned)k->n_cells), dim3(H2L_THREADS), 0, s, g, d_tcells, \
-                                           slot, herm, d_hankel, reach, d_V, d_vflag, local); \
-                        hipLaunchKernelGGL((kde_h2l_kernel<PP, 1>), dim3((unsigned)n_heads), dim3(H2L_THREADS), 0, s, g, d_tcells, \
-                                           slot, herm, d_hankel, reach, d_V, d_vflag, local); \
-                    } \
-                    if (nd == n_heads && h2l_split == 1 && pilot_form == 1) { \
-                        hipLaunchKernelGGL(kde_local_pilot_wave_kernel<PP>, dim3((unsigned)n_blocks, (unsigned)(Q_CHUNK / (64 * FGT_WAVES))), dim3(64 * FGT_WAVES), 0, s, g, \
-                                           d_blocks, k->ys, n, local, pilot, pstamps); \
-                        pilot_host_pairs = (unsigned long long)(PP * PP / 23 + 1) * (unsigned long long)n; \
-                    } else if (nd < n_heads) \
-                        hipLaunchKernelGGL((kde_local_pilot_kernel<PP, true>), dim3((unsigned)n_blocks), dim3(KDE_THREADS), 0, s, g, \
-                                           d_blocks, k->ys, n, k->coef, k->cell_start, slot, local, n_heads, h2l_form >= 1 ? h2l_split : 1, pilot, k->pair_count); \
-                    else \
-                        hipLaunchKernelGGL((kde_local_pilot_kernel<PP, false>), dim3((unsigned)n_blocks), dim3(KDE_THREADS), 0, s, g, \
-                                           d_blocks, k->ys, n, k->coef, k->cell_start, slot, local, n_heads, h2l_form >= 1 ? h2l_split : 1, pilot, k->pair_count); \
-                } else { \
-                    hipLaunchKernelGGL(kde_hermite_pilot_kernel<PP>, grid, dim3(KDE_THREADS), 0, s, g, d_blocks, \
-                                       k->ys, n, k->coef, k->cell_start, slot, herm, n_split, part, k->pair_count); \
-                } } while (0)
+                    hipLaunchKernelGGL((kde_local_pilot_kernel<PP, false>), dim3((unsigned)n_blocks), dim3(KDE_THREADS), 0, s, g, \
+                                       d_blocks, k->ys, n, k->coef, k->cell_start, slot, local, n_heads, h2l_split, pilot, k->pair_count); \
+            } while (0)
             static const int twice = PISA_DEV_INT("KDE_TWICE", 0);
             for (int rep = 0; rep < ((twice & 2) ? 2 : 1); rep++) {
-                if (P == 14) KDE_FGT(14); else if (P == 16) KDE_FGT(16); else if (P == 18) KDE_FGT(18); else KDE_FGT(20);
+                if (!local_exp) {
+                    if (P == 14) KDE_SERIES(14); else if (P == 16) KDE_SERIES(16); else if (P == 18) KDE_SERIES(18); else KDE_SERIES(20);
+                } else if (P == 14) KDE_LOCAL_MFMA(14);
+                else if (P == 16) KDE_LOCAL_MFMA(16);
+                else if (P == 18) KDE_LOCAL_VALU(18);
+                else KDE_LOCAL_VALU(20);
             }
-#undef KDE_FGT
+#undef KDE_SERIES
+#undef KDE_LOCAL_MFMA
+#undef KDE_LOCAL_VALU
             KDE_TRY(check_hip(hipGetLastError(), "kde expansion kernels"));
 #ifdef PISA_DEV_PROBES
             if (pstamps) {
@@ -2846,16 +2733,13 @@ static int64_t lattice_patches(int R, int sw, int lpw, const int64_t *count) {
 
 static void lattice_shape(const pisa_hip_kde *k, int R, const double *step, const int64_t *count, int &sw_out, int &lg_out) {
     const int strips_a = (int)((count[0] + R - 1) / R);
-    static const int forced_sw = PISA_DEV_INT("KDE_LATTICE_SW", 0);
-    static const int forced_lg = PISA_DEV_INT("KDE_LATTICE_LG", 0);
     const double rp = sqrt(k->g.rcut2) / fabs(k->g.U[0] * step[0]), rl = sqrt(k->g.rcut2) / fabs(k->g.U[4] * step[1]);
     const double n0 = (double)count[0], n1 = (double)count[1];
     for (int lg : {8, 16, 32, 64}) {
-        if (forced_lg > 0 && lg != forced_lg) continue;   // (development build; one of 8, 16, 32, 64)
         int best = 1;
         double best_cost = INFINITY;
         for (int sw = 1; sw <= lg; sw *= 2) {
-            if (forced_sw > 0 ? sw != std::min(forced_sw, lg) : (sw > 1 && sw / 2 >= strips_a)) continue;
+            if (sw > 1 && sw / 2 >= strips_a) continue;
             const int lpw = lg / sw;
             double rows = 0.0, cols = 0.0;
             for (int64_t j = 0; j < count[1]; j += lpw)
@@ -2870,7 +2754,7 @@ static void lattice_shape(const pisa_hip_kde *k, int R, const double *step, cons
         // (every sub-patch also has a list of the shares within reach of it, n_shares entries at most: 256 MB in all)
         const int64_t n_shares = k->n / LAT_SHARE + 1;
         const int64_t cap = std::min<int64_t>(4096, std::max<int64_t>(1, ((int64_t)64 << 20) / n_shares));
-        if (lattice_patches(R, best, lg / best, count) <= cap || forced_lg > 0 || lg == 64) return;
+        if (lattice_patches(R, best, lg / best, count) <= cap || lg == 64) return;
     }
 }
 
@@ -2978,9 +2862,7 @@ PISA_API int pisa_hip_kde_evaluate_lattice(pisa_hip_kde *k, const double *h_orig
         PISA_TRY_HIP(hipMemsetAsync(stamps, 0, (size_t)n_waves * 32, s));
     }
 #endif
-    static const int no_count = PISA_DEV_INT("KDE_LATTICE_NO_COUNT", 0);   // development: the launch without its per-wavefront atomic
-    unsigned long long *lat_count = no_count ? nullptr : k->pair_count;
-#define KDE_LAT(RR, LL) hipLaunchKernelGGL((kde_lattice_kernel<RR, LL>), dim3((unsigned)n_waves), dim3(64), 0, s, L, g.rcut2, rec, k->n, lists, load, wstart, n_patches, part, lat_count, stamps)
+#define KDE_LAT(RR, LL) hipLaunchKernelGGL((kde_lattice_kernel<RR, LL>), dim3((unsigned)n_waves), dim3(64), 0, s, L, g.rcut2, rec, k->n, lists, load, wstart, n_patches, part, k->pair_count, stamps)
 #define KDE_LAT_R(RR) do { if (lg == 8) KDE_LAT(RR, 8); else if (lg == 16) KDE_LAT(RR, 16); else if (lg == 32) KDE_LAT(RR, 32); else KDE_LAT(RR, 64); } while (0)
     static const int twice = PISA_DEV_INT("KDE_TWICE", 0);
     for (int rep = 0; rep < ((twice & 1) ? 2 : 1); rep++) {

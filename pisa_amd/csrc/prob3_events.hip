@@ -342,10 +342,6 @@ static int launch_events(const Prob3Consts &c, const EarthDev &e, const EvCont *
         for (int b = a + 1; b < e.n_shell; b++)
             if (e.coszen_limit[a] > -1.0 && e.coszen_limit[b] > -1.0 && fabs(e.rhos[a] - e.rhos[b]) < 1e-5)
                 staged = true;
-    static const int force_staged = PISA_DEV_INT("EVENTS_STAGED", 0);
-    if (force_staged) staged = true;   // development / test switch: the general form
-    // direct form: 3 wavefronts per SIMD with the running product in LDS (see the kernel); 2: product in registers
-    static const int waves_cfg = PISA_DEV_INT("EVENTS_WAVES", 3);
     // a long-range potential at all?  (XL = U^dagger . lri . U of either side: all zeros without one)
     bool has_lri = false;
     for (int sd = 0; sd < 2; sd++)
@@ -354,7 +350,7 @@ static int launch_events(const Prob3Consts &c, const EarthDev &e, const EvCont *
                 if (c.side[sd].XL.m[i][j].re != 0.0 || c.side[sd].XL.m[i][j].im != 0.0) has_lri = true;
     size_t lds = 3 * PISA_HIP_MAX_SHELLS * sizeof(double) +
                  (staged ? (size_t)max_seg * threads * 10
-                         : (c.decay ? (size_t)18 * threads * 8 : (waves_cfg > 2 ? (size_t)12 * threads * 8 : 0))) + 16;
+                         : (c.decay ? (size_t)18 * threads * 8 : (size_t)12 * threads * 8)) + 16;
     // one launch per sign (see the kernel) and per EV_MAX_CONT containers
     for (int side = 0; side < 2; side++) {
         EvArgs a;
@@ -368,18 +364,13 @@ static int launch_events(const Prob3Consts &c, const EarthDev &e, const EvCont *
                 max_blocks = nb > max_blocks ? nb : max_blocks;
             }
             dim3 block(threads), grid((unsigned)max_blocks * (unsigned)a.n_cont);
-#define LAUNCH_EV(D, S_, ST) hipLaunchKernelGGL((prob3_events_kernel<D, S_, ST>), grid, block, lds, s, c, e, a, max_seg, d_status)
-#define LAUNCH_SIDE(D, ST) do { if (side == 0) LAUNCH_EV(D, 0, ST); else LAUNCH_EV(D, 1, ST); } while (0)
-            if (c.decay) {
-                if (staged) LAUNCH_SIDE(true, true);
-                else if (side == 0) hipLaunchKernelGGL((prob3_events_kernel<true, 0, false, DECAY_WAVES>), grid, block, lds, s, c, e, a, max_seg, d_status);
-                else hipLaunchKernelGGL((prob3_events_kernel<true, 1, false, DECAY_WAVES>), grid, block, lds, s, c, e, a, max_seg, d_status);
-            }
-            else if (staged) LAUNCH_SIDE(false, true);
-            else if (waves_cfg == 4 && !has_lri) { if (side == 0) hipLaunchKernelGGL((prob3_events_kernel<false, 0, false, 4, false>), grid, block, lds, s, c, e, a, max_seg, d_status); else hipLaunchKernelGGL((prob3_events_kernel<false, 1, false, 4, false>), grid, block, lds, s, c, e, a, max_seg, d_status); }
-            else if (waves_cfg >= 3 && !has_lri) { if (side == 0) hipLaunchKernelGGL((prob3_events_kernel<false, 0, false, 3, false>), grid, block, lds, s, c, e, a, max_seg, d_status); else hipLaunchKernelGGL((prob3_events_kernel<false, 1, false, 3, false>), grid, block, lds, s, c, e, a, max_seg, d_status); }
-            else if (waves_cfg >= 3) { if (side == 0) hipLaunchKernelGGL((prob3_events_kernel<false, 0, false, 3>), grid, block, lds, s, c, e, a, max_seg, d_status); else hipLaunchKernelGGL((prob3_events_kernel<false, 1, false, 3>), grid, block, lds, s, c, e, a, max_seg, d_status); }
-            else LAUNCH_SIDE(false, false);
+#define LAUNCH_EV(S_, D, ...) hipLaunchKernelGGL((prob3_events_kernel<D, S_, __VA_ARGS__>), grid, block, lds, s, c, e, a, max_seg, d_status)
+#define LAUNCH_SIDE(D, ...) do { if (side == 0) LAUNCH_EV(0, D, __VA_ARGS__); else LAUNCH_EV(1, D, __VA_ARGS__); } while (0)
+            // direct form without decay: 3 wavefronts per SIMD with the running product in LDS (see the kernel)
+            if (staged) { if (c.decay) LAUNCH_SIDE(true, true); else LAUNCH_SIDE(false, true); }
+            else if (c.decay) LAUNCH_SIDE(true, false, DECAY_WAVES);
+            else if (has_lri) LAUNCH_SIDE(false, false, 3);
+            else LAUNCH_SIDE(false, false, 3, false);
 #undef LAUNCH_SIDE
 #undef LAUNCH_EV
             PISA_CHECK_LAUNCH("prob3_events_kernel");

@@ -28,13 +28,15 @@ namespace pisa {
 // and an evaluation is two launches:
 //   stage A   wave = (distinct density, sign, 64 energies): the terms of (E, rho)
 //             -> records terms[sign][density][field][n_e]  (1-3 MB, L2 resident)
-//   stage C   workgroup = (row, sign, 64 energies) x G waves: forms each layer matrix
+//   stage C   workgroup = four waves holding (rows, sign, 64 energies), rows packed by their length (default),
+//             or (row, sign, 64 energies) x 2 waves (more rows than the packed form indexes; development
+//             library: PISA_HIP_CHAIN_MODE=split): forms each layer matrix
 //             A = sum_k phase_k Q_k from the record of the layer's density where it multiplies
 //             it (a pair belongs to one row: nothing is computed twice) -- the chain is
 //             multiplied from its middle outwards on both sides at once (see
 //             prob3_chain_kernel), wave 0 joins the waves' partial products (LDS), rotates to
 //             the flavour basis and stores P and the gather tables.
-// The earlier split is kept as an option (PISA_HIP_PROB3_FUSED_AMP=0 at plan creation):
+// The earlier split is kept as an option of the development library (PISA_HIP_PROB3_FUSED_AMP=0 at plan creation):
 //   stage AB  wave = (item of a few pairs of one density, sign, 64 energies): terms in registers,
 //             then the item's layer matrices -> amp[sign][pair][18][n_e]; stage C reads them.
 //             Stage AB is bound by those stores (20-29 MB per evaluation through HBM).
@@ -42,7 +44,7 @@ namespace pisa {
 // Stage C associates the product differently from the sequential reference and uses
 // fused multiply-adds, so its results agree with prob3_grid_kernel to rounding
 // (<= 3e-13 absolute on the probabilities), not bit for bit.
-constexpr int CHAIN_GROUPS_DEFAULT = 2;
+constexpr int CHAIN_GROUPS_DEFAULT = 2;   // waves per row of the unpacked chain launch
 
 // Where a kernel finds the per-evaluation constants.  One parameter point: by value in the
 // kernel-argument segment (2.3 KB, scalar loads).  SEVERAL independent parameter points in one launch
@@ -186,8 +188,7 @@ prob3_chain_kernel(const CS cs, int n_e, const int32_t *__restrict__ row_start,
                     double *__restrict__ prob_nu, double *__restrict__ prob_nubar,
                     double2 *__restrict__ pepmu, const double *__restrict__ energy,
                     const int32_t *__restrict__ pair_u, const double *__restrict__ pair_dist,
-                    int n_unique, const int32_t *__restrict__ blk, int n_points, int n_tiles,
-                    unsigned long long *__restrict__ signal) {
+                    int n_unique, const int32_t *__restrict__ blk, int n_points, int n_tiles) {
     auto MM = [](const mat3 &A_, const mat3 &B_, mat3 &C_) { mat_mul_fma(A_, B_, C_); };
     CSTAMP(0);
     // Several points, packed launch (n_tiles > 0): a 1-D grid in which the (point, sign, energy tile)
@@ -313,23 +314,6 @@ prob3_chain_kernel(const CS cs, int n_e, const int32_t *__restrict__ row_start,
     if (g == 0 && live && cnt > 0) load_pair(k0 + mid, T);
     __syncthreads();
     CSTAMP(3);
-#ifdef PISA_DEV_PROBES
-    if (signal) {
-        // hand-over to a consumer kernel that is already resident (common.hpp, HandOver; guide: "valid forms", producer):
-        // every wave waits for its own stores, workgroup barrier, ONE lane releases at agent scope and adds to its counter
-        const unsigned lin = ((unsigned)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-        if (g == 0 && live) chain_tail<G, AMP>(c, S, L, R, T, have_l, have_r, s_part, part_0, lane, Gr, n_steps, cnt, mid, e_major, ie, n_e, n_cz, jcz,
-                                               side, n_points, pt, out, pepmu);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __hip_atomic_fetch_add(signal + (lin & (HANDOVER_SLOTS - 1)), 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        return;
-    }
-#endif
     if (g != 0 || !live) return;
     chain_tail<G, AMP>(c, S, L, R, T, have_l, have_r, s_part, part_0, lane, Gr, n_steps, cnt, mid, e_major, ie, n_e, n_cz, jcz, side, n_points, pt,
                        out, pepmu);
@@ -433,7 +417,8 @@ struct pisa_hip_grid_plan {
     int32_t *d_pair_u;     // [n_pairs] distinct-density index of each pair
     int32_t *d_blk;        // [4 * n_blk][4] packed launch, per wave: row | group << 16 | groups << 24 (-1 idle), chain start, chain length, 0
     int n_blk;
-    int chain_packed;      // 1 (default): packed chain launch; PISA_HIP_CHAIN_MODE=split: one row per workgroup
+    int chain_packed;      // 1 (default): packed chain launch; 0 (n_cz > 0xffff; development library, PISA_HIP_CHAIN_MODE=split):
+                           // one row per workgroup of CHAIN_GROUPS_DEFAULT waves
     int32_t *d_chain_u;    // [n_chain] the same per chain entry (position in d_row_pairs)
     double *d_chain_dist;  // [n_chain] layer length per chain entry
     double *d_terms;       // stage-A records [points][2][n_unique][PROB3_NF][n_e] (AMP mode)
@@ -444,7 +429,7 @@ struct pisa_hip_grid_plan {
     Prob3Consts *h_consts;   // [MULTI_RING][PISA_HIP_MAX_POINTS] pinned, device-mapped staging blocks
     int consts_slot;
     int fused_amp;         // 1 (default): stage A + chain kernel forming the layer matrices itself;
-                           // 0 (PISA_HIP_PROB3_FUSED_AMP=0 when the plan is created): stage AB
+                           // 0 (development library, PISA_HIP_PROB3_FUSED_AMP=0 when the plan is created): stage AB
                            // stores the layer matrices, the chain kernel reads them
     // host copies for re-cutting the items when n_e changes
     int32_t *h_pair_u;
@@ -472,7 +457,6 @@ static int cut_items(pisa_hip_grid_plan *p, int n_e) {
     const int tiles = (n_e + 63) / 64;
     int ch = (int)(((int64_t)p->n_pairs * 2 * tiles + 2047) / 2048);
     if (ch < 1) ch = 1;
-    if (const int v = PISA_DEV_INT("PROB3_CH", 0); v > 0) ch = v;
     const int np = p->n_pairs;
     int32_t *iu = new int32_t[np + 1], *ip0 = new int32_t[np + 1], *icnt = new int32_t[np + 1];
     int ni = 0;
@@ -645,10 +629,6 @@ static int launch_planned(const CS &cs, bool decay, int n_points, pisa_hip_grid_
                           int32_t n_e, int32_t e_major, double *d_prob_nu, double *d_prob_nubar, double *d_pepmu,
                           hipStream_t s) {
     const unsigned tiles = (unsigned)((n_e + 63) / 64);
-    static const int groups = []() {
-        const int g = PISA_DEV_INT("CHAIN_GROUPS", CHAIN_GROUPS_DEFAULT);
-        return (g == 1 || g == 2 || g == 4) ? g : CHAIN_GROUPS_DEFAULT;
-    }();
     if (plan->n_e_terms < n_e || plan->n_pt_terms < n_points) {
         if (plan->d_terms) (void)hipFree(plan->d_terms);
         plan->d_terms = nullptr;
@@ -666,13 +646,12 @@ static int launch_planned(const CS &cs, bool decay, int n_points, pisa_hip_grid_
         hipLaunchKernelGGL((prob3_terms_kernel<false, CS>), tgrid, tblock, 0, s, cs, d_energy, (int)n_e,
                            plan->d_rho, plan->n_unique, plan->d_terms);
     PISA_CHECK_LAUNCH("prob3_terms_kernel");
-    dim3 cblock(64 * groups), cgrid((unsigned)plan->n_cz, 2u * n_points, tiles);
+    dim3 cblock(64 * CHAIN_GROUPS_DEFAULT), cgrid((unsigned)plan->n_cz, 2u * n_points, tiles);
 #define CHAIN(G, A) hipLaunchKernelGGL((prob3_chain_kernel<G, A, CS>), cgrid, cblock, 0, s, cs, (int)n_e, plan->d_row_start, \
                        plan->d_row_cnt, plan->d_row_pairs, plan->n_cz, plan->n_pairs, plan->d_terms,              \
                        (int)e_major, d_prob_nu, d_prob_nubar, (double2 *)d_pepmu, d_energy, plan->d_chain_u,      \
-                       plan->d_chain_dist, plan->n_unique, plan->d_blk, n_points, lin_tiles, sig)
+                       plan->d_chain_dist, plan->n_unique, plan->d_blk, n_points, lin_tiles)
     int lin_tiles = 0;
-    unsigned long long *sig = nullptr;
     if (plan->chain_packed && plan->n_blk > 0) {
         cblock = dim3(256);
         cgrid = dim3((unsigned)plan->n_blk, 2u * n_points, tiles);
@@ -680,16 +659,9 @@ static int launch_planned(const CS &cs, bool decay, int n_points, pisa_hip_grid_
             lin_tiles = (int)tiles;
             cgrid = dim3((unsigned)plan->n_blk * 2u * n_points * tiles, 1, 1);
         }
-#ifdef PISA_DEV_PROBES
-        if (n_points == 1 && g_chain_signal.flags) {   // (evaluator.hip: the accumulate kernel of this evaluation polls these counters)
-            sig = g_chain_signal.flags;
-            g_chain_signal.n_wg = (int)(cgrid.x * cgrid.y * cgrid.z);
-            g_chain_signal.epoch++;
-        }
-#endif
         if (decay) CHAIN(0, 2); else CHAIN(0, 1);
-    } else if (decay) { if (groups == 1) CHAIN(1, 2); else if (groups == 4) CHAIN(4, 2); else CHAIN(2, 2); }
-    else { if (groups == 1) CHAIN(1, 1); else if (groups == 4) CHAIN(4, 1); else CHAIN(2, 1); }
+    } else if (decay) CHAIN(CHAIN_GROUPS_DEFAULT, 2);
+    else CHAIN(CHAIN_GROUPS_DEFAULT, 1);
 #undef CHAIN
     PISA_CHECK_LAUNCH("prob3_chain_kernel");
     return PISA_HIP_OK;
@@ -706,12 +678,8 @@ PISA_API int pisa_hip_prob3_grid_planned(const pisa_hip_prob3_params *h_params,
     if (rc) return rc;
     hipStream_t s = as_stream(stream);
     const unsigned tiles = (unsigned)((n_e + 63) / 64);
-    static const int groups = []() {
-        const int g = PISA_DEV_INT("CHAIN_GROUPS", CHAIN_GROUPS_DEFAULT);
-        return (g == 1 || g == 2 || g == 4) ? g : CHAIN_GROUPS_DEFAULT;
-    }();
     const int fused_amp = plan->fused_amp;
-    dim3 cblock(64 * groups), cgrid((unsigned)plan->n_cz, 2, tiles);
+    dim3 cblock(64 * CHAIN_GROUPS_DEFAULT), cgrid((unsigned)plan->n_cz, 2, tiles);
     if (fused_amp) return launch_planned(cv, c.decay != 0, 1, plan, d_energy, n_e, e_major, d_prob_nu, d_prob_nubar, d_pepmu, s);
     if (plan->n_e_alloc < n_e) {
         if (plan->d_amp) (void)hipFree(plan->d_amp);
@@ -733,12 +701,10 @@ PISA_API int pisa_hip_prob3_grid_planned(const pisa_hip_prob3_params *h_params,
                                plan->d_rho, plan->d_item_u, plan->d_item_p0, plan->d_item_cnt,
                                plan->d_pair_dist, plan->n_pairs, plan->d_amp);
     }
-#define CHAIN(G) hipLaunchKernelGGL((prob3_chain_kernel<G, 0, ConstsByValue>), cgrid, cblock, 0, s, cv, (int)n_e, plan->d_row_start, \
-                       plan->d_row_cnt, plan->d_row_pairs, plan->n_cz, plan->n_pairs, plan->d_amp,          \
-                       (int)e_major, d_prob_nu, d_prob_nubar, (double2 *)d_pepmu, d_energy, plan->d_pair_u,  \
-                       plan->d_pair_dist, plan->n_unique, plan->d_blk, 1, 0, (unsigned long long *)nullptr)
-    if (groups == 1) CHAIN(1); else if (groups == 4) CHAIN(4); else CHAIN(2);
-#undef CHAIN
+    hipLaunchKernelGGL((prob3_chain_kernel<CHAIN_GROUPS_DEFAULT, 0, ConstsByValue>), cgrid, cblock, 0, s, cv, (int)n_e, plan->d_row_start,
+                       plan->d_row_cnt, plan->d_row_pairs, plan->n_cz, plan->n_pairs, plan->d_amp,
+                       (int)e_major, d_prob_nu, d_prob_nubar, (double2 *)d_pepmu, d_energy, plan->d_pair_u,
+                       plan->d_pair_dist, plan->n_unique, plan->d_blk, 1, 0);
     PISA_CHECK_LAUNCH("prob3_chain_kernel");
     return PISA_HIP_OK;
 }
