@@ -108,7 +108,9 @@ int pisa_hip_prob3_grid(const pisa_hip_prob3_params *h_params, const double *d_e
  * matrix and lists the distinct shell densities.  Per evaluation H(E, rho) is then
  * diagonalised per (energy, distinct density) instead of per node and layer, and
  * each row's chain is multiplied in parts.  Results equal pisa_hip_prob3_grid to
- * rounding (<= 3e-13 absolute on the probabilities), not bit for bit.
+ * rounding, not bit for bit: <= 3e-13 absolute on the grid of tests/golden/prob3_grid_prem12.npz
+ * (tests/test_gpu_kernels.py), and both within 1e-11 of the exact probabilities from 0.1 GeV to
+ * 100 TeV (tests/test_gpu_prob3_exact.py: 9.3e-12 this form's worst, 8.3e-12 the planned one's).
  * plan_create synchronises (it reads the rows back); the planned call is async. */
 typedef struct pisa_hip_grid_plan pisa_hip_grid_plan;
 int pisa_hip_grid_plan_create(const double *d_densities, const double *d_distances, int32_t n_cz,

@@ -562,6 +562,11 @@ __device__ __forceinline__ void layer_amplitude(const Prob3Side &S, const double
             sincos(arg, &s, &c);
             ph[k] = cmake(c, s);
         }
+        // anchor a: a member of the closest pair; f_k = ph_k - ph_a (f_a = 0 exactly)
+        const double g01 = fabs(M[0] - M[1]), g02 = fabs(M[0] - M[2]), g12 = fabs(M[1] - M[2]);
+        const bool a1 = g12 < fmin(g01, g02);
+        const cplx pha = a1 ? ph[1] : ph[0];
+        const cplx f[3] = {a1 ? csub(ph[0], pha) : cmake(0.0, 0.0), a1 ? cmake(0.0, 0.0) : csub(ph[1], pha), csub(ph[2], pha)};
         // real denominators (M_k - M_j)(M_k - M_l)  (:870-872)
         double den0 = (M[0] - M[1]) * (M[0] - M[2]);
         double den1 = (M[1] - M[2]) * (M[1] - M[0]);
@@ -597,9 +602,16 @@ __device__ __forceinline__ void layer_amplitude(const Prob3Side &S, const double
                     p1 = cmake(p1.re / den1, p1.im / den1);
                     p2 = cmake(p2.re / den2, p2.im / den2);
                 }
-                cplx acc = cmul(ph[0], p0);
-                acc = cadd(acc, cmul(ph[1], p1));
-                acc = cadd(acc, cmul(ph[2], p2));
+                // The reference adds ph_0 p_0 + ph_1 p_1 + ph_2 p_2 (:519-531).  The three quotients sum to the identity
+                // whatever the nodes M_k are, so the same matrix is ph_a + sum_k (ph_k - ph_a) p_k for any a; with a in
+                // the closest pair of eigenvalues the ill-conditioned quotient p_a (numerator cancelled to scale / gap
+                // digits, 4e-11 per entry at 100 TeV) is not used at all and its partner's is weighted by O(gap t): the
+                // ONE departure from the reference's operation order in this function (the reference's own sum misses
+                // unitarity by 5e-11 there; tests/test_gpu_prob3_exact.py)
+                cplx acc = cmul(f[0], p0);
+                acc = cadd(acc, cmul(f[1], p1));
+                acc = cadd(acc, cmul(f[2], p2));
+                if (i == j) acc = cadd(acc, pha);
                 A.m[i][j] = acc;
             }
 #undef HMM
@@ -671,8 +683,9 @@ __device__ __forceinline__ void layer_amplitude(const Prob3Side &S, const double
 // it costs ONE matrix product; X itself is assembled from the host-prepared mass-basis images (X0 + 2E a XV +
 // 2E XL, as the planned grid form does) instead of two products with U, and its eigenvalues are taken from X
 // directly (similar to 2E H: the same spectrum).  About half the instructions of layer_amplitude<true, true>
-// and far fewer live registers (no three sets of shifted diagonals, no 27 partial products); the result differs
-// from it by rounding (<= 1e-13 on the probabilities, tests/test_gpu_prob3_variants.py, decay goldens).
+// and far fewer live registers (no three sets of shifted diagonals, no 27 partial products).  Measured against exact
+// values (tests/test_gpu_prob3_exact.py: five decay cases, 0.1 GeV - 100 TeV, dm21 down to 0): within 1.2e-12 of the
+// exact probabilities, where layer_amplitude<true> (the reference's sum) is within 9.3e-12.
 __device__ __forceinline__ void layer_amplitude_decay_poly(const Prob3Side &S, double energy, double rho,
                                                            double baseline, mat3 &A) {
     const double tworttwoGf = 1.52588e-4;
@@ -823,6 +836,21 @@ __device__ __forceinline__ void eigen_terms(const Prob3Side &S, const double (&d
 #pragma unroll
         for (int k = 0; k < 3; k++)  // vacuum ordering, resolved on the host (Prob3Consts::vac_order)
             Mr[k] = vac_order[k] == 0 ? mu[0] : (vac_order[k] == 1 ? mu[1] : mu[2]);
+        // The sum below is ANCHORED on state 0, A' = e_0 + (e_1 - e_0) Q_1 + (e_2 - e_0) Q_2, and the labelling of the
+        // three states is free (a Lagrange sum is symmetric in its nodes).  A projector of a nearly degenerate pair
+        // loses log10(scale / gap) digits in its numerator (at 100 TeV the matter term is 4e5 solar splittings:
+        // 4e-11 per entry); as long as state 0 is one of the pair, the other's projector is weighted by e_b - e_0 =
+        // O(gap t) and its error drops out, and the far state's projector is well conditioned.  So state 0 is made
+        // a member of the closest pair: with (1, 2) closest, 0 and 1 trade places.  (Measured against exact values,
+        // tests/test_gpu_prob3_exact.py: worst distance and unitarity defect at 100 TeV before / after in
+        // EXPERIMENTS.md, "prob3 against exact values".)
+        {
+            const double g01 = fabs(Mr[1] - Mr[0]), g02 = fabs(Mr[2] - Mr[0]), g12 = fabs(Mr[2] - Mr[1]);
+            const bool trade = g12 < fmin(g01, g02);
+            const double m0 = trade ? Mr[1] : Mr[0], m1 = trade ? Mr[0] : Mr[1];
+            Mr[0] = m0;
+            Mr[1] = m1;
+        }
         // A unit phase common to a layer's amplitude drops out of every probability (the chain
         // product only collects a global phase), so the layer matrix may be taken as
         //     A' = exp(+i Mbar t) A = exp(-i (H - tr H / 3) t),  Mbar = (M_0+M_1+M_2)/3,
