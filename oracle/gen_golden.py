@@ -20,6 +20,8 @@ Outputs (all numpy .npz, inputs + expected outputs only -- no reference text):
   barr_wide_ref.npz       the same at 0.1 GeV .. 100 TeV: the clamp of modRatioNuBar, the NaN flux pairs
   hist_ref.npz            np.histogramdd recipe of translation.test_histogram
   stats_wide_ref.npz      reference stats.mcllh_mean / mcllh_eff / correct_chi2 / signed_sqrt_mod_chi2 / conv_llh
+  stats_edge_ref.npz      the nine reference metrics on the families of tests/metric_cases.py (non-integer and large
+                          counts, the zeros of lgamma, the clip, widths from 0 to 1e3 sqrt(lam))
   side_stages_ref.npz     the services around the path: reference two_nu_osc.apply_probs_vectorized,
                           astrophysical.apply_sys_loop, genie_sys.apply_genie_sys,
                           bin_indexing.lookup_indices_vectorized_{1,2,3}d (+ the arrays of its unit test)
@@ -284,10 +286,10 @@ def gen_stats():
     save("stats_ref.npz", **out)
 
 
-def gen_stats_wide():
-    """the metrics beyond llh / poisson_llh / chi2 / mod_chi2, by the reference's own functions.  `uncertainties` is
-    absent: expected values travel as an ndarray subclass carrying its standard deviations, which the stand-in for
-    `unumpy` splits off again (nominal_values / std_devs) -- no arithmetic of that package is emulated."""
+def _stats_with_std():
+    """the reference's stats module and `with_std`.  `uncertainties` is absent: expected values travel as an ndarray
+    subclass carrying its standard deviations, which the stand-in for `unumpy` splits off again (nominal_values /
+    std_devs) -- no arithmetic of that package is emulated."""
     import importlib.util
 
     st = ref_shim.ref_module("pisa.utils.stats")
@@ -307,6 +309,12 @@ def gen_stats_wide():
 
     st.unp = types.SimpleNamespace(nominal_values=lambda x: np.array(x, dtype=np.float64),
                                    std_devs=lambda x: np.array(getattr(x, "s", np.zeros(np.shape(x)))))
+    return st, with_std
+
+
+def gen_stats_wide():
+    """the metrics beyond llh / poisson_llh / chi2 / mod_chi2, by the reference's own functions"""
+    st, with_std = _stats_with_std()
     rs = np.random.RandomState(7)
     n = 160
     expected = rs.rand(n) * 60
@@ -323,6 +331,31 @@ def gen_stats_wide():
         v = np.ma.filled(np.ma.masked_invalid(np.ma.asarray(v, dtype=float)), np.nan)
         out[name] = np.asarray(v, dtype=np.float64)
     save("stats_wide_ref.npz", **out)
+
+
+def gen_stats_edge():
+    """the reference's nine metrics on every family of tests/metric_cases.py and every kind the family is evaluated
+    with: members "<family>/<kind>", per-bin fp64 values with NaN where the reference masks.  The inputs are the
+    families' own (tests/golden/metric_exact_ref.npz carries them); the file's bytes depend on the values alone."""
+    # the repository root goes FIRST, wherever else it may already stand on the path: behind oracle/ itself (HERE,
+    # put first above) `oracle` would name oracle/oracle.py and not the package
+    sys.path.insert(0, os.path.dirname(HERE))
+    from oracle.gen_prob3_exact import save as save_plain
+    from tests import metric_cases as T
+
+    st, with_std = _stats_with_std()
+    out = {}
+    for fam in T.SEEDED:
+        f = T.families()[fam]
+        for kind in T.kinds_of(fam):
+            expected = with_std(f["lam"], f["sigma"]) if kind not in ("llh", "poisson_llh", "chi2") else f["lam"].copy()
+            with np.errstate(all="ignore"):
+                v = getattr(st, kind)(f["k"].copy(), expected)
+            v = np.ma.filled(np.ma.masked_invalid(np.ma.asarray(v, dtype=float)), np.nan)
+            out["%s/%s" % (fam, kind)] = np.asarray(v, dtype=np.float64)
+    path = os.path.join(OUT, "stats_edge_ref.npz")
+    save_plain(path, out)
+    print("wrote", path, "%.1f KB" % (os.path.getsize(path) / 1024))
 
 
 def gen_barr():
@@ -555,8 +588,11 @@ def gen_side():
 
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
-    which = sys.argv[1:] or ["pickles", "layers", "params", "lookup", "stats", "barr", "hist", "grid", "flux", "side", "stats_wide"]
+    # stats_edge stays LAST: it puts the repository root first on sys.path, which changes what `import oracle` names
+    # for anything imported after it
+    which = sys.argv[1:] or ["pickles", "layers", "params", "lookup", "stats", "barr", "hist", "grid", "flux", "side", "stats_wide", "stats_edge"]
     fns = dict(pickles=gen_ref_pickles, layers=gen_layers, params=gen_params, lookup=gen_lookup,
-               stats=gen_stats, barr=gen_barr, hist=gen_hist, grid=gen_grid, flux=gen_flux, side=gen_side, stats_wide=gen_stats_wide)
+               stats=gen_stats, barr=gen_barr, hist=gen_hist, grid=gen_grid, flux=gen_flux, side=gen_side, stats_wide=gen_stats_wide,
+               stats_edge=gen_stats_edge)
     for w in which:
         fns[w]()

@@ -438,6 +438,9 @@ def test_unfused_stage_kernels(K, oracle):
 
 
 def test_metric_golden_and_errors(K):
+    # (values: rtol = 1e-12 here is superseded by the gate of tests/test_gpu_metric_exact.py, a few eps of the terms
+    # against exact values, which runs these inputs too as its family `stats_ref`; what only this test holds: the
+    # errors, chi2's all-bins rule, the front ends' shapes)
     g = load_golden("stats_ref.npz")
     a, e = K.to_device(g["actual"]), K.to_device(g["expected"])
     for name in ("llh", "poisson_llh", "chi2", "mod_chi2"):
@@ -731,6 +734,9 @@ def test_wide_metrics_reference_vectors_and_restatement():
             return 1.0 + (k + alpha) * (1.0 + np.abs(np.log(np.maximum(k + alpha, 1e-300))))
         return 1.0
 
+    # (1e-12 * scale_of below is superseded by the gate of tests/test_gpu_metric_exact.py: G eps (m + 1) against exact
+    # values, on these inputs (its family `stats_wide_ref`) and on non-integer, large and edge counts; the totals
+    # there are compared with the kernels' own tree, bit for bit.  The assertions here stay as they were.)
     for kind in kinds:
         total, per_bin = K.metric(kind, dev(W["actual"]), dev(W["expected"]), dev(W["sigma"] ** 2), per_bin=True)
         got = per_bin.cpu().numpy()
