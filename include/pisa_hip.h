@@ -995,6 +995,59 @@ int pisa_hip_fisher(const double *d_hist, const double *d_sumw2, int32_t n_point
                     double *d_pull, double *d_totals, double *d_var0, int64_t *d_nonempty,
                     int32_t *d_status, void *stream);
 
+/* ------------------------------------------------------- hypersurface fits */
+/* Replaces the per-bin loop of pisa/utils/hypersurface/hypersurface.py Hypersurface.fit (:699-959: one Minuit
+ * MIGRAD + HESSE per bin on a closure that writes into the object) by ONE launch over n_prob independent
+ * problems (bins x maps) that share the design of the systematic sets.
+ * Host arrays: h_x [n_par][n_sets] value - nominal per parameter and set (:430; finite); h_form [n_par] one of
+ * PISA_HIP_HSFIT_LINEAR ... _LOGARITHMIC (the forms of HYPERSURFACE_PARAM_FUNCTIONS, :81-205; quadratic and
+ * exponential_scaled have two coefficients, the others one); h_p0 / h_lo / h_hi / h_inv_prior_sigma [n_coef]
+ * start point, bounds (-inf / +inf: none) and prior weights (0: none; :824-839), coefficient 0 the intercept,
+ * then every parameter's coefficients in order; n_coef must be 1 + the forms' coefficients.
+ * Device arrays: d_y / d_sigma [n_sets][n_prob] the (normalised) maps and their errors, the problem index
+ * fastest; d_x [n_par * n_sets] scratch the call fills from h_x on `stream`.
+ *   eta_n = c_0 + sum_p f_p(x_pn; c_p);  m_n = exp(eta_n) if log_mode, else eta_n
+ *   L(c)  = sum_used ((m_n - y_n) / sigma_n)^2 + sum_i (inv_prior_sigma_i c_i)^2                     (:847-852)
+ * A set with sigma_n = 0 is not used, whatever its y and its model value are (:744-749; `include_empty` is the host's: sigma = 1 before upload).  A
+ * problem with a non-finite y or sigma among its used sets is not fitted (:781-784); one with fewer used sets
+ * than free coefficients is not fitted either (NOT_FITTED | UNDERDETERMINED): coefficients, covariance, chi2 and
+ * loss are NaN.  Otherwise Levenberg-Marquardt on the normal equations in fp64 from the start point clamped into
+ * the box: damping on the diagonal, a trial point (projected onto the box) is taken only if its loss is finite
+ * and not larger, the solve runs over the free components (not the fixed intercept, not a coefficient on a bound
+ * whose descent direction leaves the box); stopped when the relative decrease of the loss is <= 1e-10 at a
+ * damping lambda <= 1 (a tiny step after a run of refused ones is no stall), else
+ * NOT_CONVERGED after max_iter trial points.  Then the EXACT half-Hessian of L (J^T J + sum_n r_n d2r_n + prior)
+ * at the point, up to two Newton steps with it, and its inverse by Cholesky:
+ *   d_coef [n_prob][n_coef]; d_cov [n_prob][n_coef][n_coef] the covariance HESSE reports with errordef =
+ *   LEAST_SQUARES (:917-922), exactly symmetric; NaN with NOT_POSDEF if the half-Hessian is not positive
+ *   definite (:921-925); zero rows and columns for a fixed intercept (:956-957) and -- a deviation: Minuit's
+ *   error in its transformed space is not meaningful there -- for a coefficient that ends on a bound;
+ *   d_chi2 [n_sets][n_prob] ((m - y) / sigma)^2 of EVERY set by plain IEEE division (:982-989);
+ *   d_loss, d_n_iter (trial points), d_status [n_prob] (bit flags below).
+ * Every matrix entry is one sequential chain over the sets in ascending order: a problem's results do not depend
+ * on n_prob, on its place in the batch or on the launch shape.
+ * PISA_HIP_ERR_INVALID before any device access: n_par outside [1, MAX_COEFFTS - 1], n_coef not what the forms
+ * give or above PISA_HIP_HSFIT_MAX_COEFFTS, n_sets outside [1, PISA_HIP_HSFIT_MAX_SETS], n_prob outside
+ * [1, 2^31 - 1] (with the limits no size overflows int64), an unknown form, lo > hi or a NaN bound, x / p0 /
+ * prior weight not finite, a negative prior weight or max_iter, a NULL pointer. */
+#define PISA_HIP_HSFIT_MAX_COEFFTS 16
+#define PISA_HIP_HSFIT_MAX_SETS 128
+#define PISA_HIP_HSFIT_LINEAR 0
+#define PISA_HIP_HSFIT_QUADRATIC 1
+#define PISA_HIP_HSFIT_EXPONENTIAL 2
+#define PISA_HIP_HSFIT_EXPONENTIAL_SCALED 3
+#define PISA_HIP_HSFIT_LOGARITHMIC 4
+#define PISA_HIP_HSFIT_NOT_FITTED 1
+#define PISA_HIP_HSFIT_NOT_CONVERGED 2
+#define PISA_HIP_HSFIT_NOT_POSDEF 4
+#define PISA_HIP_HSFIT_UNDERDETERMINED 8
+int pisa_hip_hypersurface_fit(const double *h_x, const int32_t *h_form, int32_t n_par, int32_t n_sets,
+                              int64_t n_prob, const double *d_y, const double *d_sigma, const double *h_p0,
+                              const double *h_lo, const double *h_hi, const double *h_inv_prior_sigma,
+                              int32_t n_coef, int32_t log_mode, int32_t fix_intercept, int32_t max_iter,
+                              double *d_x, double *d_coef, double *d_cov, double *d_chi2, double *d_loss,
+                              int32_t *d_n_iter, int32_t *d_status, void *stream);
+
 /* ------------------------------------------------------- raw device memory */
 /* Thin wrappers so hosts without torch (a cgo/ctypes binding of the
  * reference) can own device buffers. */

@@ -710,6 +710,43 @@ def fisher(hist, sumw2, lo, hi, dx, truth=None):
                 status=status & 0xFFFFFFFF)
 
 
+def hypersurface_fit(x, forms, y, sigma, p0, lo, hi, inv_prior_sigma, log_mode, fix_intercept=False, max_iter=200):
+    """n_prob independent hypersurface fits in one launch (`pisa_hip_hypersurface_fit`): host x [n_par, n_sets]
+    (value - nominal), forms [n_par] names of `_lib.HSFIT_FORMS`, device y / sigma [n_sets, n_prob], host p0 / lo /
+    hi / inv_prior_sigma [n_coef] (intercept first; +-inf: no bound; 0: no prior).  Returns a dict of device
+    tensors coef [n_prob, C], cov [n_prob, C, C], chi2 [n_sets, n_prob], loss [n_prob], n_iter and status
+    [n_prob] (int32; bit flags `_lib.HSFIT_*`)."""
+    x = np.ascontiguousarray(x, np.float64)
+    if x.ndim != 2 or len(forms) != x.shape[0]:
+        raise ValueError("hypersurface_fit: x is [n_par, n_sets] with one form per parameter")
+    for f in forms:
+        if f not in _lib.HSFIT_FORMS:
+            raise ValueError("Hypersurface function '%s' not known; choose from %s" % (f, list(_lib.HSFIT_FORMS)))
+    n_par, n_sets = x.shape
+    assert y.shape == sigma.shape and y.dim() == 2 and y.shape[0] == n_sets and y.dtype == sigma.dtype == F8
+    y, sigma = y.contiguous(), sigma.contiguous()
+    n_prob = y.shape[1]
+    host = [np.ascontiguousarray(v, np.float64).reshape(-1) for v in (p0, lo, hi, inv_prior_sigma)]
+    n_coef = host[0].size
+    if any(v.size != n_coef for v in host):
+        raise ValueError("hypersurface_fit: p0, lo, hi and inv_prior_sigma need one entry per coefficient")
+    dev = y.device
+    a_form = (C.c_int32 * max(n_par, 1))(*[_lib.HSFIT_FORMS.index(f) for f in forms])
+    work = torch.empty(max(x.size, 1), dtype=F8, device=dev)
+    out = dict(coef=torch.empty((n_prob, n_coef), dtype=F8, device=dev),
+               cov=torch.empty((n_prob, n_coef, n_coef), dtype=F8, device=dev),
+               chi2=torch.empty((n_sets, n_prob), dtype=F8, device=dev),
+               loss=torch.empty(n_prob, dtype=F8, device=dev),
+               n_iter=torch.empty(n_prob, dtype=torch.int32, device=dev),
+               status=torch.empty(n_prob, dtype=torch.int32, device=dev))
+    _lib.check(_lib.lib().pisa_hip_hypersurface_fit(
+        x.ctypes.data_as(C.c_void_p), a_form, n_par, n_sets, n_prob, _ptr(y), _ptr(sigma),
+        *[v.ctypes.data_as(C.c_void_p) for v in host], n_coef, int(bool(log_mode)), int(bool(fix_intercept)),
+        int(max_iter), _ptr(work), _ptr(out["coef"]), _ptr(out["cov"]), _ptr(out["chi2"]), _ptr(out["loss"]),
+        _ptr(out["n_iter"]), _ptr(out["status"]), _stream()))
+    return out
+
+
 def bin_scale(x, scale=None, scalar=1.0, floor=None, out=None):
     """out = x * scale * scalar [floored]; see `pisa_hip_bin_scale`."""
     lib = _lib.lib()
