@@ -7,8 +7,11 @@
 // is minimised by Levenberg-Marquardt on the normal equations (damping on the diagonal, a trial point is taken
 // only if its loss is finite and not larger, every trial point projected onto the box of the bounds, the solve
 // over the free components only), stopped when the loss has stalled.  Then the EXACT half-Hessian of L
-// (J^T J + sum_n r_n d2r_n + prior) is formed at the point, up to two Newton steps are taken with it, and its
-// Cholesky inverse is the covariance HESSE reports with errordef = LEAST_SQUARES.
+// (J^T J + sum_n r_n d2r_n + prior) is formed at the point and Newton steps are taken with it until the Newton
+// decrement -g . d (the loss decrease the quadratic model still promises; its root bounds every |d_i| / sigma_i)
+// is at most 1e-14 (that step is still taken), eight steps at the most: status 0 says that this was reached.
+// The Cholesky inverse of the Hessian at the final point is the covariance HESSE reports with
+// errordef = LEAST_SQUARES.
 // Lanes run over the sets for the model, the residuals and the derivative rows; lanes run over the entries of
 // the normal matrix / Hessian / gradient, EACH entry one lane's sequential chain over the sets in ascending
 // order (as fisher.hip): a result depends on the problem's numbers alone, not on the launch shape or on where
@@ -31,6 +34,9 @@ constexpr double HS_LAMBDA_MAX = 1e16;
 constexpr double HS_LAMBDA_STALL = 1.0;   // a stall counts only if the step was at least half the undamped one
 constexpr double HS_DAMP_FLOOR = 1e-30;  // keeps a coefficient whose derivative row is zero at the point in place
 constexpr double HS_POLISH_SLACK = 1e-12;
+constexpr int HS_POLISH_MAX = 8;          // Newton steps with the exact Hessian
+constexpr double HS_NEWTON_TOL = 1e-14;   // Newton decrement -g . d at which a point counts as stationary
+constexpr double HS_PIVOT_REL = 1e-13;    // a pivot below this share of its diagonal entry is rounding: singular
 
 struct HsDesign {
     int32_t form[HS_MAXC];    // per parameter
@@ -190,7 +196,9 @@ __device__ void hs_normal(const HsDesign &ds, const HsLds &s, const double *cv, 
 
 // F = A with the rows and columns of the fixed components replaced by the identity and `lambda` times the
 // diagonal added; d = -g (0 at the fixed components).  Then F = its lower Cholesky factor (left-looking, lanes
-// over the rows of a column).  False if a pivot is not positive.
+// over the rows of a column).  False if a pivot is not positive, or so small a share of the diagonal entry it
+// is what is left of (HS_PIVOT_REL) that its sign is rounding's: the matrix of two identical derivative rows
+// would otherwise pass as positive definite in one problem out of a few.
 __device__ bool hs_factor(const HsLds &s, int n_coef, double lambda) {
     const int lane = threadIdx.x;
     for (int q = lane; q < n_coef * n_coef; q += HS_LANES) {
@@ -209,8 +217,8 @@ __device__ bool hs_factor(const HsLds &s, int n_coef, double lambda) {
             v = s.F[lane * n_coef + k];
             for (int m = 0; m < k; m++) v -= s.F[lane * n_coef + m] * s.F[k * n_coef + m];
         }
-        const double piv = __shfl(v, k);
-        if (!(piv > 0.0) || !isfinite(piv)) return false;   // every lane has the same piv
+        const double piv = __shfl(v, k), diag = __shfl(mine ? s.F[lane * n_coef + k] : 0.0, k);
+        if (!(piv > HS_PIVOT_REL * diag) || !(piv > 0.0) || !isfinite(piv)) return false;   // every lane has the same piv
         const double lkk = sqrt(piv);
         if (mine) s.F[lane * n_coef + k] = lane == k ? lkk : v / lkk;
         __syncthreads();
@@ -348,18 +356,27 @@ hsfit_kernel(HsDesign ds, const double *__restrict__ x, const double *__restrict
                 if (lambda > HS_LAMBDA_MAX) break;
             }
         }
-        st = conv ? 0 : PISA_HIP_HSFIT_NOT_CONVERGED;
 
-        // the exact half-Hessian at the point, up to two Newton steps with it, then once more at the final point
+        // the exact half-Hessian at the point; Newton steps with it until the Newton decrement says the point is
+        // stationary (`polished`), then the Hessian once more at the final point
         L = hs_eval(ds, s, s.c, n_par, n_sets, n_coef, log_mode);
         hs_normal(ds, s, s.c, n_sets, n_coef, log_mode, true);
-        for (int k = 0; k < 2 && conv; k++) {
+        bool polished = false;
+        for (int k = 0; k <= HS_POLISH_MAX && conv; k++) {
             hs_active(ds, s, n_coef, fix_intercept);
             if (!hs_factor(s, n_coef, 0.0)) {
                 __syncthreads();
                 break;
             }
             hs_solve(s, s.d, 1, 1, n_coef);
+            if (lane == 0) {
+                double nu2 = 0.0;
+                for (int i = 0; i < n_coef; i++) nu2 -= s.g[i] * s.d[i];   // d = 0 at the fixed components
+                s.s[1] = nu2;
+            }
+            __syncthreads();
+            polished = s.s[1] <= HS_NEWTON_TOL;
+            if (k == HS_POLISH_MAX) break;
             hs_trial(ds, s, n_coef);
             const double Lt = hs_eval(ds, s, s.t, n_par, n_sets, n_coef, log_mode);
             const bool ok = isfinite(Lt) && Lt <= L + HS_POLISH_SLACK * fabs(L);
@@ -370,7 +387,7 @@ hsfit_kernel(HsDesign ds, const double *__restrict__ x, const double *__restrict
                 L = hs_eval(ds, s, s.c, n_par, n_sets, n_coef, log_mode);   // E, r, u back at c
             }
             hs_normal(ds, s, s.c, n_sets, n_coef, log_mode, true);
-            if (!ok) break;
+            if (!ok || polished) break;   // the step the decrement was computed for is the last one
         }
         // covariance: the fixed intercept and every coefficient that ended on a bound have zero rows and columns
         if (lane < n_coef)
@@ -383,8 +400,11 @@ hsfit_kernel(HsDesign ds, const double *__restrict__ x, const double *__restrict
             hs_solve(s, s.B, n_coef, n_coef, n_coef);
         } else {
             __syncthreads();
-            st |= PISA_HIP_HSFIT_NOT_POSDEF;
         }
+        // 0: stalled AND stationary by the Newton decrement.  A Hessian that is not positive definite has no
+        // decrement: the flag for it stands alone if the descent had stalled
+        st = conv && (polished || !pd) ? 0 : PISA_HIP_HSFIT_NOT_CONVERGED;
+        if (!pd) st |= PISA_HIP_HSFIT_NOT_POSDEF;
         for (int q = lane; q < cc; q += HS_LANES) {
             const int i = q / n_coef, j = q % n_coef;
             double v = NAN;

@@ -8,7 +8,7 @@ The first derivatives are the gradient functions of `HYPERSURFACE_PARAM_FUNCTION
 are restated here (and checked against central differences of the first).  The half-gradient and the EXACT
 half-Hessian of L are accumulated in np.longdouble; the covariance HESSE estimates with
 errordef = LEAST_SQUARES is the inverse of that half-Hessian.  `lm_fit` is a simple Levenberg-Marquardt
-with a Newton polish, the solver the host tests hand to `Hypersurface.fit`.
+with a Newton polish to a Newton-decrement criterion (the kernel's algorithm step for step), the solver the host tests hand to `Hypersurface.fit`.
 """
 import numpy as np
 
@@ -100,6 +100,23 @@ def chi2_all(forms, x, y, sigma, c, log_mode):
         return ((m - np.asarray(y, np.float64)) / np.asarray(sigma, np.float64)) ** 2
 
 
+PIVOT_REL, POLISH_MAX, NEWTON_TOL = 1e-13, 8, 1e-14          # HS_PIVOT_REL, HS_POLISH_MAX, HS_NEWTON_TOL
+
+
+def cholesky(M):
+    """lower factor, left-looking as the kernel's; None if a pivot is not positive or is so small a share of its
+    diagonal entry (PIVOT_REL) that its sign is rounding's"""
+    n = M.shape[0]
+    F = np.array(M, np.float64)
+    for k in range(n):
+        v = F[k:, k] - F[k:, :k] @ F[k, :k]
+        if not (v[0] > PIVOT_REL * F[k, k] and v[0] > 0.0 and np.isfinite(v[0])):
+            return None
+        F[k, k] = np.sqrt(v[0])
+        F[k + 1:, k] = v[1:] / F[k, k]
+    return np.tril(F)
+
+
 def lm_fit(forms, x, y, sigma, p0, lo, hi, ips, log_mode, fix_intercept=False, max_iter=200, tol=1e-10):
     """one problem: (coef, cov, loss, n_iter, status); status bits as the library's"""
     from pisa_amd._lib import (HSFIT_NOT_CONVERGED, HSFIT_NOT_FITTED, HSFIT_NOT_POSDEF, HSFIT_UNDERDETERMINED)
@@ -130,11 +147,8 @@ def lm_fit(forms, x, y, sigma, p0, lo, hi, ips, log_mode, fix_intercept=False, m
         d = np.diag(M).copy()
         M[np.diag_indices(n_coef)] = np.where(f, 1.0, d + damp * np.maximum(d, 1e-30))
         b[f] = 0
-        try:
-            L = np.linalg.cholesky(M)
-        except np.linalg.LinAlgError:
-            return None
-        return np.linalg.solve(L.T, np.linalg.solve(L, b))
+        L = cholesky(M)
+        return None if L is None else np.linalg.solve(L.T, np.linalg.solve(L, b))
 
     L, g, H = lgh(c)
     lam, n_iter, conv = 1e-3, 0, False
@@ -158,11 +172,14 @@ def lm_fit(forms, x, y, sigma, p0, lo, hi, ips, log_mode, fix_intercept=False, m
             lam *= 10.0
             if lam > 1e16:
                 break
-    status = 0 if conv else HSFIT_NOT_CONVERGED
+    polished = False
     if conv:
-        for _ in range(2):
+        for k in range(POLISH_MAX + 1):
             d = step(H, g, fixed(c, g))
             if d is None:
+                break
+            polished = -(g @ d) <= NEWTON_TOL          # the Newton decrement; d = 0 at the fixed components
+            if k == POLISH_MAX:
                 break
             t = np.where(fixed(c, g), c, np.clip(c + d, lo, hi))
             Lt = loss_only(forms, x, y, sigma, t, log_mode, ips)
@@ -170,17 +187,21 @@ def lm_fit(forms, x, y, sigma, p0, lo, hi, ips, log_mode, fix_intercept=False, m
                 break
             c = t
             L, g, H = lgh(c)
+            if polished:          # the step the decrement was computed for is the last one
+                break
     f = (c <= lo) | (c >= hi)
     f[0] |= bool(fix_intercept)
     M = H.copy()
     M[f, :] = 0
     M[:, f] = 0
     M[f, f] = 1.0
-    try:
-        Lc = np.linalg.cholesky(M)
+    Lc = cholesky(M)
+    # 0: stalled AND stationary by the Newton decrement; a Hessian that is not positive definite has no decrement
+    status = 0 if conv and (polished or Lc is None) else HSFIT_NOT_CONVERGED
+    if Lc is not None:
         inv = np.linalg.solve(Lc.T, np.linalg.solve(Lc, np.eye(n_coef)))
         cov = np.where(f[:, None] | f[None, :], 0.0, (inv + inv.T) / 2)
-    except np.linalg.LinAlgError:
+    else:
         cov, status = nan_cov, status | HSFIT_NOT_POSDEF
     return c, cov, L, n_iter, status
 
@@ -282,3 +303,342 @@ def case_limit(n_prob=5, seed=11, n_sets=70):
 
 def free_box(n_coef):
     return np.full(n_coef, -np.inf), np.full(n_coef, np.inf)
+
+
+# ------------------------------------------------------------------ families
+# Each family is a dict: forms, x [n_par, n_sets], y, sigma [n_sets, n_prob], truth [n_prob, C] (or None) and the fit
+# arguments p0, lo, hi, ips, log_mode, fix_intercept, max_iter.  `well_posed` says whether tests/test_host_hsfit.py
+# holds the restatement to a tenth of the gates on it; the others are the flag families.
+import functools
+import os
+
+EXACT_FILE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "hsfit_exact_ref.npz")
+MAX_ITER = 200
+ALL_FORMS = tuple(HYPERSURFACE_PARAM_FUNCTIONS)
+
+
+def family(forms, x, y, sigma, truth, log_mode, p0=None, lo=None, hi=None, ips=None, fix_intercept=False,
+           max_iter=MAX_ITER, well_posed=True):
+    n_coef = layout(forms)[1]
+    box = free_box(n_coef)
+    if p0 is None:          # Hypersurface.fit's default start: intercept 0 in log mode, 1 otherwise, the rest 0
+        p0 = np.zeros(n_coef)
+        p0[0] = 0.0 if log_mode else 1.0
+    return dict(forms=tuple(forms), x=np.asarray(x, np.float64), y=np.asarray(y, np.float64),
+                sigma=np.asarray(sigma, np.float64), truth=truth, log_mode=bool(log_mode),
+                p0=np.asarray(p0, np.float64), lo=box[0] if lo is None else np.asarray(lo, np.float64),
+                hi=box[1] if hi is None else np.asarray(hi, np.float64),
+                ips=np.zeros(n_coef) if ips is None else np.asarray(ips, np.float64),
+                fix_intercept=bool(fix_intercept), max_iter=int(max_iter), well_posed=well_posed)
+
+
+def solve(fam):
+    """the restatement on a family"""
+    return batch_solver(fam["x"], fam["forms"], fam["y"], fam["sigma"], fam["p0"], fam["lo"], fam["hi"], fam["ips"],
+                        fam["log_mode"], fam["fix_intercept"], fam["max_iter"])
+
+
+def on_axis(offsets):
+    """x [n_par, 1 + sum of len(offsets)]: the nominal set at 0, then every parameter's own sets"""
+    x = np.zeros((len(offsets), 1 + sum(len(o) for o in offsets)))
+    k = 1
+    for p, offs in enumerate(offsets):
+        x[p, k:k + len(offs)] = offs
+        k += len(offs)
+    return x
+
+
+def scatter(rs, forms, x, truth, log_mode, rel=0.01, floor=1e-4):
+    """y, sigma [n_sets, n_prob]: sigma = rel |y0| U(0.5, 2) + floor, Gaussian scatter"""
+    y0 = np.stack([model(forms, x, t, log_mode, np.float64)[0] for t in truth], axis=1)
+    sigma = rel * np.abs(y0) * rs.uniform(0.5, 2.0, y0.shape) + floor
+    return y0 + sigma * rs.normal(size=y0.shape), sigma
+
+
+OFFSETS_FORMS = ([-1.0, -0.5, 0.5, 1.0], [-0.4, -0.2, 0.2, 0.4])
+
+
+def _intercepts(rs, n_prob, log_mode):
+    return rs.normal(0.0, 0.05, n_prob) + (0.0 if log_mode else 1.0)
+
+
+def _form_truth(rs, form, n_prob):
+    """coefficients of one parameter at which the problem is well posed on x in [-1, 1]"""
+    if form == "linear":
+        return [rs.normal(0.0, 0.3, n_prob)]
+    if form == "quadratic":
+        return [rs.normal(0.0, 0.3, n_prob), rs.normal(0.0, 0.3, n_prob)]
+    if form == "exponential":
+        return [rs.normal(0.0, 0.5, n_prob)]
+    if form == "exponential_scaled":        # b away from 0, a away from -1: the valley belongs to f_ill
+        return [rs.uniform(-0.4, 0.4, n_prob), rs.choice([-1.0, 1.0], n_prob) * rs.uniform(0.6, 1.2, n_prob)]
+    return [np.clip(rs.normal(0.0, 0.3, n_prob), -0.7, 0.7)]          # logarithmic: 1 + m x >= 0.3
+
+
+@functools.lru_cache(maxsize=None)
+def f_forms(form, log_mode, n_prob=64, max_iter=MAX_ITER, p0_all=None):
+    """one parameter of `form` and one linear parameter, 9 on-axis sets"""
+    rs = np.random.RandomState(100 + 10 * ALL_FORMS.index(form) + int(log_mode))
+    forms = (form, "linear")
+    x = on_axis(OFFSETS_FORMS)
+    truth = np.stack([_intercepts(rs, n_prob, log_mode)] + _form_truth(rs, form, n_prob)
+                     + [rs.normal(0.0, 0.3, n_prob)], axis=1)
+    y, sigma = scatter(rs, forms, x, truth, log_mode)
+    p0 = None if p0_all is None else np.full(truth.shape[1], p0_all)
+    return family(forms, x, y, sigma, truth, log_mode, p0=p0, max_iter=max_iter, well_posed=max_iter > 0)
+
+
+SET_COUNTS = (63, 64, 65, 127, 128)
+SETS_VARIANTS = tuple("n%d" % n for n in SET_COUNTS) + ("log65", "unused")
+FORMS_SETS_LOG = ("exponential", "quadratic", "linear")
+
+
+@functools.lru_cache(maxsize=None)
+def f_sets(variant, n_prob=8):
+    """case_limit's design at the set counts where the lane loops and the chains end; `log65`: log mode with an
+    exponential parameter; `unused`: 128 sets, sigma = 0 on sets 63 and 64 of the first half of the problems and on
+    the last set of the others (NaN values there: an unused set may hold anything)"""
+    if variant == "log65":
+        rs = np.random.RandomState(65)
+        x = rs.uniform(-1.0, 1.0, (3, 65))
+        x[:, 0] = 0.0
+        truth = np.stack([rs.normal(0, 0.05, n_prob), rs.normal(0, 0.5, n_prob), rs.normal(0, 0.3, n_prob),
+                          rs.normal(0, 0.3, n_prob), rs.normal(0, 0.3, n_prob)], axis=1)
+        y, sigma = scatter(rs, FORMS_SETS_LOG, x, truth, True)
+        return family(FORMS_SETS_LOG, x, y, sigma, truth, True)
+    n_sets = 128 if variant == "unused" else int(variant[1:])
+    x, y, sigma, truth = case_limit(n_prob, seed=11 + n_sets, n_sets=n_sets)
+    if variant == "unused":
+        half = n_prob // 2
+        sigma[63:65, :half] = 0.0
+        sigma[127, half:] = 0.0
+        y[64, :half] = np.nan
+        y[127, half:] = np.nan
+    return family(FORMS_LIMIT, x, y, sigma, truth, False)
+
+
+FORMS_MANY = ("linear", "exponential")
+MANY_FIRST, MANY_EXTRA, MANY_POOL = 4096, 70, 64
+# (index, kind): a workgroup takes problem i and then i + 4096.  Bad first, good second ...
+MANY_BAD = tuple((i, k) for i, k in zip(range(0, 24, 2), ("nan", "few", "flat") * 4)) \
+    + tuple((i + MANY_FIRST, k) for i, k in zip(range(40, 64, 4), ("nan", "few", "flat") * 2))     # ... and good first
+
+
+@functools.lru_cache(maxsize=None)
+def f_many_pool():
+    """the distinct well-posed problems of f_many: log mode, intercept + linear + exponential on 5 sets"""
+    rs = np.random.RandomState(4166)
+    x = on_axis(([-0.5, 0.5], [-1.0, 1.0]))
+    truth = np.stack([rs.normal(0, 0.05, MANY_POOL), rs.normal(0, 0.3, MANY_POOL), rs.normal(0, 0.5, MANY_POOL)],
+                     axis=1)
+    y, sigma = scatter(rs, FORMS_MANY, x, truth, True)
+    return family(FORMS_MANY, x, y, sigma, truth, True)
+
+
+@functools.lru_cache(maxsize=None)
+def f_many():
+    """4096 + 70 problems: problem j is problem j % 64 of the pool, except the bad ones of MANY_BAD --
+    `nan`: a NaN value in a used set (not fitted); `few`: two used sets for three coefficients (not fitted,
+    underdetermined); `flat`: the two sets of the exponential parameter unused, so that its derivative row is zero
+    on every used set (fitted; the Hessian is singular: NOT_POSDEF).  Returns the family and `source` [n_prob]:
+    the pool index, -1 for the bad ones."""
+    pool = f_many_pool()
+    n = MANY_FIRST + MANY_EXTRA
+    source = np.arange(n) % MANY_POOL
+    y, sigma = pool["y"][:, source].copy(), pool["sigma"][:, source].copy()
+    for i, kind in MANY_BAD:
+        source[i] = -1
+        if kind == "nan":
+            y[2, i] = np.nan
+        elif kind == "few":
+            sigma[2:, i] = 0.0
+        else:
+            sigma[3:, i] = 0.0
+    return family(FORMS_MANY, pool["x"], y, sigma, None, True, well_posed=False), source
+
+
+BOX_VARIANTS = ("lower", "two_sided", "pinned", "outside", "intercept", "leave")
+
+
+@functools.lru_cache(maxsize=None)
+def f_box(variant, n_prob=32):
+    """case_a's first problems with a box: `lower` a lower bound that cuts some bins, `two_sided` both sides cut
+    some, `pinned` lo == hi, `outside` the start outside the box on two coefficients, `intercept` a bound on the
+    intercept, `leave` the start ON a bound the minimum is inside of"""
+    x, y, sigma, truth = case_a()
+    lo, hi = free_box(6)
+    p0 = np.zeros(6)
+    if variant == "lower":
+        lo[1] = -0.1
+    elif variant == "two_sided":
+        lo[2], hi[2] = -0.3, 0.3
+    elif variant == "pinned":
+        lo[3] = hi[3] = 0.05
+    elif variant == "outside":
+        lo[1], hi[1], p0[1] = -1.0, 0.2, 3.0
+        lo[5], hi[5], p0[5] = 0.1, 0.6, -0.5
+    elif variant == "intercept":
+        hi[0] = 0.0
+    else:
+        lo[4], p0[4] = 0.25, 0.25
+        hi[1], p0[1] = 2.0, 2.0
+    return family(FORMS_A, x, y[:, :n_prob].copy(), sigma[:, :n_prob].copy(), truth[:n_prob], True, p0=p0, lo=lo, hi=hi)
+
+
+FORMS_LIN = ("quadratic", "linear", "linear")
+LIN_VARIANTS = ("plain", "prior", "up30", "down30")
+LIN_SCALE = dict(plain=1.0, prior=1.0, up30=2.0 ** 30, down30=2.0 ** -30)
+
+
+@functools.lru_cache(maxsize=None)
+def f_lin(variant, n_prob=32):
+    """the exact anchor: identity link, linear and quadratic forms only, so a linear weighted least-squares
+    problem; 12 sets whose sigma spans three decades; `prior`: prior weights on three coefficients; `up30` /
+    `down30`: y and sigma times 2^30 / 2^-30 (the answer scales by the same power of two, exactly)"""
+    rs = np.random.RandomState(12)
+    x = rs.uniform(-1.0, 1.0, (3, 12))
+    x[:, 0] = 0.0
+    truth = np.concatenate([1.0 + rs.normal(0, 0.05, (n_prob, 1)), rs.normal(0, 0.3, (n_prob, 4))], axis=1)
+    y0 = np.stack([model(FORMS_LIN, x, t, False, np.float64)[0] for t in truth], axis=1)
+    sigma = (10.0 ** np.linspace(-4.0, -1.0, 12))[:, None] * rs.uniform(0.8, 1.25, y0.shape)
+    y = y0 + sigma * rs.normal(size=y0.shape)
+    ips = np.array([0.0, 1 / 0.2, 0.0, 1 / 0.5, 1 / 0.1]) if variant == "prior" else None
+    s = LIN_SCALE[variant]
+    return family(FORMS_LIN, x, y * s, sigma * s, truth * s, False, ips=ips)
+
+
+FORMS_EDGE = ("logarithmic", "linear")
+
+
+@functools.lru_cache(maxsize=None)
+def f_log_edge(n_prob=32):
+    """the truth next to where the model ends: min over the sets of 1 + m x in [0.03, 0.1]; start at zero"""
+    rs = np.random.RandomState(31)
+    x = on_axis(OFFSETS_FORMS)
+    m = rs.choice([-1.0, 1.0], n_prob) * (1.0 - rs.uniform(0.03, 0.1, n_prob))
+    truth = np.stack([rs.normal(0, 0.05, n_prob), m, rs.normal(0, 0.3, n_prob)], axis=1)
+    y, sigma = scatter(rs, FORMS_EDGE, x, truth, True)
+    return family(FORMS_EDGE, x, y, sigma, truth, True)
+
+
+FORMS_TWIN = ("linear", "linear")
+ILL_NAN = (3, 7, 8)          # the problems of f_ill("nan_start") in which the set the start point has no value at is used
+LAMBDA_DECADES = 19          # x10 steps from HS_LAMBDA0 = 1e-3 to HS_LAMBDA_MAX = 1e16
+
+
+@functools.lru_cache(maxsize=None)
+def f_ill(variant, n_prob=16):
+    """the flag families.  `twin`: two linear parameters with identical x rows, identity link (singular Hessian,
+    the minimum loss unique); `twin_prior`: the same with a prior on both slopes (positive definite again);
+    `nan_start`: logarithmic with a start point at which 1 + m x <= 0 on the last set, which is used in the problems
+    ILL_NAN only; `valley`: exponential_scaled with the intercept fixed at 0 and flat data at exp(1) on sets
+    that all lie at x > 0: the model reaches them only as a step, b -> -inf with a -> -2"""
+    rs = np.random.RandomState(900 + len(variant))
+    if variant in ("twin", "twin_prior"):
+        row = np.array([0.0, -1.0, -0.6, -0.3, 0.3, 0.5, 0.8, 1.0])
+        x = np.stack([row, row])
+        truth = np.stack([1.0 + rs.normal(0, 0.05, n_prob), rs.normal(0, 0.3, n_prob), rs.normal(0, 0.3, n_prob)], axis=1)
+        y, sigma = scatter(rs, FORMS_TWIN, x, truth, False)
+        ips = np.array([0.0, 1 / 0.3, 1 / 0.4]) if variant == "twin_prior" else None
+        return family(FORMS_TWIN, x, y, sigma, truth, False, ips=ips, well_posed=variant == "twin_prior")
+    if variant == "nan_start":
+        x = on_axis(([-1.0, -0.5, 0.5, 1.0], [-0.4, -0.2, 0.2, 0.4]))
+        x = np.concatenate([x, [[1.5], [0.0]]], axis=1)
+        truth = np.stack([rs.normal(0, 0.05, n_prob), rs.uniform(-0.5, -0.3, n_prob), rs.normal(0, 0.3, n_prob)], axis=1)
+        y, sigma = scatter(rs, FORMS_EDGE, x, truth, True)
+        unused = np.ones(n_prob, bool)
+        unused[list(ILL_NAN)] = False
+        sigma[-1, unused] = 0.0
+        p0 = np.array([0.0, -0.8, 0.0])          # 1 - 0.8 * 1.5 < 0
+        return family(FORMS_EDGE, x, y, sigma, truth, True, p0=p0, well_posed=False)
+    assert variant == "valley"
+    forms = ("exponential_scaled",)
+    x = on_axis(([0.25, 0.5, 0.75, 1.0],))[:, 1:]
+    truth = np.stack([np.full(n_prob, 1.0), rs.uniform(-0.2, 0.2, n_prob), np.zeros(n_prob)], axis=1)
+    y, sigma = scatter(rs, forms, x, truth, True)
+    return family(forms, x, y, sigma, truth, True, fix_intercept=True, well_posed=False)
+
+
+FORMS_SCAN = ("exponential_scaled", "linear")
+
+
+@functools.lru_cache(maxsize=None)
+def scan(log_mode, n_prob=256):
+    """exponential_scaled + linear with unconstrained truths: some problems run along the (a + 1) b = const valley"""
+    rs = np.random.RandomState(77 + int(log_mode))
+    x = on_axis(OFFSETS_FORMS)
+    truth = np.stack([_intercepts(rs, n_prob, log_mode), rs.normal(0, 0.5, n_prob), rs.normal(0, 0.5, n_prob),
+                      rs.normal(0, 0.3, n_prob)], axis=1)
+    y, sigma = scatter(rs, FORMS_SCAN, x, truth, log_mode)
+    return family(FORMS_SCAN, x, y, sigma, truth, log_mode, well_posed=False)
+
+
+MAX_ITER_0 = (("exponential", True), ("logarithmic", False), ("quadratic", True))
+
+
+def f_no_iter(form, log_mode):
+    """f_forms problems with max_iter = 0 from a start point that is not zero: flagged, the start point returned"""
+    return f_forms(form, log_mode, 8, 0, 0.1)
+
+
+def _families():
+    out = {}
+    for f in ALL_FORMS:
+        for lm in (True, False):
+            out["forms-%s-%s" % (f, "log" if lm else "identity")] = functools.partial(f_forms, f, lm)
+    for v in SETS_VARIANTS:
+        out["sets-" + v] = functools.partial(f_sets, v)
+    out["many-pool"] = f_many_pool
+    for v in BOX_VARIANTS:
+        out["box-" + v] = functools.partial(f_box, v)
+    for v in LIN_VARIANTS:
+        out["lin-" + v] = functools.partial(f_lin, v)
+    out["log-edge"] = f_log_edge
+    for v in ("twin_prior", "twin", "nan_start", "valley"):
+        out["ill-" + v] = functools.partial(f_ill, v)
+    for f, lm in MAX_ITER_0:
+        out["no-iter-%s-%s" % (f, "log" if lm else "identity")] = functools.partial(f_no_iter, f, lm)
+    out["scan-log"] = functools.partial(scan, True)
+    out["scan-identity"] = functools.partial(scan, False)
+    return out
+
+
+FAMILIES = _families()
+WELL_POSED = tuple(n for n in FAMILIES if n.split("-")[0] in ("forms", "sets", "many", "box", "lin", "log")
+                   or n == "ill-twin_prior")
+
+
+def get(name):
+    return FAMILIES[name]()
+
+
+@functools.lru_cache(maxsize=None)
+def reference(name):
+    """the restatement's result on a family, computed once per session"""
+    return solve(get(name))
+
+
+def free_mask(fam, coef):
+    """[n_prob, C]: the coefficients that are neither on a bound, nor pinned, nor the fixed intercept"""
+    free = (coef > fam["lo"]) & (coef < fam["hi"])
+    if fam["fix_intercept"]:
+        free[:, 0] = False
+    return free
+
+
+def measures(fam, out, which=None):
+    """the worst stationarity and covariance figures of a result over the problems `which` (default: all), on the
+    free block of every problem"""
+    free = free_mask(fam, out["coef"])
+    worst_s = worst_c = 0.0
+    for k in (range(fam["y"].shape[1]) if which is None else which):
+        args = (fam["forms"], fam["x"], fam["y"][:, k], fam["sigma"][:, k], out["coef"][k])
+        worst_s = max(worst_s, stationarity(*args, out["cov"][k], fam["log_mode"], fam["ips"], free[k]))
+        ref = cov_reference(*args, fam["log_mode"], fam["ips"], free[k])
+        worst_c = max(worst_c, cov_error(out["cov"][k], ref, free[k]))
+    return worst_s, worst_c
+
+
+# the restatement's share of flagged problems (NOT_CONVERGED or NOT_POSDEF) in the scan, measured by
+# tests/test_host_hsfit.py: the device may exceed it by two percentage points (paths parting on borderline problems)
+SCAN_FLAGGED = {"scan-log": 31 / 256, "scan-identity": 34 / 256}

@@ -4,7 +4,29 @@
                 half-Hessian at the returned coefficients
 plus: results do not depend on where a problem sits in the batch (bit for bit), the compile-time limits, bounds
 and priors, the data rules (NaN, sigma = 0, too few sets), and `fit_hypersurfaces` end to end on planted events.
+
+The seeded families of tests/hsfit_cases.py carry the same gates, and a third (the loss is at most 1e-9 relative above
+the restatement's), to every form in both links, the set counts at the wavefront width, more problems than
+workgroups, every bound shape, an exact anchor (a linear problem against the 40-digit solution of its normal
+equations, tests/golden/hsfit_exact_ref.npz) and every status bit.  tests/test_host_hsfit.py holds the restatement
+to a tenth of the gates on each of them first.  Worst figures on an MI355X (gates 1e-6, 1e-10, 1e-9):
+
+  family (tests/hsfit_cases.py)              stationarity  covariance  loss excess  trial points
+  forms: 5 forms x 2 links, 64 problems each   5.5e-14       6.6e-14     3.4e-14      <= 21
+  sets: 63 / 64 / 65 / 127 / 128, log65,
+        unused sets on lanes 63, 64 and last   3.4e-14       1.7e-14     5.3e-15      <= 6
+  many: 4096 + 70 (64 distinct problems)       2.6e-14       1.1e-15     2.7e-14      <= 8
+  box: six bound shapes, 32 problems each      3.5e-14       1.9e-13     1.8e-14      <= 35
+       (loss above scipy's bounded fit: 1.3e-14)
+  lin: linear problem, 4 variants              1.2e-12       2.4e-14     1.5e-13      <= 6
+       against the 40-digit solution:          9.9e-13       1.9e-14     1.5e-13
+  log-edge: min(1 + m x) in [0.03, 0.1]        1.5e-13       9.9e-16     1.4e-14      <= 7
+  ill-twin_prior                               3.0e-14       4.2e-13     6.8e-15      <= 7
+       against the 40-digit solution:          5.9e-14       8.9e-13     6.8e-15
+  scan: exponential_scaled + linear, 2 x 256   status 0: 4.6e-13 (log), 1.9e-13 (identity);
+        flagged 12.1 % (log) and 13.3 % (identity), the restatement's shares exactly
 """
+import functools
 import os
 from collections import OrderedDict
 
@@ -221,6 +243,242 @@ def test_data_rules_on_the_device(case_a):
     # too few trial points: flagged, the coefficients are still numbers
     short = _fit(x, H.FORMS_A, y[:, :3].copy(), sigma[:, :3].copy(), np.zeros(6), max_iter=2)
     assert np.all(short["status"] & _lib.HSFIT_NOT_CONVERGED) and np.all(np.isfinite(short["coef"]))
+
+
+# ------------------------------------------------------------------ the families of tests/hsfit_cases.py
+@functools.lru_cache(maxsize=None)
+def _dev(name):
+    """the device's result on a family, one launch per session"""
+    f = H.get(name)
+    return _fit(f["x"], f["forms"], f["y"], f["sigma"], f["p0"], f["lo"], f["hi"], f["ips"], f["log_mode"],
+                f["fix_intercept"], f["max_iter"])
+
+
+def _fam_measures(fam, out, which=None):
+    return _measures(fam["forms"], fam["x"], fam["y"], fam["sigma"], out, fam["log_mode"], fam["ips"],
+                     H.free_mask(fam, out["coef"]), which)
+
+
+@pytest.mark.parametrize("name", H.WELL_POSED)
+def test_well_posed_families_meet_the_measures(name):
+    fam, out, ref = H.get(name), _dev(name), H.reference(name)
+    assert np.all(out["status"] == 0), np.bincount(out["status"])
+    worst_s, worst_c = _fam_measures(fam, out)
+    excess = np.max((out["loss"] - ref["loss"]) / ref["loss"])
+    print("%s: stationarity %.3g, covariance %.3g, loss above the restatement's %.3g, trial points <= %d"
+          % (name, worst_s, worst_c, excess, out["n_iter"].max()))
+    assert worst_s <= STATIONARITY
+    assert worst_c <= COVARIANCE
+    assert excess <= LOSS
+    # the same coefficients end on a bound as in the restatement
+    assert np.array_equal(H.free_mask(fam, out["coef"]), H.free_mask(fam, ref["coef"]))
+
+
+def _anchor(name, out, coef, cov, loss):
+    sd = np.sqrt(np.einsum("kii->ki", cov))
+    worst_c = np.max(np.abs(out["coef"] - coef) / sd)
+    worst_v = max(H.cov_error(out["cov"][k], cov[k]) for k in range(len(loss)))
+    worst_l = np.max(np.abs(out["loss"] - loss) / loss)
+    print("%s against the exact solution: coefficients %.3g of their error, covariance %.3g, loss %.3g"
+          % (name, worst_c, worst_v, worst_l))
+    assert worst_c <= STATIONARITY
+    assert worst_v <= COVARIANCE
+    assert worst_l <= LOSS
+
+
+@pytest.mark.parametrize("name, key", [("lin-plain", "f_lin/plain"), ("lin-prior", "f_lin/prior"),
+                                       ("lin-up30", "f_lin/plain"), ("lin-down30", "f_lin/plain"),
+                                       ("ill-twin_prior", "f_ill/twin_prior")])
+def test_exact_anchor(name, key):
+    """coefficients, covariance and loss against the 40-digit solution of the normal equations
+    (oracle/gen_hsfit_exact.py), which no minimiser had a part in"""
+    g = np.load(H.EXACT_FILE, allow_pickle=False)
+    s = H.LIN_SCALE.get(name[4:], 1.0)      # a power of two: the exact answer scales exactly
+    out = _dev(name)
+    assert np.all(out["status"] == 0)
+    _anchor(name, out, g[key + "/coef"] * s, g[key + "/cov"] * (s * s), g[key + "/loss"])
+    if s != 1.0:
+        np.testing.assert_allclose(out["loss"], _dev("lin-plain")["loss"], rtol=1e-12)
+
+
+def _scipy_loss(fam, k):
+    """2 x cost of scipy.optimize.least_squares(bounds=...) on problem k; a pinned coefficient is substituted"""
+    from scipy.optimize import least_squares
+
+    forms, x, y, sigma, log_mode = fam["forms"], fam["x"], fam["y"][:, k], fam["sigma"][:, k], fam["log_mode"]
+    var = fam["lo"] < fam["hi"]
+    start = np.clip(fam["p0"], fam["lo"], fam["hi"])
+
+    def full(v):
+        c = start.copy()
+        c[var] = v
+        return c
+
+    def parts(v):
+        with np.errstate(all="ignore"):
+            m, E, _ = H.model(forms, x, full(v), log_mode, np.float64)
+            return (m - y) / sigma, ((m if log_mode else np.ones_like(m)) / sigma)[:, None] * E[:, var]
+
+    def resid(v):
+        r = parts(v)[0]
+        return np.where(np.isfinite(r), r, 1e150)
+
+    def jac(v):
+        return np.nan_to_num(parts(v)[1], nan=0.0, posinf=1e150, neginf=-1e150)
+    sp = least_squares(resid, start[var], jac=jac, bounds=(fam["lo"][var], fam["hi"][var]), xtol=1e-15, ftol=1e-15,
+                       gtol=1e-15, max_nfev=2000)
+    return 2.0 * sp.cost
+
+
+@pytest.mark.parametrize("variant", H.BOX_VARIANTS)
+def test_bound_shapes(variant):
+    """(the measures on the free block: test_well_posed_families_meet_the_measures)"""
+    fam, out = H.get("box-" + variant), _dev("box-" + variant)
+    coef, lo, hi = out["coef"], fam["lo"], fam["hi"]
+    assert np.all(coef >= lo) and np.all(coef <= hi)
+    on = ~H.free_mask(fam, coef)
+    worst = -np.inf
+    for k in range(coef.shape[0]):
+        _, g, _ = H.loss_grad_hess(fam["forms"], fam["x"], fam["y"][:, k], fam["sigma"][:, k], coef[k],
+                                    fam["log_mode"], fam["ips"])
+        for i in np.flatnonzero(on[k]):
+            assert np.all(out["cov"][k][i, :] == 0.0) and np.all(out["cov"][k][:, i] == 0.0)
+            if lo[i] < hi[i]:          # descent leaves the box through the bound
+                assert (g[i] > 0) if coef[k, i] == lo[i] else (g[i] < 0)
+        if on[k].any():                # every problem a bound cuts
+            sp = _scipy_loss(fam, k)
+            worst = max(worst, (out["loss"][k] - sp) / sp)
+    print("box-%s: on the lower bound %s, on the upper %s of %d; loss above scipy.optimize.least_squares(bounds) %.3g"
+          % (variant, (coef == lo).sum(0), (coef == hi).sum(0), coef.shape[0], worst))
+    assert worst <= LOSS
+    n = coef.shape[0]
+    if variant == "lower":
+        assert 4 <= on[:, 1].sum() <= n - 4
+    elif variant == "two_sided":
+        assert np.sum(coef[:, 2] == -0.3) >= 4 and np.sum(coef[:, 2] == 0.3) >= 4 and np.sum(~on[:, 2]) >= 4
+    elif variant == "pinned":
+        assert np.all(coef[:, 3] == 0.05)
+    elif variant == "outside":
+        assert on[:, 1].sum() >= 4 and on[:, 5].sum() >= 1
+    elif variant == "intercept":
+        assert 4 <= on[:, 0].sum() <= n - 4
+    else:                              # the start sits on two bounds the minimum is inside of
+        assert worst == -np.inf and not on.any()
+        assert np.all(coef[:, 4] > lo[4]) and np.all(coef[:, 1] < hi[1])
+
+
+def _launch(fam, sel):
+    return _fit(fam["x"], fam["forms"], fam["y"][:, sel].copy(), fam["sigma"][:, sel].copy(), fam["p0"], fam["lo"],
+                fam["hi"], fam["ips"], fam["log_mode"], fam["fix_intercept"], fam["max_iter"])
+
+
+def _same_result(a, b):
+    for key in ("coef", "cov", "loss"):
+        assert _same_bits(a[key], b[key]), key
+    assert _same_bits(a["chi2"], b["chi2"])
+    assert np.array_equal(a["n_iter"], b["n_iter"]) and np.array_equal(a["status"], b["status"])
+
+
+def _pick(out, sel):
+    return {k: (v[:, sel] if k == "chi2" else v[sel]) for k, v in out.items()}
+
+
+def test_more_problems_than_workgroups():
+    """4096 + 70 problems: the workgroups of the first 70 take a second problem, in LDS the first one left behind,
+    also where the first one was not fitted or ended as NOT_POSDEF (and the other way round)"""
+    from pisa_amd import _lib
+
+    fam, source = H.f_many()
+    n = source.size
+    assert n == H.MANY_FIRST + H.MANY_EXTRA
+    one = _launch(fam, np.arange(n))
+    first, rest = _launch(fam, np.arange(H.MANY_FIRST)), _launch(fam, np.arange(H.MANY_FIRST, n))
+    _same_result(one, {k: np.concatenate([first[k], rest[k]], axis=1 if k == "chi2" else 0) for k in one})
+    _same_result(one, _pick(_launch(fam, np.arange(n)[::-1]), np.arange(n)[::-1]))
+    want = {"nan": _lib.HSFIT_NOT_FITTED, "few": _lib.HSFIT_NOT_FITTED | _lib.HSFIT_UNDERDETERMINED,
+            "flat": _lib.HSFIT_NOT_POSDEF}
+    partners = []
+    for i, kind in H.MANY_BAD:
+        assert one["status"][i] == want[kind], (i, kind, one["status"][i])
+        assert np.all(np.isnan(one["cov"][i]))
+        if kind == "flat":
+            assert np.all(np.isfinite(one["coef"][i])) and np.isfinite(one["loss"][i]) and one["coef"][i, 2] == 0.0
+        else:
+            assert np.all(np.isnan(one["coef"][i])) and np.isnan(one["loss"][i]) and one["n_iter"][i] == 0
+            assert np.all(np.isnan(one["chi2"][:, i]))
+        partners.append(i + H.MANY_FIRST if i < H.MANY_FIRST else i - H.MANY_FIRST)
+    good = np.flatnonzero(source >= 0)
+    assert np.all(one["status"][good] == 0) and np.all(source[partners] >= 0)
+    # every good problem is one of the pool's 64: all copies equal the pool's own launch bit for bit, the partners
+    # of the bad problems among them, and the pool meets the measures
+    pool = _dev("many-pool")
+    _same_result(_pick(one, good), _pick(pool, source[good]))
+    worst_s, worst_c = _fam_measures(fam, one, partners)
+    print("the %d problems sharing a workgroup with a bad one: stationarity %.3g, covariance %.3g"
+          % (len(partners), worst_s, worst_c))
+    assert worst_s <= STATIONARITY and worst_c <= COVARIANCE
+
+
+def test_flags():
+    from pisa_amd import _lib
+
+    NC, NP = _lib.HSFIT_NOT_CONVERGED, _lib.HSFIT_NOT_POSDEF
+    g = np.load(H.EXACT_FILE, allow_pickle=False)
+    # two identical derivative rows: singular Hessian, unique minimum loss
+    out = _dev("ill-twin")
+    print("ill-twin: status %s" % np.bincount(out["status"]))
+    assert np.all(out["status"] & NP) and np.all(np.isnan(out["cov"])) and np.all(np.isfinite(out["coef"]))
+    exact = g["f_ill/twin/loss"]
+    assert np.max(np.abs(out["loss"] - exact) / exact) <= LOSS
+    # a start point without a value: every trial point is refused until lambda has run out
+    fam, out = H.get("ill-nan_start"), _dev("ill-nan_start")
+    bad = np.zeros(fam["y"].shape[1], bool)
+    bad[list(H.ILL_NAN)] = True
+    print("ill-nan_start: trial points %s" % out["n_iter"][bad])
+    assert np.all(out["status"][bad] & NC) and np.all(out["n_iter"][bad] <= H.LAMBDA_DECADES + 1)
+    assert np.all(out["coef"][bad] == np.clip(fam["p0"], fam["lo"], fam["hi"]))
+    _same_result(_pick(out, ~bad), _launch(fam, ~bad))
+    assert np.all(out["status"][~bad] == 0)
+    # the minimum at infinity
+    fam, out = H.get("ill-valley"), _dev("ill-valley")
+    start = [H.loss_only(fam["forms"], fam["x"], fam["y"][:, k], fam["sigma"][:, k], fam["p0"], True)
+             for k in range(fam["y"].shape[1])]
+    assert np.all(out["status"] & NC) and np.all(np.isfinite(out["coef"])) and np.all(out["loss"] <= start)
+    assert np.all(out["coef"][:, 0] == 0.0)
+    # no trial point at all: the start point, flagged, with the covariance of the Hessian there
+    for f, lm in H.MAX_ITER_0:
+        name = "no-iter-%s-%s" % (f, "log" if lm else "identity")
+        fam, out = H.get(name), _dev(name)
+        assert np.all(out["status"] == NC) and np.all(out["n_iter"] == 0) and np.all(out["coef"] == fam["p0"])
+        worst_c = _fam_measures(fam, out)[1]
+        print("%s: covariance at the start point %.3g" % (name, worst_c))
+        assert worst_c <= COVARIANCE
+
+
+def test_status_zero_means_converged():
+    """Over every problem of every family, the flag families and a scan of exponential_scaled + linear with
+    unconstrained truths in both links (the 4096 + 70 problems are copies of the `many-pool` family, bit for bit:
+    test_more_problems_than_workgroups): status 0 implies the stationarity gate; a flagged problem keeps finite
+    coefficients.  The scan's flagged share may exceed the restatement's (H.SCAN_FLAGGED, measured by
+    tests/test_host_hsfit.py: 31 / 256 in log mode, 34 / 256 with the identity link) by two percentage points:
+    device and host part on borderline problems by rounding."""
+    from pisa_amd import _lib
+
+    flagged_bits = _lib.HSFIT_NOT_CONVERGED | _lib.HSFIT_NOT_POSDEF
+    for name in H.FAMILIES:
+        fam, out = H.get(name), _dev(name)
+        ok = np.flatnonzero(out["status"] == 0)
+        flagged = np.flatnonzero(out["status"] & flagged_bits)
+        assert ok.size + flagged.size == out["status"].size
+        assert np.all(np.isfinite(out["coef"][flagged]))
+        worst_s = _fam_measures(fam, out, ok)[0] if ok.size else 0.0
+        share = flagged.size / out["status"].size
+        if name in H.SCAN_FLAGGED or worst_s > STATIONARITY / 10:
+            print("%s: %.1f %% flagged (the restatement %.1f %%), stationarity of the others %.3g"
+                  % (name, 100 * share, 100 * H.SCAN_FLAGGED.get(name, np.nan), worst_s))
+        assert worst_s <= STATIONARITY, name
+        if name in H.SCAN_FLAGGED:
+            assert share <= H.SCAN_FLAGGED[name] + 0.02
 
 
 # ------------------------------------------------------------------ end to end

@@ -1,6 +1,9 @@
 """Hypersurface fitting without a GPU: the numpy restatement of the fit (tests/hsfit_cases.py) against its own
 two measures, the argument checks of `pisa_hip_hypersurface_fit` (before any device access), and everything
-`Hypersurface.fit` does around the batch solver, with the restatement handed in as the solver.
+`Hypersurface.fit` does around the batch solver, with the restatement handed in as the solver.  Every seeded family
+that tests/test_gpu_hsfit.py holds the device to the gates on is held to a TENTH of the gates here with the
+restatement (that is what "well posed" means), the golden file of exact solutions is regenerated and compared, and
+the restatement's share of flagged problems in the scan is measured.
 
 The two measures (tests/hsfit_cases.py):
   stationarity  |H^-1 (-g)|_i <= 1e-6 sqrt(cov_ii) for every free coefficient of every fitted problem
@@ -17,7 +20,7 @@ from tests import hsfit_cases as H
 
 from pisa_amd.utils import hypersurface as hs
 
-STATIONARITY, COVARIANCE = 1e-6, 1e-10
+STATIONARITY, COVARIANCE, LOSS = 1e-6, 1e-10, 1e-9
 
 
 # ------------------------------------------------------------------ the restatement itself
@@ -61,6 +64,95 @@ def test_restatement_meets_both_measures_on_the_seeded_inputs(case_a):
     assert worst_s <= STATIONARITY
     assert worst_c <= COVARIANCE
     assert worst_gn > 1e-4          # the covariance bound tells the exact Hessian from J^T J
+
+
+# ------------------------------------------------------------------ the families of tests/test_gpu_hsfit.py
+@pytest.mark.parametrize("name", H.WELL_POSED)
+def test_restatement_is_inside_a_tenth_of_the_gates_on_every_well_posed_family(name):
+    """well posed: the restatement ends with status 0 within half of max_iter and meets a tenth of both gates, on
+    every problem.  A family that does not is given another seed or truth distribution, never another gate."""
+    fam, out = H.get(name), H.reference(name)
+    assert np.all(out["status"] == 0), np.bincount(out["status"])
+    assert out["n_iter"].max() <= fam["max_iter"] // 2
+    worst_s, worst_c = H.measures(fam, out)
+    print("%s: stationarity %.3g, covariance %.3g, trial points <= %d" % (name, worst_s, worst_c, out["n_iter"].max()))
+    assert worst_s <= STATIONARITY / 10
+    assert worst_c <= COVARIANCE / 10
+    assert np.all(out["coef"] >= fam["lo"]) and np.all(out["coef"] <= fam["hi"])
+
+
+def test_box_families_cut_release_and_pin():
+    """what the box families are for happens in them: bounds cut some problems and not others, the start-on-bound
+    coefficients end strictly inside"""
+    on = {v: ~H.free_mask(H.get("box-" + v), H.reference("box-" + v)["coef"]) for v in H.BOX_VARIANTS}
+    n = on["lower"].shape[0]
+    assert 4 <= on["lower"][:, 1].sum() <= n - 4
+    coef = H.reference("box-two_sided")["coef"][:, 2]
+    assert np.sum(coef == -0.3) >= 4 and np.sum(coef == 0.3) >= 4 and np.sum(np.abs(coef) < 0.3) >= 4
+    assert np.all(on["pinned"][:, 3]) and np.all(H.reference("box-pinned")["coef"][:, 3] == 0.05)
+    assert on["outside"][:, 1].sum() >= 4 and on["outside"][:, 5].sum() >= 1
+    assert 4 <= on["intercept"][:, 0].sum() <= n - 4
+    assert not on["leave"].any()
+
+
+def test_restatement_loss_against_the_exact_minimum():
+    g = np.load(H.EXACT_FILE, allow_pickle=False)
+    for name, key in (("lin-plain", "f_lin/plain"), ("lin-prior", "f_lin/prior"), ("lin-up30", "f_lin/plain"),
+                      ("lin-down30", "f_lin/plain"), ("ill-twin_prior", "f_ill/twin_prior"), ("ill-twin", "f_ill/twin")):
+        exact = g[key + "/loss"]
+        worst = np.max(np.abs(H.reference(name)["loss"] - exact) / exact)
+        print("%s: loss off the exact minimum by %.3g" % (name, worst))
+        assert worst <= LOSS
+
+
+def test_golden_file_is_reproduced_from_the_seeds():
+    pytest.importorskip("mpmath")
+    from oracle import gen_hsfit_exact
+
+    g = np.load(H.EXACT_FILE, allow_pickle=False)
+    out = gen_hsfit_exact.build()
+    assert sorted(g.files) == sorted(out)
+    for k in out:
+        assert g[k].dtype == out[k].dtype and g[k].shape == out[k].shape and g[k].tobytes() == out[k].tobytes(), k
+
+
+def test_flag_families_and_status_zero_in_the_restatement():
+    """the flag families end as flagged, and over them and the scan a status of 0 implies the stationarity gate.
+    The flagged shares of the scan are the figures tests/test_gpu_hsfit.py holds the device to."""
+    from pisa_amd import _lib
+
+    NC, NP = _lib.HSFIT_NOT_CONVERGED, _lib.HSFIT_NOT_POSDEF
+    out = H.reference("ill-twin")
+    assert np.all(out["status"] == NP) and np.all(np.isnan(out["cov"])) and np.all(np.isfinite(out["coef"]))
+    fam, out = H.get("ill-nan_start"), H.reference("ill-nan_start")
+    bad = np.zeros(fam["y"].shape[1], bool)
+    bad[list(H.ILL_NAN)] = True
+    assert np.all(out["status"][bad] & NC) and np.all(out["status"][~bad] == 0)
+    assert np.all(out["n_iter"][bad] <= H.LAMBDA_DECADES + 1) and np.all(out["coef"][bad] == fam["p0"])
+    out = H.reference("ill-valley")
+    assert np.all(out["status"] & NC) and np.all(np.isfinite(out["coef"]))
+    fam, source = H.f_many()
+    want = {"nan": _lib.HSFIT_NOT_FITTED, "few": _lib.HSFIT_NOT_FITTED | _lib.HSFIT_UNDERDETERMINED, "flat": NP}
+    for i, kind in H.MANY_BAD:
+        res = H.lm_fit(fam["forms"], fam["x"], fam["y"][:, i], fam["sigma"][:, i], fam["p0"], fam["lo"], fam["hi"],
+                       fam["ips"], True)
+        assert res[4] == want[kind] and source[i] == -1
+        assert source[i + H.MANY_FIRST if i < H.MANY_FIRST else i - H.MANY_FIRST] >= 0
+    for f, lm in H.MAX_ITER_0:
+        name = "no-iter-%s-%s" % (f, "log" if lm else "identity")
+        fam, out = H.get(name), H.reference(name)
+        assert np.all(out["status"] == NC) and np.all(out["n_iter"] == 0) and np.all(out["coef"] == fam["p0"])
+        assert H.measures(fam, out)[1] <= COVARIANCE / 10
+    for name in ("ill-nan_start", "ill-valley", "scan-log", "scan-identity"):
+        fam, out = H.get(name), H.reference(name)
+        ok = np.flatnonzero(out["status"] == 0)
+        worst_s, _ = H.measures(fam, out, ok)
+        flagged = 1.0 - ok.size / out["status"].size
+        print("%s: %.1f %% flagged, stationarity of the others %.3g" % (name, 100 * flagged, worst_s))
+        assert worst_s <= STATIONARITY
+        assert np.all(np.isfinite(out["coef"]))
+        if name in H.SCAN_FLAGGED:
+            assert flagged == H.SCAN_FLAGGED[name]
 
 
 # ------------------------------------------------------------------ the C entry point, no device
