@@ -748,6 +748,46 @@ int pisa_hip_metric(int32_t kind, const double *d_actual, const double *d_expect
                     const double *d_sigma2, int32_t n_maps, int64_t n_bins, double *d_per_bin,
                     double *d_total, int32_t *d_status, void *stream);
 
+/* Trial ensembles: Map.metric_total (pisa/core/map.py:1572-1604: Map.metric + np.nansum) of EVERY data map t
+ * against EVERY template k in one call, where the reference loops over both:
+ *     d_out[t][k] = nansum_b metric(kind; d_data[t][b], d_expected[k][b], d_sigma2[k][b])
+ * for kind = PISA_HIP_METRIC_LLH (stats.py:169-253), _POISSON_LLH (:255-326), _CHI2 (:98-167) and _MOD_CHI2
+ * (:651-695), with every rule of pisa_hip_metric: the expectation clipped to SMALL_POS, an llh bin without data
+ * dropped with its -mu (the NaN of 0 ln 0 under nansum), chi2's whole-map rule (stats.py:160-163: all
+ * |d - mu| < 5 eps -> 0) per (t, k) pair.  d_data [n_trials][n_bins], d_expected and d_sigma2 (may be NULL = zeros;
+ * read by mod_chi2 only) [n_templates][n_bins], all finite.
+ * form: _DIRECT  one lane per (t, k) pair, the bins in ascending order through the per-bin formula (every kind);
+ *       _PRODUCT llh and poisson_llh as a dense contraction on the fp64 matrix cores,
+ *                    poisson_llh  (sum_b d ln mu - sum_b mu) - sum_b lgamma(d + 1)
+ *                    llh          sum_b (d ln mu - [d > 0] mu) - sum_{b: d > 0} (d ln d - d)
+ *                (PISA_HIP_ERR_INVALID with a chi2 kind); its preparation buffers belong to the library, one
+ *                set per process as the scratch of pisa_hip_metric: product-form calls on different streams
+ *                must not overlap;
+ *       _AUTO    the product form where it exists.
+ * The bits of entry (t, k) depend on row t of d_data and row k of d_expected / d_sigma2 only: not on the number of
+ * rows, their position or how the caller splits trials or templates over calls.
+ * d_status[1] (int32, zeroed by the caller) is set to PISA_HIP_ERR_NEGATIVE for a negative datum or expectation.
+ * PISA_HIP_ERR_INVALID before any device access: an unknown kind or form, a size outside [1, 2^31 - 1], more than
+ * 65535 * 16 templates for the full matrix, a NULL pointer, k0 outside [0, n_templates). */
+#define PISA_HIP_ENSEMBLE_AUTO 0
+#define PISA_HIP_ENSEMBLE_DIRECT 1
+#define PISA_HIP_ENSEMBLE_PRODUCT 2
+int pisa_hip_metric_matrix(int32_t kind, int32_t form, const double *d_data, const double *d_expected,
+                           const double *d_sigma2, int64_t n_trials, int64_t n_templates, int64_t n_bins,
+                           double *d_out, int32_t *d_status, void *stream);
+
+/* The same matrix reduced per trial without being written (the loop over hypotheses of a Feldman-Cousins or
+ * goodness-of-fit ensemble, where the reference calls Map.metric_total per pair and keeps the best):
+ *     v[t][k]   = d_out[t][k] + d_offset[k]        (d_offset may be NULL: v = d_out)
+ *     d_best[t] = max_k v[t][k] for the llh kinds, min_k for the chi2 kinds
+ *     d_arg[t]  = the smallest k that attains it
+ *     d_at[t]   = v[t][k0]
+ * bit for bit what the same reduction over pisa_hip_metric_matrix of the same form gives. */
+int pisa_hip_metric_matrix_best(int32_t kind, int32_t form, const double *d_data, const double *d_expected,
+                                const double *d_sigma2, const double *d_offset, int32_t k0, int64_t n_trials,
+                                int64_t n_templates, int64_t n_bins, double *d_best, int32_t *d_arg, double *d_at,
+                                int32_t *d_status, void *stream);
+
 /* ----------------------------------------------- binned post-histogram stages */
 
 /* d_out[i] = d_x[i] * d_scale[i] * scalar  (d_scale may be NULL = 1), then, if

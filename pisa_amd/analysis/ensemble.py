@@ -1,0 +1,339 @@
+"""Trial ensembles on a grid of hypotheses: the metric of MANY pseudo-data maps against MANY templates, and what
+frequentist analyses build on it (sensitivity bands, goodness of fit, Feldman-Cousins intervals).
+
+The reference has no such module: an analysis loops `Map.fluctuate` + `Map.metric_total` (pisa/core/map.py:1098-1254,
+1572-1604) over trials and hypotheses.  Here the templates of a grid are made once (`TemplateGrid.from_maker`: one
+sweep of the events per `MAX_POINTS` points where the pipeline allows it), the pseudo-data of a true point are drawn
+on the host from the reference's `RandomState` stream (`pseudo_data`), and the T x K metric values come from one
+launch (`kernels.metric_matrix`), or never exist at all (`kernels.metric_matrix_best`: best, arg and the value at the
+true point per trial).
+
+Nuisance parameters are profiled ONLY as far as they are dimensions of the grid: `delta_metric` takes the best value
+over the grid's points, no minimiser runs per trial.  A free parameter that is not a dimension of the grid stays at
+the value it had when the grid was made.
+
+The batch evaluator is an argument (`solver=`, default `DeviceSolver`): an object with
+    matrix(kind, data, expected, sigma2) -> [T, K]
+    best(kind, data, expected, sigma2, offset, k0) -> (best [T], arg [T], at [T])
+so that everything around the kernels can run with a numpy restatement (tests/ensemble_cases.py).
+"""
+import math
+
+import numpy as np
+
+__all__ = ["METRICS", "DeviceSolver", "TemplateGrid", "grid_points", "pseudo_data", "metric_matrix", "delta_metric",
+           "critical_values", "feldman_cousins", "accepted"]
+
+METRICS = ("llh", "poisson_llh", "chi2", "mod_chi2")      # kernels.METRIC_KIND
+_MAXIMISED = ("llh", "poisson_llh")
+
+
+def _check_metric(metric):
+    if metric not in METRICS:
+        raise ValueError("ensemble: metric '%s' not among %s" % (metric, list(METRICS)))
+
+
+def _host(x):
+    return x.cpu().numpy() if hasattr(x, "cpu") else np.asarray(x)
+
+
+class DeviceSolver:
+    """the default batch evaluator: `kernels.metric_matrix` / `metric_matrix_best`.  Host arrays are uploaded, device
+    tensors are used as they are; device tensors come back."""
+
+    def __init__(self, form="auto"):
+        self.form = form
+
+    def _up(self, a):
+        import torch
+
+        from pisa_amd import kernels as K
+
+        if a is None or isinstance(a, torch.Tensor):
+            return a
+        return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(K.device())
+
+    def _run(self, fn, kind, arrays, **kw):
+        return fn(kind, *[self._up(a) for a in arrays], form=self.form, **kw)
+
+    def matrix(self, kind, data, expected, sigma2=None):
+        from pisa_amd import kernels as K
+
+        return self._run(K.metric_matrix, kind, (data, expected, sigma2))
+
+    def best(self, kind, data, expected, sigma2=None, offset=None, k0=0):
+        from pisa_amd import kernels as K
+
+        return self._run(K.metric_matrix_best, kind, (data, expected, sigma2, offset), k0=int(k0))
+
+
+def _rescaled(param, value):
+    """the [0, 1]-rescaled value `param` would have at `value` (param.py:358-377) without moving it"""
+    if param._range is None:
+        raise ValueError("Cannot rescale without a range specified for parameter %s" % param.name)
+    v = value.m_as(param._units) if hasattr(value, "m_as") else float(value)
+    r0, r1 = param._range[0].m_as(param._units), param._range[1].m_as(param._units)
+    if param.scales_as_log:
+        if r0 < 0:
+            r0, r1, v = -r0, -r1, -v
+        r = (np.log(v) - np.log(r0)) / (np.log(r1) - np.log(r0))
+    else:
+        r = (v - r0) / (r1 - r0)
+    if not -1e-12 <= r <= 1 + 1e-12:
+        raise ValueError("%s: %s is outside the parameter's range" % (param.name, value))
+    return float(min(max(r, 0.0), 1.0))
+
+
+def grid_points(hypo_maker, axes):
+    """The cartesian product of `axes` = {name of a free parameter: values (numbers in the parameter's units, or
+    quantities)} as [K, n_free] values of the free parameters rescaled to [0, 1], in the order of
+    `hypo_maker.params.free`; the LAST name of `axes` runs fastest.  Free parameters that are not named stay at
+    their current value."""
+    free = hypo_maker.params.free
+    names = list(free.names)
+    base = np.array([float(p._rescaled_value) for p in free], dtype=np.float64)
+    cols, vals = [], []
+    for name, values in axes.items():
+        if name not in names:
+            raise ValueError("grid_points: '%s' is not a free parameter (%s)" % (name, names))
+        if hasattr(values, "m_as"):                 # a quantity holding an array: numbers in the parameter's units
+            values = values.m_as(free[name]._units)
+        seq = list(values) if isinstance(values, (list, tuple)) else list(np.atleast_1d(values))
+        v = [_rescaled(free[name], x) for x in seq]
+        if not v:
+            raise ValueError("grid_points: no values for '%s'" % name)
+        cols.append(names.index(name))
+        vals.append(np.asarray(v, dtype=np.float64))
+    if len(set(cols)) != len(cols):
+        raise ValueError("grid_points: a parameter is named twice")
+    n = int(np.prod([v.size for v in vals])) if vals else 1
+    pts = np.tile(base, (n, 1))
+    if vals:
+        mesh = np.meshgrid(*vals, indexing="ij")
+        for c, m in zip(cols, mesh):
+            pts[:, c] = m.ravel()
+    return pts
+
+
+class TemplateGrid:
+    """The templates of K points of the free parameters: `hist` and `sumw2` [K, B] (device tensors from
+    `from_maker`; any arrays the solver takes otherwise), `points` [K, n_free] rescaled, the output `binning` and
+    `penalty` [K] = params.priors_penalty(metric) at each point."""
+
+    def __init__(self, hist, sumw2, points, binning=None, penalty=None, metric=None, sweeps=0):
+        self.hist, self.sumw2 = hist, sumw2
+        self.points = np.atleast_2d(np.asarray(points, dtype=np.float64))
+        self.binning = binning
+        n = int(self.hist.shape[0])
+        self.penalty = np.zeros(n) if penalty is None else np.asarray(penalty, dtype=np.float64)
+        self.metric = metric
+        self.sweeps = sweeps
+        self._host = {}
+        if self.sumw2 is not None and tuple(self.sumw2.shape) != tuple(self.hist.shape):
+            raise ValueError("TemplateGrid: sumw2 has the shape of hist")
+        if self.penalty.shape != (n,) or self.points.shape[0] != n:
+            raise ValueError("TemplateGrid: one point and one penalty per template")
+
+    def __len__(self):
+        return int(self.hist.shape[0])
+
+    n_bins = property(lambda self: int(self.hist.shape[1]))
+
+    def host(self, which="hist"):
+        """`hist` / `sumw2` as a host array (fetched once)"""
+        if which not in self._host:
+            self._host[which] = _host(getattr(self, which))
+        return self._host[which]
+
+    def sigma2_for(self, metric):
+        return self.sumw2 if metric == "mod_chi2" else None
+
+    @classmethod
+    def from_maker(cls, hypo_maker, rescaled_points, metric):
+        """The templates of `hypo_maker` at `rescaled_points` [K, n_free].  One pipeline of the replayable shape
+        whose moving parameters belong to osc.prob3 / aeff.aeff takes the points through `FastPlan.maps_many` (one
+        sweep of the events per MAX_POINTS points) and the containers are added in ascending row order; anything
+        else (a flux, KDE or post-histogram stage moving, several pipelines) takes one
+        `get_outputs(return_sum=True)` per point.  Either way row k of `hist` is, bit for bit,
+        `get_outputs(return_sum=True)["total"].nominal_values` at point k and row k of `sumw2` its variances (zeros
+        where the maps carry no errors).  On return the free parameters hold the values they had at entry."""
+        from pisa_amd import kernels as K
+
+        _check_metric(metric)
+        pts = np.clip(np.atleast_2d(np.asarray(rescaled_points, dtype=np.float64)), 0.0, 1.0)
+        n_free = len(hypo_maker.params.free)
+        if pts.ndim != 2 or pts.shape[1] != n_free or pts.shape[0] < 1:
+            raise ValueError("TemplateGrid: points are [K, %d] rescaled values of the free parameters" % n_free)
+        n = pts.shape[0]
+        saved = [p.value for p in hypo_maker.params.free]
+        pens = np.zeros(n)
+
+        def set_point(i):
+            hypo_maker._set_rescaled_free_params(pts[i])
+            pens[i] = hypo_maker.params.priors_penalty(metric=metric)
+
+        pipes = hypo_maker._pipelines
+        try:
+            first = hypo_maker.get_outputs(return_sum=True)      # (also builds the replay plan)
+            if isinstance(first, list):
+                raise NotImplementedError("TemplateGrid of a pipeline with a variable binning (one MapSet per "
+                                          "selection)")
+            binning = first["total"].binning
+            n_bins = int(np.asarray(first["total"].nominal_values).size)
+            hist = var = None
+            sweeps = 0
+            if len(pipes) == 1 and pipes[0].fast_path and pipes[0]._plan is not None and n >= 2:
+                pipe, plan = pipes[0], pipes[0]._plan
+                try:
+                    maps = plan.maps_many(set_point, n)
+                except BaseException:
+                    pipe._plan = None
+                    plan.invalidate()
+                    raise
+                if maps is not None:
+                    # MapSet.total(): the containers' rows added in ascending order, starting from row 0
+                    h, v = maps["hist"].cpu().numpy(), maps["sumw2"].cpu().numpy()
+                    hist, var = h[:, 0].copy(), v[:, 0].copy()
+                    for r in range(1, h.shape[1]):
+                        hist += h[:, r]
+                        var += v[:, r]
+                    sweeps = maps["sweeps"]
+            if hist is None:
+                hist, var = np.empty((n, n_bins)), np.empty((n, n_bins))
+                for i in range(n):
+                    set_point(i)
+                    out = hypo_maker.get_outputs(return_sum=True)
+                    if isinstance(out, list):
+                        raise NotImplementedError("TemplateGrid of a pipeline with a variable binning")
+                    m = out["total"]
+                    hist[i] = np.asarray(m.nominal_values, dtype=np.float64).ravel()
+                    var[i] = np.asarray(m.variances, dtype=np.float64).ravel()
+        finally:
+            hypo_maker.set_free_params(saved)
+        grid = cls(K.to_device(hist), K.to_device(var), pts, binning, pens, metric, sweeps)
+        grid._host = {"hist": hist, "sumw2": var}
+        return grid
+
+
+def pseudo_data(grid, k, n_trials, random_state=None):
+    """[n_trials, B] pseudo-data of template k: trial t is exactly the t-th `Map.fluctuate("poisson",
+    random_state=rs)` of that template from ONE `RandomState` rs (one `scipy.stats.poisson.rvs` call on the tiled
+    expectation consumes the stream in the same order; NaN bins stay NaN and draw nothing).  Drawn on the host: a
+    counter-based generator on the device cannot reproduce the reference's stream."""
+    from scipy.stats import poisson
+
+    rs = random_state if isinstance(random_state, np.random.RandomState) else np.random.RandomState(random_state)
+    mu = np.asarray(grid.host("hist")[k], dtype=np.float64).ravel()
+    ok = ~np.isnan(mu)
+    out = np.full((int(n_trials), mu.size), np.nan)
+    if n_trials > 0 and ok.any():
+        out[:, ok] = poisson.rvs(np.tile(mu[ok], (int(n_trials), 1)), random_state=rs)
+    return out
+
+
+def _data_rows(data):
+    """a Map, a MapSet of one map, or an array -> [T, B] (host array or device tensor)"""
+    if hasattr(data, "maps"):
+        if len(data.maps) != 1:
+            raise ValueError("ensemble: a data MapSet must hold exactly one map")
+        data = data.maps[0]
+    if hasattr(data, "nominal_values"):
+        return np.asarray(data.nominal_values, dtype=np.float64).reshape(1, -1)
+    if hasattr(data, "dim"):                       # a device tensor
+        return data if data.dim() == 2 else data.reshape(1, -1)
+    a = np.asarray(data, dtype=np.float64)
+    return a if a.ndim == 2 else a.reshape(1, -1)
+
+
+def metric_matrix(data, grid, metric, with_penalty=True, solver=None):
+    """[T, K]: `Map.metric_total(template k, metric)` of every data row (+ the priors penalty of point k).  A device
+    tensor where the solver returns one, else a host array."""
+    _check_metric(metric)
+    solver = DeviceSolver() if solver is None else solver
+    m = solver.matrix(metric, _data_rows(data), grid.hist, grid.sigma2_for(metric))
+    if with_penalty and np.any(grid.penalty != 0.0):
+        if hasattr(m, "cpu"):
+            from pisa_amd import kernels as K
+
+            m = m + K.to_device(grid.penalty)[None, :]
+        else:
+            m = m + grid.penalty[None, :]
+    return m
+
+
+def delta_metric(data, grid, metric, k0, solver=None):
+    """[T] host array: per data row the distance of point k0 from the best point of the grid, penalties included --
+    best - at for the llh metrics, at - best for the chi2 metrics (>= 0; no factor of 2 is applied).  The T x K
+    matrix is never written (`pisa_hip_metric_matrix_best`)."""
+    _check_metric(metric)
+    if not 0 <= int(k0) < len(grid):
+        raise ValueError("delta_metric: k0 = %s outside the grid's %d points" % (k0, len(grid)))
+    solver = DeviceSolver() if solver is None else solver
+    offset = grid.penalty if np.any(grid.penalty != 0.0) else None
+    best, _, at = solver.best(metric, _data_rows(data), grid.hist, grid.sigma2_for(metric), offset, int(k0))
+    best, at = _host(best), _host(at)
+    return best - at if metric in _MAXIMISED else at - best
+
+
+def critical_values(delta, cl):
+    """per confidence level the value at index ceil(cl * T) - 1 of the ascending sort of `delta` [T]: the smallest
+    observed value that at least a fraction cl of the trials do not exceed; no interpolation"""
+    d = np.sort(np.asarray(delta, dtype=np.float64).ravel())
+    if d.size == 0:
+        raise ValueError("critical_values: no trials")
+    out = []
+    for c in np.atleast_1d(cl):
+        if not 0.0 < c <= 1.0:
+            raise ValueError("critical_values: confidence level %s outside (0, 1]" % c)
+        out.append(d[min(max(int(math.ceil(c * d.size)) - 1, 0), d.size - 1)])
+    return np.array(out)
+
+
+def _base_seed(random_state):
+    if random_state is None:
+        return int(np.random.SeedSequence().generate_state(1)[0])
+    if isinstance(random_state, np.random.RandomState):
+        return int(random_state.randint(0, 2 ** 31 - 1))
+    seed = int(random_state)
+    if not 0 <= seed < 2 ** 32:
+        raise ValueError("feldman_cousins: the seed %d is outside [0, 2^32)" % seed)
+    return seed
+
+
+def feldman_cousins(grid, metric, n_trials, cl=(0.6827, 0.90), random_state=None, true_points=None, solver=None):
+    """Critical values of the Feldman-Cousins ordering on the grid: for every true point k0 (default: all), n_trials
+    pseudo-data maps of template k0, their `delta_metric` at k0 and `critical_values` -> crit [len(true_points),
+    len(cl)].  Every true point draws from its own RandomState([seed, k0]) (seed: `random_state`, or one draw from it
+    if it is a RandomState), so a subset of true points reproduces the full run's rows.  Nuisance parameters are
+    profiled only as far as they are dimensions of the grid (module docstring)."""
+    _check_metric(metric)
+    if n_trials < 1:
+        raise ValueError("feldman_cousins: n_trials >= 1")
+    seed = _base_seed(random_state)
+    points = range(len(grid)) if true_points is None else [int(k) for k in true_points]
+    for k0 in points:
+        if not 0 <= k0 < len(grid):
+            raise ValueError("feldman_cousins: true point %d outside the grid's %d points" % (k0, len(grid)))
+    solver = DeviceSolver() if solver is None else solver
+    cl = np.atleast_1d(np.asarray(cl, dtype=np.float64))
+    crit = np.empty((len(points), cl.size))
+    for i, k0 in enumerate(points):
+        data = pseudo_data(grid, k0, n_trials, np.random.RandomState([seed, k0]))
+        crit[i] = critical_values(delta_metric(data, grid, metric, k0, solver), cl)
+    return crit
+
+
+def accepted(data_map, grid, metric, crit, solver=None):
+    """boolean [K]: point k is inside the confidence region of the observed map -- its `delta_metric` at k (one row
+    of the matrix, penalties included, against the row's best) is <= crit[k] ([K]: one confidence level of
+    `feldman_cousins` over all points)"""
+    _check_metric(metric)
+    crit = np.asarray(crit, dtype=np.float64)
+    if crit.shape != (len(grid),):
+        raise ValueError("accepted: crit holds one critical value per point of the grid")
+    rows = _data_rows(data_map)
+    if rows.shape[0] != 1:
+        raise ValueError("accepted: one observed map")
+    m = _host(metric_matrix(rows, grid, metric, True, solver))[0]
+    delta = m.max() - m if metric in _MAXIMISED else m - m.min()
+    return delta <= crit

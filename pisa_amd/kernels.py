@@ -600,6 +600,66 @@ def metric(kind, actual, expected, sigma2=None, per_bin=False, total_out=None, s
     return (total_out, pb) if per_bin else total_out
 
 
+# ------------------------------------------------------------------------- trial ensembles
+def _ensemble_args(kind, data, expected, sigma2, form):
+    if kind not in METRIC_KIND:
+        raise ValueError("metric_matrix: metric '%s' not among %s" % (kind, sorted(METRIC_KIND)))
+    if form not in _lib.ENSEMBLE_FORMS:
+        raise ValueError("metric_matrix: form '%s' not among %s" % (form, list(_lib.ENSEMBLE_FORMS)))
+    if data.dim() != 2 or expected.dim() != 2 or data.dtype != F8 or expected.dtype != F8:
+        raise ValueError("metric_matrix: data is [n_trials, n_bins] and expected [n_templates, n_bins], both float64")
+    if sigma2 is not None and (sigma2.shape != expected.shape or sigma2.dtype != F8):
+        raise ValueError("metric_matrix: sigma2 has the shape and dtype of expected")
+    data, expected = data.contiguous(), expected.contiguous()
+    sigma2 = None if sigma2 is None else sigma2.contiguous()
+    # (a mismatch of the bin counts reaches the library as n_bins = 0: PISA_HIP_ERR_INVALID, nothing is launched)
+    n_bins = data.shape[1] if data.shape[1] == expected.shape[1] else 0
+    return data, expected, sigma2, data.shape[0], expected.shape[0], n_bins
+
+
+def metric_matrix(kind, data, expected, sigma2=None, form="auto", status=None):
+    """Map.metric_total of every data map against every template (`pisa_hip_metric_matrix`): data [T, B], expected
+    and sigma2 [K, B] device tensors -> [T, K] device tensor.  form "direct" (every kind), "product" (llh,
+    poisson_llh: the fp64 matrix cores) or "auto" (product where it exists).  A negative datum or expectation
+    raises ValueError, as `metric` does."""
+    data, expected, sigma2, n_t, n_k, n_bins = _ensemble_args(kind, data, expected, sigma2, form)
+    dev = data.device
+    out = torch.empty((n_t, n_k), dtype=F8, device=dev)
+    own_status = status is None
+    if own_status:
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+    _lib.check(_lib.lib().pisa_hip_metric_matrix(
+        METRIC_KIND[kind], _lib.ENSEMBLE_FORMS.index(form), _ptr(data), _ptr(expected), _ptr(sigma2), n_t, n_k,
+        n_bins, _ptr(out), _ptr(status), _stream()))
+    if own_status:
+        _check_status(status)
+    return out
+
+
+def metric_matrix_best(kind, data, expected, sigma2=None, offset=None, k0=0, form="auto", status=None):
+    """the matrix of `metric_matrix` (+ offset [K] per column) reduced per trial without being written
+    (`pisa_hip_metric_matrix_best`) -> (best [T]: max over k for the llh kinds, min for the chi2 kinds; arg [T]
+    int32: the smallest k attaining it; at [T]: column k0), bit for bit the reduction of the full matrix"""
+    data, expected, sigma2, n_t, n_k, n_bins = _ensemble_args(kind, data, expected, sigma2, form)
+    dev = data.device
+    if offset is not None:
+        if offset.shape != (n_k,) or offset.dtype != F8:
+            raise ValueError("metric_matrix_best: offset is float64 [n_templates]")
+        offset = offset.contiguous()
+    best = torch.empty(n_t, dtype=F8, device=dev)
+    arg = torch.empty(n_t, dtype=torch.int32, device=dev)
+    at = torch.empty(n_t, dtype=F8, device=dev)
+    own_status = status is None
+    if own_status:
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+    _lib.check(_lib.lib().pisa_hip_metric_matrix_best(
+        METRIC_KIND[kind], _lib.ENSEMBLE_FORMS.index(form), _ptr(data), _ptr(expected), _ptr(sigma2), _ptr(offset),
+        int(k0), n_t, n_k, n_bins, _ptr(best), _ptr(arg), _ptr(at), _ptr(status), _stream()))
+    if own_status:
+        _check_status(status)
+    return best, arg, at
+
+
 # --------------------------------------------------- generalized Poisson-gamma likelihood
 def _check_status(status):
     st = int(status.item())

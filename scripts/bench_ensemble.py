@@ -1,0 +1,177 @@
+"""Time of the trial-ensemble kernels (`kernels.metric_matrix`, `kernels.metric_matrix_best`) and of one
+`feldman_cousins`, one JSON line per measurement:
+
+  * kernels, inputs resident, median of 20 launches (HIP events around each call: for the product form that is the
+    preparation launch + the contraction), llh and poisson_llh in both forms, chi2 in the direct form, at
+    (T, K, B) = (1e4, 1e2, 128) full matrix and reduced, (1e5, 1e3, 128) reduced only, (1e4, 1e3, 4800) full matrix
+    and reduced; a form whose launch takes more than half a second is timed over 5 launches (`launches` says so).
+    The product form's fraction of the fp64 peak counts 2 T K B flop (llh: 4 T K B, its two products);
+  * the same work as a loop over `kernels.metric` on a 100 x 100 corner (all there was before these kernels);
+  * end to end: one `feldman_cousins` with T = 1e4 on a 30 x 30 grid of 128-bin templates, its wall time split into
+    host drawing, upload and kernels.
+
+    python scripts/bench_ensemble.py [--reps 20] [--skip-e2e] [--skip-kernels] [--forms direct,product] [--true-points N]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+FP64_PEAK_TFLOPS = 78.6      # bench.py's FP64 peak: 256 CU x 4 SIMD x 16 lanes x 2 flop x 2.4 GHz (= the matrix cores' fp64 peak)
+
+
+def _templates(n_k, n_bins, seed=0):
+    rs = np.random.RandomState(seed)
+    x = np.linspace(0.0, 1.0, n_bins)
+    base = 100.0 * (1.0 + 0.5 * np.sin(5.0 * x)) + 5.0 * rs.rand(n_bins)
+    a = np.linspace(-0.5, 0.5, n_k)[:, None]
+    return base[None, :] * (1.0 + 0.1 * a * np.cos(3.0 * x)[None, :] + 0.05 * rs.rand(n_k, 1) * x[None, :])
+
+
+def _time(fn, reps):
+    import torch
+
+    fn()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    fn()
+    torch.cuda.synchronize()
+    if time.perf_counter() - t0 > 0.5:
+        reps = min(reps, 5)
+    ts = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        ts.append(a.elapsed_time(b))
+    return dict(ms_median=round(float(np.median(ts)), 4), ms_min=round(float(np.min(ts)), 4), launches=reps)
+
+
+def kernel_lines(reps, forms=("direct", "product")):
+    import torch
+
+    from pisa_amd import kernels as K
+
+    dev = K.device()
+    for (n_t, n_k, n_b), outputs in (((10 ** 4, 10 ** 2, 128), ("matrix", "reduced")),
+                                     ((10 ** 5, 10 ** 3, 128), ("reduced",)),
+                                     ((10 ** 4, 10 ** 3, 4800), ("matrix", "reduced"))):
+        e_host = _templates(n_k, n_b)
+        rs = np.random.RandomState(1)
+        d = torch.from_numpy(rs.poisson(e_host[rs.randint(0, n_k, n_t)]).astype(np.float64)).to(dev)
+        e = torch.from_numpy(e_host).to(dev)
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+        for kind in ("llh", "poisson_llh", "chi2"):
+            for form in [f for f in forms if f == "direct" or kind != "chi2"]:
+                for output in outputs:
+                    if output == "matrix":
+                        res = _time(lambda: K.metric_matrix(kind, d, e, form=form, status=status), reps)
+                    else:
+                        res = _time(lambda: K.metric_matrix_best(kind, d, e, k0=n_k // 2, form=form, status=status), reps)
+                    line = dict(workload="kernel", T=n_t, K=n_k, B=n_b, kind=kind, form=form, output=output, **res)
+                    if form == "product":
+                        flop = (4.0 if kind == "llh" else 2.0) * n_t * n_k * n_b
+                        line["tflops"] = round(flop / (res["ms_median"] * 1e-3) / 1e12, 3)
+                        line["frac_of_fp64_peak"] = round(line["tflops"] / FP64_PEAK_TFLOPS, 4)
+                    print(json.dumps(line), flush=True)
+        assert int(status.item()) == 0
+        if n_t == 10 ** 4 and n_k == 10 ** 2 and "direct" in forms:
+            total = torch.empty(1, dtype=torch.float64, device=dev)
+            for kind in ("llh", "poisson_llh", "chi2"):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for t in range(100):
+                    for k in range(100):
+                        K.metric(kind, d[t], e[k], total_out=total, status=status)
+                torch.cuda.synchronize()
+                print(json.dumps(dict(workload="loop_over_kernels_metric", T=100, K=100, B=n_b, kind=kind,
+                                      ms=round(1e3 * (time.perf_counter() - t0), 3), launches=10 ** 4)), flush=True)
+        del d, e
+
+
+class _TimedSolver:
+    """`DeviceSolver` with a synchronise after the upload and after the launches: their wall times, summed"""
+
+    def __init__(self, solver, timings):
+        self.solver, self.timings = solver, timings
+
+    def best(self, kind, data, expected, sigma2=None, offset=None, k0=0):
+        import torch
+
+        t0 = time.perf_counter()
+        dev = [self.solver._up(a) for a in (data, expected, sigma2, offset)]
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        out = self.solver.best(kind, *dev, k0=k0)
+        torch.cuda.synchronize()
+        self.timings["upload"] = self.timings.get("upload", 0.0) + (t1 - t0)
+        self.timings["kernels"] = self.timings.get("kernels", 0.0) + (time.perf_counter() - t1)
+        return out
+
+
+def e2e_line(n_trials, true_points):
+    import torch
+
+    from pisa_amd import kernels as K
+    from pisa_amd.analysis import ensemble as en
+
+    side, n_b = 30, 128
+    hist = _templates(side * side, n_b, seed=3)
+    grid = en.TemplateGrid(K.to_device(hist), K.to_device(0.0 * hist), np.zeros((side * side, 2)), None, None, "llh")
+    grid._host["hist"] = hist
+    timings = {}
+    draw = en.pseudo_data
+
+    def timed_draw(*a, **k):
+        t0 = time.perf_counter()
+        out = draw(*a, **k)
+        timings["draw"] = timings.get("draw", 0.0) + (time.perf_counter() - t0)
+        return out
+
+    points = None if true_points is None else list(range(0, side * side, max(1, side * side // true_points)))[:true_points]
+    en.feldman_cousins(grid, "llh", 64, random_state=1, true_points=[0])       # (first launches, allocator)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    en.pseudo_data = timed_draw
+    try:
+        crit = en.feldman_cousins(grid, "llh", n_trials, random_state=1, true_points=points,
+                                  solver=_TimedSolver(en.DeviceSolver(), timings))
+    finally:
+        en.pseudo_data = draw
+    torch.cuda.synchronize()
+    wall = time.perf_counter() - t0
+    print(json.dumps(dict(workload="feldman_cousins", grid="%dx%d" % (side, side), B=n_b, T=n_trials, metric="llh",
+                          true_points=crit.shape[0], wall_s=round(wall, 3), draw_s=round(timings["draw"], 3),
+                          upload_s=round(timings["upload"], 3), kernels_s=round(timings["kernels"], 3),
+                          other_s=round(wall - timings["draw"] - timings["upload"] - timings["kernels"], 3),
+                          crit90_mean=round(float(crit[:, 1].mean()), 6))), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--trials", type=float, default=1e4)
+    ap.add_argument("--true-points", type=int, default=None, help="only this many true points of the 900 (default: all)")
+    ap.add_argument("--forms", default="direct,product", help="the kernel forms to time")
+    ap.add_argument("--skip-e2e", action="store_true")
+    ap.add_argument("--skip-kernels", action="store_true")
+    args = ap.parse_args()
+    import torch
+
+    torch.cuda.set_device(0)
+    if not args.skip_kernels:
+        kernel_lines(args.reps, tuple(args.forms.split(",")))
+    if not args.skip_e2e:
+        e2e_line(int(args.trials), args.true_points)
+
+
+if __name__ == "__main__":
+    main()
