@@ -2421,12 +2421,17 @@ PISA_API int pisa_hip_kde_create(int32_t dim, const double *d_x, const double *d
         // r_cut / 8 wide, so the bound depends on tol through the cell size as well: 20 at 1e-14 (1.8e-15), 16 at 1e-12
         // (2.8e-12; round 4 took 18 there: 3.5e-14, 28 x finer than the cut-off it sits beside), 14 at 1e-10.  The pilot's
         // error reaches a density only through lambda = (pilot / g)^-alpha, i.e. scaled by alpha (<= 1).
-        int P = 20;
-        for (int cand : {14, 16, 18}) {
+        // The cells are wider than r_cut / 8 where the grid had to fit cells_cap(n) (a far outlier, with or without weight,
+        // widens the bounding box): if order 20 misses the bound as well there is no expansion, the pilot is the direct
+        // pair sum (n_dense = 0).  Before, 20 was taken unchecked: pilot errors of 5e-6 of a cell's weight at cell = 3.8.
+        int P = 0;
+        for (int cand : {14, 16, 18, 20}) {
             double bound = 2.3 * 1.09 * 1.09, fact = 1.0;
             for (int i = 1; i <= cand; i++) { bound *= 0.5 * g.cell; fact *= (double)i; }
             if (bound / sqrt(fact) <= 4.0 * tol) { P = cand; break; }
         }
+        const bool series_ok = P != 0;
+        if (!series_ok) P = 20;   // (sizes below only)
         // local expansions need the intermediate V of every cell of the grid: bounded
         const bool local_ok = g_kde_expansion >= 2 && ceil(sqrt(g.rcut2) * g.inv_cell) <= (double)H2L_MAX_REACH &&
                               (double)k->n_cells * (P * P) * 8.0 < 2.0e9;
@@ -2437,7 +2442,7 @@ PISA_API int pisa_hip_kde_create(int32_t dim, const double *d_x, const double *d
         constexpr int64_t expansion_min_n = 1000;
         // (1 000: C3-shaped evaluations of 1e5 / 3e5 events take 11.5 / 27.5 ms with the round-2 threshold of 20 000 sources per
         //  estimator -- direct pair sums below it --, 5.7 / 5.9 ms with this one)
-        if (g_kde_expansion && dim == 2 && cut && n >= expansion_min_n) {
+        if (g_kde_expansion && series_ok && dim == 2 && cut && n >= expansion_min_n) {
             for (size_t h = 0; h < h_starts.size(); h++) {
                 const int64_t end = h + 1 < h_starts.size() ? h_starts[h + 1] : n;
                 if (end - h_starts[h] < dense_min) continue;
