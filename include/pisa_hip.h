@@ -392,6 +392,45 @@ int pisa_hip_reweight_hist_acc(const pisa_hip_container *h_containers, int32_t n
                                const pisa_hip_binning *h_out_binning, int64_t *d_limbs,
                                int32_t *d_status, void *stream);
 
+/* ------------------------------------------------ the accumulate plan
+ * Events outside the output binning deposit nothing at any parameter point, and which they are is fixed by the
+ * binning and the events' static coordinates.  The resident order (pisa_hip_deposit_block_order) gathers the others
+ * into whole blocks of 256 events; a plan lists, once per set of containers, the blocks that hold at least one event
+ * whose BIN half of d_node_bin16 is not 0xffff (padding, 0xffffffff, is idle by the same rule; an event inside the
+ * binning but outside the calc grid counts: it still forms its product and flags a non-finite flux).  A planned call
+ * streams the listed blocks alone, dealt round robin to the wavefronts of the container's workgroups, and gives the
+ * same limbs and the same status word as pisa_hip_reweight_hist[_acc]: the sums are exact in any order.
+ *
+ * _create   applies where pisa_hip_reweight_hist uses the 16-bit index form with every accumulator in LDS
+ *           (d_node_bin16 / d_weighted_flux_q for every container with events, calc grid and binning below 65535
+ *           entries, pisa_hip_hist_window_bins(n_bins) == 0).  Elsewhere it returns PISA_HIP_OK with *plan = NULL and
+ *           the caller keeps to pisa_hip_reweight_hist[_acc].  Reads every index column once on `stream` and
+ *           synchronises it (the block counts go to the host, where the work split is made: one workgroup per CU,
+ *           dealt to the containers by their DEPOSITING events; a container without any gets none).
+ * _destroy  NULL is fine.
+ * _info     for tests and diagnostics: blocks of 256 events of one container, how many of them are listed, the
+ *           workgroups it gets, and (h_dep_blocks != NULL: room for n_dep_blocks int32) the list itself, ascending.
+ * _planned  pisa_hip_reweight_hist (clear_first != 0) or _acc (clear_first == 0) through the plan.  `scale` and every
+ *           column pointer are read from h_containers at each call; the plan contributes the lists and the work
+ *           split only.  PISA_HIP_ERR_INVALID if n_containers, an event count, the grid or the binning differ from
+ *           what the plan was made from, or if the call would not use the 16-bit index form (no gather table).
+ *
+ * THE PLAN SNAPSHOTS WHICH BLOCKS DEPOSIT.  A caller that rewrites a d_node_bin16 column (another binning, another
+ * event order, other events) makes a new plan.  Flux refreshes -- pisa_hip_fold_flux, the Barr folds -- write
+ * d_weighted_flux_q only and leave a plan valid. */
+typedef struct pisa_hip_hist_plan pisa_hip_hist_plan;
+int pisa_hip_hist_plan_create(const pisa_hip_container *h_containers, int32_t n_containers,
+                              const pisa_hip_binning *h_calc_grid, const pisa_hip_binning *h_out_binning,
+                              pisa_hip_hist_plan **plan, void *stream);
+int pisa_hip_hist_plan_destroy(pisa_hip_hist_plan *plan);
+int pisa_hip_hist_plan_info(const pisa_hip_hist_plan *plan, int32_t container, int32_t *n_blocks,
+                            int32_t *n_dep_blocks, int32_t *workgroups, int32_t *h_dep_blocks);
+int pisa_hip_reweight_hist_planned(const pisa_hip_hist_plan *plan, const pisa_hip_container *h_containers,
+                                   int32_t n_containers, const pisa_hip_binning *h_calc_grid,
+                                   const double *d_prob_nu, const double *d_prob_nubar, const double *d_pepmu,
+                                   const pisa_hip_binning *h_out_binning, int64_t *d_limbs, int32_t *d_status,
+                                   int32_t clear_first, void *stream);
+
 /* Largest n_containers*n_bins pisa_hip_finalize_metric accepts (one workgroup). */
 #define PISA_HIP_FINALIZE_METRIC_MAX 4096
 
@@ -509,7 +548,8 @@ int pisa_hip_finalize_metric_parts(int64_t *d_limbs, int32_t n_points, int32_t n
  * that per point).  An evaluator is made once per pipeline from everything that does not change between
  * parameter points (the event columns, the binnings, the grid plan, the output buffers); per point
  *      pisa_hip_evaluator_eval(ev, params, kind, d_actual, ...)
- * enqueues  pisa_hip_prob3_grid_planned (gather tables only) -> pisa_hip_reweight_hist[_acc] ->
+ * enqueues  pisa_hip_prob3_grid_planned (gather tables only) -> pisa_hip_reweight_hist[_acc] (through a
+ * pisa_hip_hist_plan of the evaluator's own, made by _create from the containers it copies, where one applies) ->
  * [all-reduce of the limbs] -> pisa_hip_finalize_metric_parts (16 workgroups, clear_limbs = 1)  -- the same
  * launches, the same bits as those four calls -- and, if asked to, waits for the value: the metric's sixteen
  * partial sums arrive in device-mapped pinned host memory and are joined as pisa_hip_finalize_metric_parts
@@ -541,6 +581,8 @@ typedef struct {
     pisa_hip_allreduce_fn allreduce;
     void *comm;
 } pisa_hip_evaluator_desc;
+/* _create reads the d_node_bin16 columns of the containers (the evaluator's pisa_hip_hist_plan): it waits for the
+ * whole device first, so columns written on any stream before the call are seen complete. */
 int pisa_hip_evaluator_create(const pisa_hip_evaluator_desc *desc, pisa_hip_evaluator **out);
 int pisa_hip_evaluator_destroy(pisa_hip_evaluator *ev);
 /* aeff.py:78-86: the scale of one container (aeff_scale * livetime * norms) for the points to come */

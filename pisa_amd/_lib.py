@@ -282,6 +282,10 @@ _SIGS = {
     "pisa_hip_finalize_metric": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "pisa_hip_finalize_metric_scaled": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "pisa_hip_prob3_grid_planned_multi": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "pisa_hip_hist_plan_create": (C.c_int, [C.POINTER(Container), C.c_int32, C.POINTER(Binning), C.POINTER(Binning), C.POINTER(C.c_void_p), C.c_void_p]),
+    "pisa_hip_hist_plan_destroy": (C.c_int, [C.c_void_p]),
+    "pisa_hip_hist_plan_info": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p]),
+    "pisa_hip_reweight_hist_planned": (C.c_int, [C.c_void_p, C.POINTER(Container), C.c_int32, C.POINTER(Binning), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Binning), C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "pisa_hip_reweight_hist_multi": (C.c_int, [C.POINTER(Container), C.c_int32, C.POINTER(Binning), C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(Binning), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "pisa_hip_multi_points_per_pass": (C.c_int, [C.c_int64]),
     "pisa_hip_finalize_metric_multi": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),

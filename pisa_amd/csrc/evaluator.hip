@@ -17,6 +17,7 @@ struct pisa_hip_evaluator {
     pisa_hip_binning calc_grid, out_binning;
     pisa_hip_evaluator_desc d;
     int64_t n_bins, limb_count;
+    pisa_hip_hist_plan *hist_plan;   // of `cont` (NULL where none applies): the accumulation streams the depositing blocks only
 };
 
 using namespace pisa;
@@ -43,11 +44,24 @@ PISA_API int pisa_hip_evaluator_create(const pisa_hip_evaluator_desc *desc, pisa
     ev->d.h_out_binning = &ev->out_binning;
     ev->n_bins = n_bins;
     ev->limb_count = (int64_t)desc->n_containers * n_bins * 2 * PISA_HIP_ACC_LIMBS;
+    ev->hist_plan = nullptr;
+    // the plan reads every index column: a device-wide wait first, so that columns still being written on another
+    // stream (a non-blocking one does not order with the null stream) are complete when they are marked
+    if ((rc = check_hip(hipDeviceSynchronize(), "hipDeviceSynchronize"))) {
+        delete ev;
+        return rc;
+    }
+    if ((rc = pisa_hip_hist_plan_create(ev->cont.data(), desc->n_containers, &ev->calc_grid, &ev->out_binning,
+                                        &ev->hist_plan, nullptr))) {
+        delete ev;
+        return rc;
+    }
     *out = ev;
     return PISA_HIP_OK;
 }
 
 PISA_API int pisa_hip_evaluator_destroy(pisa_hip_evaluator *ev) {
+    if (ev) pisa_hip_hist_plan_destroy(ev->hist_plan);
     delete ev;
     return PISA_HIP_OK;
 }
@@ -71,9 +85,14 @@ PISA_API int pisa_hip_evaluator_eval(pisa_hip_evaluator *ev, const pisa_hip_prob
         for (int k = 0; k < n_part; k++) part[k] = NAN;   // "not yet": a partial sum is never NaN unless an input was negative
     int rc = pisa_hip_prob3_grid_planned(h_params, d.plan, d.d_energy, d.n_e, d.e_major, nullptr, nullptr, d.d_pepmu, stream);
     if (rc) return rc;
-    rc = (limbs_zero ? pisa_hip_reweight_hist_acc : pisa_hip_reweight_hist)(
-        ev->cont.data(), (int32_t)ev->cont.size(), &ev->calc_grid, nullptr, nullptr, d.d_pepmu, &ev->out_binning,
-        d.d_limbs, d.d_status, stream);
+    if (ev->hist_plan)
+        rc = pisa_hip_reweight_hist_planned(ev->hist_plan, ev->cont.data(), (int32_t)ev->cont.size(), &ev->calc_grid, nullptr,
+                                            nullptr, d.d_pepmu, &ev->out_binning, d.d_limbs, d.d_status, limbs_zero ? 0 : 1,
+                                            stream);
+    else
+        rc = (limbs_zero ? pisa_hip_reweight_hist_acc : pisa_hip_reweight_hist)(
+            ev->cont.data(), (int32_t)ev->cont.size(), &ev->calc_grid, nullptr, nullptr, d.d_pepmu, &ev->out_binning,
+            d.d_limbs, d.d_status, stream);
     if (rc) return rc;
     if (d.allreduce) {
         const int nrc = d.allreduce(d.d_limbs, d.d_limbs, (size_t)ev->limb_count, 4 /* ncclInt64 */, 0 /* ncclSum */,

@@ -28,10 +28,25 @@
 #include <algorithm>
 #include <atomic>
 #include <string.h>
+#include <vector>
 
 #include "common.hpp"
 #include "metric_device.hpp"
 #include "gpllh_device.hpp"
+
+// The accumulate plan of a set of containers (include/pisa_hip.h, pisa_hip_hist_plan_create): which 256-event
+// blocks of every container hold an event that can deposit, and the work split of the launches that sweep them.
+struct pisa_hip_hist_plan {
+    int32_t n_cont = 0, threads = 0;
+    int64_t n_nodes = 0, n_bins = 0;
+    std::vector<int64_t> n_events;           // per container: the snapshot a planned call is checked against
+    std::vector<int32_t> n_blocks, n_dep;    // per container: blocks of 256 events / those that deposit
+    std::vector<const int32_t *> list;       // per container: DEVICE block numbers, ascending; nullptr = every block
+    std::vector<int64_t> offset;             // per container: its list starts at d_lists + offset
+    std::vector<int32_t> blk_start;          // per launch (MAX_CONT containers): MAX_CONT + 1 entries
+    std::vector<int64_t> chunk;              // per launch
+    int32_t *d_lists = nullptr;              // one allocation: the lists, the counts, the marks
+};
 
 namespace pisa {
 
@@ -191,6 +206,10 @@ struct ContDev {
     // bins [p W, (p+1) W), W = the LDS window (HistArgs::window)
     const int32_t *part_start;
     int32_t n_part, part_width;
+    // optional (pisa_hip_hist_plan; MODE 7 sweeping together): the n_dep blocks of 256 events that hold an event which
+    // can deposit, ascending -- the sweep visits these and no other block
+    const int32_t *dep_blocks;
+    int32_t n_dep, reserved;
 };
 
 struct HistArgs {
@@ -211,6 +230,7 @@ struct HistArgs {
                           // Development library only (PISA_HIP_HIST_DBG): 2 no deposits, 4 no flush
     int32_t window;       // > 0: LDS holds this many bins starting at the chunk's lowest bin
 };
+static_assert(sizeof(HistArgs) + 2 * sizeof(void *) <= 4096, "kernel arguments of hist_accumulate_kernel beyond 4 KiB");
 
 // MODE 0: generic histogram (weights or counts; quantities (w, 1))
 // MODE 1: fused reweight chain from coordinates (quantities (w, w^2))
@@ -284,6 +304,24 @@ hist_accumulate_kernel(const HistArgs a, unsigned long long *__restrict__ g_limb
     const int64_t q_end = ((together ? C.n : end) + 3) >> 2;
     int64_t q = (together ? lb * nthreads : (start >> 2)) + threadIdx.x;
     bool qhave = QUAD && q < q_end;
+    // Planned sweep (ContDev::dep_blocks): the wavefronts of the container's workgroups take the listed blocks round
+    // robin -- wavefront wv of workgroup lb the ordinals lb W + wv + i W n_wg (W wavefronts per workgroup), ordinal o
+    // standing for block dep[o] -- so every workgroup's share is equal to within one block.  The block number is one
+    // scalar load per sweep (the list is written once, by the plan: constant address space), fetched a sweep ahead of
+    // the column loads that need it.  No list: the direct index above, a wave-uniform choice.
+    typedef const int32_t __attribute__((address_space(4))) *dep_list;
+    const dep_list dep = QUAD && together ? (dep_list)C.dep_blocks : nullptr;
+    const int o_step = (int)n_wg * (nthreads >> 6);
+    const int n_dep = C.n_dep;
+    int o = 0, blk_next = 0;
+    if (QUAD && dep) {
+        o = __builtin_amdgcn_readfirstlane((int)lb * (nthreads >> 6) + (int)(threadIdx.x >> 6));
+        const int last = n_dep - 1;
+        const int blk = dep[o < last ? o : last];
+        blk_next = dep[o + o_step < last ? o + o_step : last];
+        q = (int64_t)blk * 64 + (threadIdx.x & 63);
+        qhave = o < n_dep && q < q_end;
+    }
     uint4 qx = make_uint4(~0u, ~0u, ~0u, ~0u);
     double2 g0 = awa, g1 = awa;
     if (QUAD && qhave) {
@@ -493,8 +531,17 @@ hist_accumulate_kernel(const HistArgs a, unsigned long long *__restrict__ g_limb
             const unsigned b2 = qx.z >> 16, b3 = qx.w >> 16;
             double2 p2 = tab[n2 == 0xffffu ? 0 : n2];
             double2 p3 = tab[n3 == 0xffffu ? 0 : n3];
-            const int64_t qn = q + qstep;
-            const bool have_n = qn < q_end;
+            int64_t qn = q + qstep;
+            bool have_n = qn < q_end;
+            if (dep) {   // (wave-uniform) the next listed block, and the number of the one after it
+                // (the lanes of a wavefront leave the sweep one by one in its last block only: `o` is the same in
+                // all that are here, which the compiler cannot see across the loops)
+                const int o_next = __builtin_amdgcn_readfirstlane(o + o_step), last = n_dep - 1;
+                qn = (int64_t)blk_next * 64 + (threadIdx.x & 63);
+                have_n = o_next < n_dep && qn < q_end;
+                blk_next = dep[o_next + o_step < last ? o_next + o_step : last];
+                o = o_next;
+            }
             const int64_t ql = have_n ? qn : q;  // unconditional loads (the last sweep re-reads its own quad)
             const uint4 qxn = idxq[ql];
             const double2 *gn = aw + ((ql >> 6) * 256 + (ql & 63));
@@ -511,6 +558,9 @@ hist_accumulate_kernel(const HistArgs a, unsigned long long *__restrict__ g_limb
             q = qn;
             qhave = have_n;
         }
+        // (nothing after the sweep reads the ordinal: said here, it and the block number stay wave-uniform values in
+        // scalar registers inside the sweep although the lanes leave it one by one)
+        o = 0; blk_next = 0;
         if (part < 0) break;
         // next partition of this chunk, if any
         const int64_t pe = (int64_t)s_part[part + 1] * 256;
@@ -1302,6 +1352,11 @@ static int plan_blocks(const int64_t *n_events, int n_cont, int threads, int64_t
     return plan_blocks_balanced(n_events, n_cont, threads, target, chunk, blk_start);
 }
 
+static int hist_threads() {
+    const int threads = PISA_DEV_INT("HIST_THREADS", 1024);
+    return threads < 64 || threads > 1024 || (threads & 63) ? HIST_THREADS : threads;
+}
+
 // optional hipEvent pair recorded around the accumulate kernel of the next
 // hist launch (bench.py measures the dominant kernel with them)
 static thread_local hipEvent_t g_prof_start = nullptr, g_prof_stop = nullptr;
@@ -1310,7 +1365,7 @@ static int run_hist(const ContDev *conts, int n_cont, int mode, const DevBinning
                     int64_t n_nodes, const double *prob_nu, const double *prob_nubar,
                     const double *pepmu, const DevBinning &outb, int64_t n_bins,
                     long long *d_limbs, int32_t *d_status, hipStream_t s, bool clear_first = true,
-                    bool second_quantity = true) {
+                    bool second_quantity = true, const pisa_hip_hist_plan *plan = nullptr) {
     if (n_bins > (1 << 28)) return PISA_HIP_ERR_INVALID;
     int64_t lds_bytes = lds_acc_bytes(n_bins);
     bool lds = lds_bytes <= LDS_ACC_BYTES_MAX;
@@ -1350,12 +1405,23 @@ static int run_hist(const ContDev *conts, int n_cont, int mode, const DevBinning
         for (int c = 0; c < nc; c++) {
             a.cont[c] = conts[base + c];
             nev[c] = conts[base + c].n;
+            a.cont[c].dep_blocks = plan ? plan->list[base + c] : nullptr;
+            a.cont[c].n_dep = plan ? plan->n_dep[base + c] : 0;
+            a.cont[c].reserved = 0;
             // the partitioned order is used where its partitions are this launch's LDS windows
             if (!(window > 0 && mode == 7 && a.cont[c].part_width == window)) a.cont[c].part_start = nullptr;
         }
-        int threads = PISA_DEV_INT("HIST_THREADS", 1024);
-        if (threads < 64 || threads > 1024 || (threads & 63)) threads = HIST_THREADS;
-        int nblocks = plan_blocks(nev, nc, threads, a.chunk, a.blk_start);
+        int threads = hist_threads();
+        int nblocks;
+        if (plan) {   // the split made with the plan, from the depositing blocks of every container
+            threads = plan->threads;
+            const int32_t *bs = plan->blk_start.data() + (size_t)(base / MAX_CONT) * (MAX_CONT + 1);
+            for (int c = 0; c <= MAX_CONT; c++) a.blk_start[c] = bs[c];
+            a.chunk = plan->chunk[base / MAX_CONT];
+            nblocks = a.blk_start[nc];
+        } else {
+            nblocks = plan_blocks(nev, nc, threads, a.chunk, a.blk_start);
+        }
         if (nblocks <= 0) continue;
         for (int c = 0; c < nc; c++) {
             a.cont_chunk[c] = 0;
@@ -1478,7 +1544,8 @@ static int reweight_hist_impl(const pisa_hip_container *h_containers, int32_t n_
                               const pisa_hip_binning *h_calc_grid, const double *d_prob_nu,
                               const double *d_prob_nubar, const double *d_pepmu,
                               const pisa_hip_binning *h_out_binning, int64_t *d_limbs,
-                              int32_t *d_status, void *stream, bool clear_first) {
+                              int32_t *d_status, void *stream, bool clear_first,
+                              const pisa_hip_hist_plan *plan = nullptr) {
     if (!h_containers || n_containers < 1 || n_containers > 1024 || !d_limbs)
         return PISA_HIP_ERR_INVALID;
     DevBinning grid, outb;
@@ -1538,8 +1605,10 @@ static int reweight_hist_impl(const pisa_hip_container *h_containers, int32_t n_
         d.flav = h.flav;
         d.side = h.nubar > 0 ? 0 : 1;
     }
+    // a plan stands for the 16-bit index form of exactly these containers on this grid and binning
+    if (plan && !(all_idx16 && n_nodes == plan->n_nodes && n_bins == plan->n_bins)) { delete[] conts; return PISA_HIP_ERR_INVALID; }
     rc = run_hist(conts, n_containers, all_idx16 ? 7 : all_compact ? 5 : (all_packed ? 3 : (all_indexed ? 2 : 1)), &grid, n_nodes, d_prob_nu, d_prob_nubar,
-                  d_pepmu, outb, n_bins, (long long *)d_limbs, d_status, as_stream(stream), clear_first);
+                  d_pepmu, outb, n_bins, (long long *)d_limbs, d_status, as_stream(stream), clear_first, true, plan);
     delete[] conts;
     return rc;
 }
@@ -1561,6 +1630,163 @@ PISA_API int pisa_hip_reweight_hist_acc(const pisa_hip_container *h_containers,
                                         int32_t *d_status, void *stream) {
     return reweight_hist_impl(h_containers, n_containers, h_calc_grid, d_prob_nu, d_prob_nubar,
                               d_pepmu, h_out_binning, d_limbs, d_status, stream, false);
+}
+
+// ---------------------------------------------------------------------------
+// THE ACCUMULATE PLAN (pisa_hip_hist_plan_*): which events lie outside the output binning is fixed by the binning and
+// the events' static coordinates; the resident order (order.hip, `deposit_block_order`) gathers the others into whole
+// blocks of 256.  The plan lists those blocks once, and hist_accumulate_kernel<7, true> then streams them alone.
+namespace pisa {
+
+// marks[b] = block b of 256 events holds an event whose bin half is not 0xffff (the multi-point kernel's `any_in`:
+// the bin alone -- an event inside the binning but outside the calc grid still forms its product)
+__global__ void __launch_bounds__(256)
+hist_plan_mark_kernel(const uint32_t *__restrict__ idx16, uint8_t *__restrict__ marks) {
+    const uint32_t v = idx16[(int64_t)blockIdx.x * 256 + threadIdx.x];   // (the column is padded to whole blocks)
+    const int any = __syncthreads_or((v >> 16) != 0xffffu);
+    if (threadIdx.x == 0) marks[blockIdx.x] = (uint8_t)(any != 0);
+}
+
+// the marked block numbers, ascending, and their count: one workgroup, every thread a contiguous run of blocks
+__global__ void __launch_bounds__(1024)
+hist_plan_compact_kernel(const uint8_t *__restrict__ marks, int32_t n_blocks, int32_t *__restrict__ list,
+                         int32_t *__restrict__ count) {
+    __shared__ int s_cnt[1024];
+    const int t = threadIdx.x;
+    const int per = (n_blocks + 1023) / 1024;
+    const int lo = t * per < n_blocks ? t * per : n_blocks;
+    const int hi = lo + per < n_blocks ? lo + per : n_blocks;
+    int cnt = 0;
+    for (int b = lo; b < hi; b++) cnt += marks[b];
+    s_cnt[t] = cnt;
+    __syncthreads();
+    for (int d = 1; d < 1024; d <<= 1) {   // inclusive scan
+        const int v = t >= d ? s_cnt[t - d] : 0;
+        __syncthreads();
+        s_cnt[t] += v;
+        __syncthreads();
+    }
+    int pos = s_cnt[t] - cnt;
+    for (int b = lo; b < hi; b++)
+        if (marks[b]) list[pos++] = b;
+    if (t == 1023) *count = s_cnt[1023];
+}
+
+}  // namespace pisa
+
+PISA_API int pisa_hip_hist_plan_destroy(pisa_hip_hist_plan *plan) {
+    if (!plan) return PISA_HIP_OK;
+    if (plan->d_lists) (void)hipFree(plan->d_lists);   // (waits for the launches that still read it)
+    delete plan;
+    return PISA_HIP_OK;
+}
+
+PISA_API int pisa_hip_hist_plan_create(const pisa_hip_container *h_containers, int32_t n_containers,
+                                       const pisa_hip_binning *h_calc_grid, const pisa_hip_binning *h_out_binning,
+                                       pisa_hip_hist_plan **out, void *stream) {
+    if (!out) return PISA_HIP_ERR_INVALID;
+    *out = nullptr;
+    if (!h_containers || n_containers < 1 || n_containers > 1024) return PISA_HIP_ERR_INVALID;
+    DevBinning grid, outb;
+    int64_t n_nodes, n_bins;
+    int rc = make_dev_binning(h_calc_grid, grid, n_nodes);
+    if (rc) return rc;
+    if (grid.ndim > 2) return PISA_HIP_ERR_INVALID;
+    if ((rc = make_dev_binning(h_out_binning, outb, n_bins))) return rc;
+    // where reweight_hist_impl chooses MODE 7 and run_hist no window: 16-bit indices for every container with
+    // events, all accumulators in LDS
+    if (!(n_nodes < 0xffff && n_bins < 0xffff) || lds_acc_bytes(n_bins) > LDS_ACC_BYTES_MAX) return PISA_HIP_OK;
+    int64_t total = 0;
+    for (int c = 0; c < n_containers; c++) {
+        const pisa_hip_container &h = h_containers[c];
+        if (h.n_events < 0 || h.n_events > (1LL << 38)) return PISA_HIP_ERR_INVALID;
+        if (h.n_events > 0 && !(h.d_node_bin16 && h.d_weighted_flux_q)) return PISA_HIP_OK;
+        total += (h.n_events + 255) / 256;
+    }
+    if (total >= (1LL << 31)) return PISA_HIP_ERR_INVALID;
+    pisa_hip_hist_plan *p = new pisa_hip_hist_plan();
+    p->n_cont = n_containers;
+    p->threads = hist_threads();
+    p->n_nodes = n_nodes;
+    p->n_bins = n_bins;
+    p->n_events.resize(n_containers);
+    p->n_blocks.resize(n_containers);
+    p->n_dep.assign(n_containers, 0);
+    p->list.assign(n_containers, nullptr);
+    p->offset.resize(n_containers);
+    // one allocation: int32 lists[total] | int32 counts[n_containers] | uint8 marks[total]
+    const size_t bytes = (size_t)(total + n_containers) * 4 + (size_t)total;
+    hipStream_t s = as_stream(stream);
+    auto fail = [&](int code) { pisa_hip_hist_plan_destroy(p); return code; };
+    if ((rc = check_hip(hipMalloc((void **)&p->d_lists, bytes), "hipMalloc"))) return fail(rc);
+    int32_t *d_counts = p->d_lists + total;
+    uint8_t *d_marks = reinterpret_cast<uint8_t *>(d_counts + n_containers);
+    if ((rc = check_hip(hipMemsetAsync(d_counts, 0, (size_t)n_containers * 4, s), "hipMemsetAsync"))) return fail(rc);
+    int64_t at = 0;
+    for (int c = 0; c < n_containers; c++) {
+        const pisa_hip_container &h = h_containers[c];
+        const int32_t nb = (int32_t)((h.n_events + 255) / 256);
+        p->n_events[c] = h.n_events;
+        p->n_blocks[c] = nb;
+        p->offset[c] = at;
+        if (nb > 0) {
+            hipLaunchKernelGGL(hist_plan_mark_kernel, dim3((unsigned)nb), dim3(256), 0, s, h.d_node_bin16, d_marks + at);
+            hipLaunchKernelGGL(hist_plan_compact_kernel, dim3(1), dim3(1024), 0, s, d_marks + at, nb, p->d_lists + at,
+                               d_counts + c);
+        }
+        at += nb;
+    }
+    if ((rc = check_hip(hipGetLastError(), "hist_plan kernels"))) return fail(rc);
+    if ((rc = check_hip(hipMemcpyAsync(p->n_dep.data(), d_counts, (size_t)n_containers * 4, hipMemcpyDeviceToHost, s),
+                        "hipMemcpyAsync"))) return fail(rc);
+    if ((rc = check_hip(hipStreamSynchronize(s), "hipStreamSynchronize"))) return fail(rc);
+    // the work split, once: plan_blocks on the DEPOSITING events of every container (a container without any gets no
+    // workgroup, the others at least one sweep per workgroup and together one workgroup per CU)
+    for (int base = 0; base < n_containers; base += MAX_CONT) {
+        const int nc = n_containers - base < MAX_CONT ? n_containers - base : MAX_CONT;
+        int64_t nev[MAX_CONT], chunk = 0;
+        int32_t blk_start[MAX_CONT + 1] = {0};
+        for (int c = 0; c < nc; c++) {
+            if (p->n_dep[base + c] < 0 || p->n_dep[base + c] > p->n_blocks[base + c]) return fail(PISA_HIP_ERR_HIP);
+            nev[c] = 256 * (int64_t)p->n_dep[base + c];
+            // every block deposits: no list, the direct index
+            p->list[base + c] = p->n_dep[base + c] < p->n_blocks[base + c] ? p->d_lists + p->offset[base + c] : nullptr;
+        }
+        plan_blocks(nev, nc, p->threads, chunk, blk_start);
+        for (int c = nc; c < MAX_CONT; c++) blk_start[c + 1] = blk_start[nc];
+        p->blk_start.insert(p->blk_start.end(), blk_start, blk_start + MAX_CONT + 1);
+        p->chunk.push_back(chunk);
+    }
+    *out = p;
+    return PISA_HIP_OK;
+}
+
+PISA_API int pisa_hip_hist_plan_info(const pisa_hip_hist_plan *plan, int32_t container, int32_t *n_blocks,
+                                     int32_t *n_dep_blocks, int32_t *workgroups, int32_t *h_dep_blocks) {
+    if (!plan || container < 0 || container >= plan->n_cont) return PISA_HIP_ERR_INVALID;
+    const int32_t *bs = plan->blk_start.data() + (size_t)(container / MAX_CONT) * (MAX_CONT + 1) + container % MAX_CONT;
+    if (n_blocks) *n_blocks = plan->n_blocks[container];
+    if (n_dep_blocks) *n_dep_blocks = plan->n_dep[container];
+    if (workgroups) *workgroups = bs[1] - bs[0];
+    if (h_dep_blocks && plan->n_dep[container] > 0) {
+        if (plan->list[container])
+            PISA_TRY_HIP(hipMemcpy(h_dep_blocks, plan->list[container], (size_t)plan->n_dep[container] * 4, hipMemcpyDeviceToHost));
+        else
+            for (int32_t b = 0; b < plan->n_dep[container]; b++) h_dep_blocks[b] = b;
+    }
+    return PISA_HIP_OK;
+}
+
+PISA_API int pisa_hip_reweight_hist_planned(const pisa_hip_hist_plan *plan, const pisa_hip_container *h_containers,
+                                            int32_t n_containers, const pisa_hip_binning *h_calc_grid,
+                                            const double *d_prob_nu, const double *d_prob_nubar, const double *d_pepmu,
+                                            const pisa_hip_binning *h_out_binning, int64_t *d_limbs,
+                                            int32_t *d_status, int32_t clear_first, void *stream) {
+    if (!plan || !h_containers || n_containers != plan->n_cont) return PISA_HIP_ERR_INVALID;
+    for (int c = 0; c < n_containers; c++)
+        if (h_containers[c].n_events != plan->n_events[c]) return PISA_HIP_ERR_INVALID;
+    return reweight_hist_impl(h_containers, n_containers, h_calc_grid, d_prob_nu, d_prob_nubar, d_pepmu, h_out_binning,
+                              d_limbs, d_status, stream, clear_first != 0, plan);
 }
 
 

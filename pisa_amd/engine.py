@@ -898,6 +898,9 @@ class HotPathEngine:
         self._args = None          # pointers of the engine's buffers as the C ABI takes them (`_arg_block`)
         self._evaluator = None     # pisa_hip_evaluator of the standard shape (`_evaluator_for`)
         self.one_call = True       # eval_host through it; False: the three separate C-ABI calls (tests compare both)
+        self._hist_plan = None     # pisa_hip_hist_plan of `_cont_arr` for the separate accumulate call (`_hist_plan_for`)
+        self.hist_plan = True      # accumulate through a plan (the depositing blocks only) where one applies; False: the
+                                   # un-planned call, which the one-call evaluator does not offer (tests compare both)
         self.data = None
         self._data_src = None
         self._out_block = None   # weak reference to the device-backed maps handed out last
@@ -1049,6 +1052,7 @@ class HotPathEngine:
             out.permute(0, 2, 1, 3).copy_(tmp.view(out.shape[0], 64, 4, 2))
 
     _evaluator = None
+    _hist_plan = None
 
     def set_scale(self, name, scale):
         i = self.names.index(name)
@@ -1192,15 +1196,37 @@ class HotPathEngine:
         if ev is not None:
             _lib.lib().pisa_hip_evaluator_destroy(ev["handle"])
 
+    def _hist_plan_for(self):
+        """the accumulate plan of the container array (`pisa_hip_hist_plan_create`: the blocks of every container that
+        can deposit, and the work split over them) as the handle the planned call takes, or None where none applies;
+        made at the first use and again when the array has been written (`containers_changed`), like the evaluator --
+        which keeps a plan of its own.  Flux refreshes and `set_scale` leave it valid."""
+        hp = self._hist_plan
+        if hp is not None and hp["gen"] == self._cont_gen and hp["cont"] is self._cont_arr:
+            return hp["handle"]
+        self._release_hist_plan()
+        h = C.c_void_p()
+        _lib.check(_lib.lib().pisa_hip_hist_plan_create(self._cont_arr, len(self._cont_arr), C.byref(self.grid.binning),
+                                                        C.byref(self.out_binning), C.byref(h), K._stream()))
+        self._hist_plan = dict(gen=self._cont_gen, cont=self._cont_arr, handle=h if h.value else None)
+        return self._hist_plan["handle"]
+
+    def _release_hist_plan(self):
+        hp, self._hist_plan = self._hist_plan, None
+        if hp is not None and hp["handle"] is not None:
+            _lib.lib().pisa_hip_hist_plan_destroy(hp["handle"])
+
     def __del__(self):
         try:
             self._release_evaluator()
+            self._release_hist_plan()
         except Exception:  # interpreter shutdown
             pass
 
     def close(self):
         """release the evaluator and the direct RCCL communicator (before the process group is destroyed)"""
         self._release_evaluator()
+        self._release_hist_plan()
         if self._rccl:
             self._rccl.destroy()
         self._rccl = None
@@ -1268,8 +1294,13 @@ class HotPathEngine:
         rc = self._flux_tables(pepmu) if self.node_flux else 0
         if rc == 0:
             lib = a["lib"]
-            fn = lib.pisa_hip_reweight_hist_acc if self._limbs_zero else lib.pisa_hip_reweight_hist
-            rc = fn(a["cont"], a["n_cont"], a["grid"], nu, nubar, pepmu, a["outb"], a["limbs"], a["status"], K._stream())
+            plan = self._hist_plan_for() if self.hist_plan and a["cont"] is self._cont_arr else None
+            if plan is not None:
+                rc = lib.pisa_hip_reweight_hist_planned(plan, a["cont"], a["n_cont"], a["grid"], nu, nubar, pepmu, a["outb"],
+                                                        a["limbs"], a["status"], 0 if self._limbs_zero else 1, K._stream())
+            else:
+                fn = lib.pisa_hip_reweight_hist_acc if self._limbs_zero else lib.pisa_hip_reweight_hist
+                rc = fn(a["cont"], a["n_cont"], a["grid"], nu, nubar, pepmu, a["outb"], a["limbs"], a["status"], K._stream())
         self._limbs_zero = self._maps_valid = False
         return rc
 
@@ -1413,7 +1444,7 @@ class HotPathEngine:
         for its value are `tail_host`'s either way."""
         if (self.plan is not None and self.indexed and not self.osc_events and self.data is not None
                 and self._fits_tail()):
-            ev = self._evaluator_for() if self.one_call and kind != GPLLH else None
+            ev = self._evaluator_for() if self.one_call and self.hist_plan and kind != GPLLH else None
             if ev is not None:
                 return self._eval_one_call(ev, params, kind)
             self._lean_front(params)
