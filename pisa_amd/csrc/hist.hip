@@ -5,6 +5,8 @@
 //   histogram_regular       weighted N-D histogram        (translation.py:90-205)
 //   reweight_hist           fused prob3.apply + aeff.apply + hist.apply(sumw2)
 //   hist_finalize           fixed point -> fp64 maps
+// Both accumulate kernels share flush_window / flush_rotation, the weight chains weight_compact / weight_reference and
+// window_lowest_bin; run_hist takes the instantiation of hist_accumulate_kernel from the table hist_forms.
 //
 // ORDER-INDEPENDENT ACCUMULATION.  Every summand x = +-m 2^e is cut EXACTLY into the (at most
 // three) 32-bit digits it occupies in a fixed-point number of NL 32-bit slabs with LSB 2^-116
@@ -232,6 +234,74 @@ struct HistArgs {
 };
 static_assert(sizeof(HistArgs) + 2 * sizeof(void *) <= 4096, "kernel arguments of hist_accumulate_kernel beyond 4 KiB");
 
+// One window of LDS slab accumulators (`ncopies` replicas of n_acc = NL * 2 * n_bins words, first bin `lo`) -> integer
+// units, handed to add(g, bin, v): v units for word g = (bin * 2 + quantity) * NL + slab of the window's limbs.  The
+// loop runs in GLOBAL order (limb fastest): a wave's 64 atomics fall into 512 contiguous bytes, which the L2 atomic
+// units take at full rate (scattered 96 B apart they do not).  Workgroups of a container finish together; each starts
+// at a different offset `rot` (flush_rotation of its ordinal lb) so that they do not all queue on the same limbs.
+__device__ __forceinline__ int flush_rotation(int64_t lb, int n_acc) { return (int)((lb * 7 * 64) % n_acc); }
+template <class F>
+__device__ __forceinline__ void flush_window(const unsigned long long *win, int ncopies, int n_bins, int n_acc,
+                                             int rot, int nthreads, F &&add) {
+    for (int g0 = threadIdx.x; g0 < n_acc; g0 += nthreads) {
+        int g = g0 + rot;
+        if (g >= n_acc) g -= n_acc;
+        const int bin = g / (2 * NL);
+        const int rem = g - bin * 2 * NL;
+        const int q = rem / NL;
+        const int j = rem - q * NL;
+        const int k = (j * 2 + q) * n_bins + bin;
+        unsigned long long v = win[k];
+        for (int r = 1; r < ncopies; r++) v += win[r * n_acc + k];  // integer: exact
+        if (v != 0ull) add(g, bin, v);
+    }
+}
+
+// The two weight chains (-ffp-contract=off for this file: the association is the rounding).  Compact: the flux pair
+// (g_e, g_mu) pre-multiplied by the static per-event factor initial_weights * weighted_aeff.  Reference: its own order.
+__device__ __forceinline__ double weight_compact(double ge, double gmu, double pe, double pmu, double scale) {
+    return ((ge * pe) + (gmu * pmu)) * scale;
+}
+__device__ __forceinline__ double weight_reference(double w0, double fe, double fmu, double pe, double pmu, double ae, double scale) {
+    const double w = w0 * ((fe * pe) + (fmu * pmu));  // prob3.py:622
+    return w * (ae * scale);                          // aeff.py:87
+}
+
+// The lowest bin that events [start, end) of a container deposit into -- where the LDS window of a binning too large
+// for LDS is put; 0 if none deposits.  QUAD: from the index words of the 16-bit form (four events each; q_end: one
+// past the last word of the chunk), else from the packed (node, bin) pairs.  Called by every thread of the workgroup.
+template <bool QUAD>
+__device__ __forceinline__ int window_lowest_bin(const ContDev &C, int64_t start, int64_t end, int64_t q_end, int nthreads) {
+    __shared__ int s_lo;
+    if (threadIdx.x == 0) s_lo = 0x7fffffff;
+    __syncthreads();
+    int m = 0x7fffffff;
+    if (QUAD) {
+        const uint4 *idxq = reinterpret_cast<const uint4 *>(C.idx16);
+        for (int64_t i = (start >> 2) + threadIdx.x; i < q_end; i += nthreads) {
+            const uint4 v = idxq[i];
+            const int b[4] = {(int)(v.x >> 16), (int)(v.y >> 16), (int)(v.z >> 16), (int)(v.w >> 16)};
+#pragma unroll
+            for (int k = 0; k < 4; k++)
+                if (b[k] != 0xffff && b[k] < m) m = b[k];
+        }
+    } else {
+        const int4 *idx4 = reinterpret_cast<const int4 *>(C.node_bin);
+        for (int64_t i = (start >> 1) + threadIdx.x; i < (end >> 1); i += nthreads) {
+            const int4 v = idx4[i];
+            if (v.y >= 0 && v.y < m) m = v.y;
+            if (v.w >= 0 && v.w < m) m = v.w;
+        }
+    }
+    for (int d = 32; d > 0; d >>= 1) {
+        const int other = __shfl_xor(m, d);
+        m = other < m ? other : m;
+    }
+    if ((threadIdx.x & 63) == 0 && m != 0x7fffffff) atomicMin(&s_lo, m);
+    __syncthreads();
+    return s_lo == 0x7fffffff ? 0 : s_lo;
+}
+
 // MODE 0: generic histogram (weights or counts; quantities (w, 1))
 // MODE 1: fused reweight chain from coordinates (quantities (w, w^2))
 // MODE 2: fused reweight chain from pre-digitised indices, 2 events / thread / sweep
@@ -348,34 +418,7 @@ hist_accumulate_kernel(const HistArgs a, unsigned long long *__restrict__ g_limb
             for (int k = threadIdx.x; k <= C.n_part; k += nthreads) s_part[k] = C.part_start[k];
         for (int k = threadIdx.x; k < n_acc * (parts ? 2 : a.copies); k += nthreads) s_acc[k] = 0ull;
         if ((PACKED || QUAD) && a.window > 0 && !(QUAD && C.part_start)) {
-            __shared__ int s_lo;
-            if (threadIdx.x == 0) s_lo = 0x7fffffff;
-            __syncthreads();
-            int m = 0x7fffffff;
-            if (QUAD) {
-                const uint4 *idxq = reinterpret_cast<const uint4 *>(C.idx16);
-                for (int64_t qq = (start >> 2) + threadIdx.x; qq < q_end; qq += nthreads) {
-                    const uint4 v = idxq[qq];
-                    const int b[4] = {(int)(v.x >> 16), (int)(v.y >> 16), (int)(v.z >> 16), (int)(v.w >> 16)};
-#pragma unroll
-                    for (int k = 0; k < 4; k++)
-                        if (b[k] != 0xffff && b[k] < m) m = b[k];
-                }
-            } else {
-            const int4 *idx4 = reinterpret_cast<const int4 *>(C.node_bin);
-            for (int64_t p = (start >> 1) + threadIdx.x; p < (end >> 1); p += nthreads) {
-                const int4 ix = idx4[p];
-                if (ix.y >= 0 && ix.y < m) m = ix.y;
-                if (ix.w >= 0 && ix.w < m) m = ix.w;
-            }
-            }
-            for (int o = 32; o > 0; o >>= 1) {
-                const int other = __shfl_xor(m, o);
-                m = other < m ? other : m;
-            }
-            if ((threadIdx.x & 63) == 0 && m != 0x7fffffff) atomicMin(&s_lo, m);
-            __syncthreads();
-            bin_lo = s_lo == 0x7fffffff ? 0 : s_lo;
+            bin_lo = window_lowest_bin<QUAD>(C, start, end, q_end, nthreads);
         }
         __syncthreads();
     }
@@ -393,24 +436,17 @@ hist_accumulate_kernel(const HistArgs a, unsigned long long *__restrict__ g_limb
         };
         auto add0 = [&](int j, long long d) { put(0, j, (unsigned long long)d); };
         auto add1 = [&](int j, long long d) { put(1, j, (unsigned long long)d); };
-        auto add30 = [&](int j, unsigned long long d0, unsigned long long d1, unsigned long long d2) {
+        auto put3 = [&](int qn, int j, unsigned long long d0, unsigned long long d1, unsigned long long d2) {
             if (in_lds) {
-                const int i0 = __mul24(j * 2 + 0, n_bins) + rel;
+                const int i0 = __mul24(j * 2 + qn, n_bins) + rel;
                 lds_add(&my_acc[i0], d0); lds_add(&my_acc[i0 - 2 * n_bins], d1); lds_add(&my_acc[i0 - 4 * n_bins], d2);
             } else {
-                const int64_t i0 = ((int64_t)bin * 2 + 0) * NL + j;
+                const int64_t i0 = ((int64_t)bin * 2 + qn) * NL + j;
                 glb_add(&g_out[i0], d0); glb_add(&g_out[i0 - 1], d1); glb_add(&g_out[i0 - 2], d2);
             }
         };
-        auto add31 = [&](int j, unsigned long long d0, unsigned long long d1, unsigned long long d2) {
-            if (in_lds) {
-                const int i0 = __mul24(j * 2 + 1, n_bins) + rel;
-                lds_add(&my_acc[i0], d0); lds_add(&my_acc[i0 - 2 * n_bins], d1); lds_add(&my_acc[i0 - 4 * n_bins], d2);
-            } else {
-                const int64_t i0 = ((int64_t)bin * 2 + 1) * NL + j;
-                glb_add(&g_out[i0], d0); glb_add(&g_out[i0 - 1], d1); glb_add(&g_out[i0 - 2], d2);
-            }
-        };
+        auto add30 = [&](int j, unsigned long long d0, unsigned long long d1, unsigned long long d2) { put3(0, j, d0, d1, d2); };
+        auto add31 = [&](int j, unsigned long long d0, unsigned long long d1, unsigned long long d2) { put3(1, j, d0, d1, d2); };
 #ifdef PISA_DEV_PROBES
         if (a.opts & 2) {  // probe: keep the loads and the weight chain alive, no atomics
             if (w == 1.2345e-300 || w2 == 1.2345e-300) bad = true;
@@ -421,26 +457,10 @@ hist_accumulate_kernel(const HistArgs a, unsigned long long *__restrict__ g_limb
         if (!(a.opts & 1)) ok = deposit_units(w2, add31, add1) && ok;
         if (!ok) bad = true;
     };
-
-    // slab accumulators -> integer units, added to the global limbs.  The loop runs in
-    // GLOBAL order (limb fastest): a wave's 64 atomics fall into 512 contiguous bytes,
-    // which the L2 atomic units take at full rate (scattered 96 B apart they do not).
-    // Workgroups of a container finish together; each starts at a different offset so
-    // that they do not all queue on the same limbs at the same moment.
     auto flush_win = [&](const unsigned long long *win, int lo, int ncopies) {
-        const int rot = (int)((lb * 7 * 64) % n_acc);
-        for (int g0 = threadIdx.x; g0 < n_acc; g0 += nthreads) {
-            int g = g0 + rot;
-            if (g >= n_acc) g -= n_acc;
-            const int bin = g / (2 * NL);
-            const int rem = g - bin * 2 * NL;
-            const int q = rem / NL;
-            const int j = rem - q * NL;
-            const int k = (j * 2 + q) * n_bins + bin;
-            unsigned long long v = win[k];
-            for (int r = 1; r < ncopies; r++) v += win[r * n_acc + k];  // integer: exact
-            if (v != 0ull && lo + bin < (int)a.n_bins) atomicAdd(&g_out[(int64_t)lo * 2 * NL + g], v);
-        }
+        flush_window(win, ncopies, n_bins, n_acc, flush_rotation(lb, n_acc), nthreads, [&](int g, int bin, unsigned long long v) {
+            if (lo + bin < (int)a.n_bins) atomicAdd(&g_out[(int64_t)lo * 2 * NL + g], v);   // (a window may reach beyond the last bin)
+        });
     };
     // partitioned order: the other LDS window (see the QUAD sweep) and the first bin of what it holds
     int other_lo = -1;
@@ -505,7 +525,7 @@ hist_accumulate_kernel(const HistArgs a, unsigned long long *__restrict__ g_limb
                 qhave = q < q_stop;
             }
         }
-        const int64_t q_end = q_stop;   // (shadows the chunk's end inside the sweep below)
+        const int64_t q_lim = q_stop;   // (this partition's end)
         // The pair loop's software pipeline (see below), two half-sweeps per quad: while
         // events 0,1 of the quad are consumed the flux of events 2,3 is in flight, while 2,3
         // are consumed the next quad's indices and the flux of its events 0,1.
@@ -519,8 +539,8 @@ hist_accumulate_kernel(const HistArgs a, unsigned long long *__restrict__ g_limb
                 const double2 g2 = gq[128], g3 = gq[192];
                 if (n0 == 0xffffu) p0 = zero2;
                 if (n1 == 0xffffu) p1 = zero2;
-                double w0 = ((g0.x * p0.x) + (g0.y * p0.y)) * scale;
-                double w1 = ((g1.x * p1.x) + (g1.y * p1.y)) * scale;
+                double w0 = weight_compact(g0.x, g0.y, p0.x, p0.y, scale);
+                double w1 = weight_compact(g1.x, g1.y, p1.x, p1.y, scale);
                 if (b0 == 0xffffu) w0 = 0.0;
                 if (b1 == 0xffffu) w1 = 0.0;
                 accumulate(b0 == 0xffffu ? 0 : (int)b0, w0, w0 * w0);
@@ -532,13 +552,13 @@ hist_accumulate_kernel(const HistArgs a, unsigned long long *__restrict__ g_limb
             double2 p2 = tab[n2 == 0xffffu ? 0 : n2];
             double2 p3 = tab[n3 == 0xffffu ? 0 : n3];
             int64_t qn = q + qstep;
-            bool have_n = qn < q_end;
+            bool have_n = qn < q_lim;
             if (dep) {   // (wave-uniform) the next listed block, and the number of the one after it
                 // (the lanes of a wavefront leave the sweep one by one in its last block only: `o` is the same in
                 // all that are here, which the compiler cannot see across the loops)
                 const int o_next = __builtin_amdgcn_readfirstlane(o + o_step), last = n_dep - 1;
                 qn = (int64_t)blk_next * 64 + (threadIdx.x & 63);
-                have_n = o_next < n_dep && qn < q_end;
+                have_n = o_next < n_dep && qn < q_lim;
                 blk_next = dep[o_next + o_step < last ? o_next + o_step : last];
                 o = o_next;
             }
@@ -548,8 +568,8 @@ hist_accumulate_kernel(const HistArgs a, unsigned long long *__restrict__ g_limb
             const double2 g0n = gn[0], g1n = gn[64];
             if (n2 == 0xffffu) p2 = zero2;
             if (n3 == 0xffffu) p3 = zero2;
-            double w2 = ((g0.x * p2.x) + (g0.y * p2.y)) * scale;
-            double w3 = ((g1.x * p3.x) + (g1.y * p3.y)) * scale;
+            double w2 = weight_compact(g0.x, g0.y, p2.x, p2.y, scale);
+            double w3 = weight_compact(g1.x, g1.y, p3.x, p3.y, scale);
             if (b2 == 0xffffu) w2 = 0.0;
             if (b3 == 0xffffu) w3 = 0.0;
             accumulate(b2 == 0xffffu ? 0 : (int)b2, w2, w2 * w2);
@@ -604,13 +624,11 @@ hist_accumulate_kernel(const HistArgs a, unsigned long long *__restrict__ g_limb
             // below the prefetch and wait for all of it
             double wa, wb;
             if (COMPACT) {
-                wa = ((awa.x * pa.x) + (awa.y * pa.y)) * scale;
-                wb = ((awb.x * pb.x) + (awb.y * pb.y)) * scale;
+                wa = weight_compact(awa.x, awa.y, pa.x, pa.y, scale);
+                wb = weight_compact(awb.x, awb.y, pb.x, pb.y, scale);
             } else {
-                wa = awa.y * ((fa.x * pa.x) + (fa.y * pa.y));  // prob3.py:622
-                wa = wa * (awa.x * scale);                     // aeff.py:87
-                wb = awb.y * ((fb.x * pb.x) + (fb.y * pb.y));
-                wb = wb * (awb.x * scale);
+                wa = weight_reference(awa.y, fa.x, fa.y, pa.x, pa.y, awa.x, scale);
+                wb = weight_reference(awb.y, fb.x, fb.y, pb.x, pb.y, awb.x, scale);
             }
             if (ix.y < 0) wa = 0.0;
             if (ix.w < 0) wb = 0.0;
@@ -628,11 +646,10 @@ hist_accumulate_kernel(const HistArgs a, unsigned long long *__restrict__ g_limb
                 double2 x = aw[i];
                 double w;
                 if (COMPACT) {
-                    w = ((x.x * pp.x) + (x.y * pp.y)) * scale;
+                    w = weight_compact(x.x, x.y, pp.x, pp.y, scale);
                 } else {
                     double2 f = flux2[i];
-                    w = x.y * ((f.x * pp.x) + (f.y * pp.y));
-                    w = w * (x.x * scale);
+                    w = weight_reference(x.y, f.x, f.y, pp.x, pp.y, x.x, scale);
                 }
                 accumulate(ix1.y, w, w * w);
             }
@@ -647,23 +664,21 @@ hist_accumulate_kernel(const HistArgs a, unsigned long long *__restrict__ g_limb
         const double2 *aeff2 = reinterpret_cast<const double2 *>(C.aeff);
         const double2 *w02 = reinterpret_cast<const double2 *>(C.w0);
         const double2 *flux2 = reinterpret_cast<const double2 *>(C.flux);
-        for (int64_t p = p0 + threadIdx.x; p < p1; p += nthreads) {
-            const int2 nd = node2[p];
-            const int2 bn = bin2[p];
-            const double2 ae = aeff2[p];
-            const double2 w0 = w02[p];
-            const double2 fa = flux2[2 * p], fb = flux2[2 * p + 1];
+        for (int64_t i = p0 + threadIdx.x; i < p1; i += nthreads) {
+            const int2 nd = node2[i];
+            const int2 bn = bin2[i];
+            const double2 ae = aeff2[i];
+            const double2 w0 = w02[i];
+            const double2 f0 = flux2[2 * i], f1 = flux2[2 * i + 1];
             double2 pa = make_double2(0.0, 0.0), pb = make_double2(0.0, 0.0);
             if (nd.x >= 0) pa = tab[nd.x];
             if (nd.y >= 0) pb = tab[nd.y];
             if (bn.x >= 0) {
-                double w = w0.x * ((fa.x * pa.x) + (fa.y * pa.y));  // prob3.py:622
-                w = w * (ae.x * scale);                             // aeff.py:87
+                const double w = weight_reference(w0.x, f0.x, f0.y, pa.x, pa.y, ae.x, scale);
                 accumulate(bn.x, w, w * w);
             }
             if (bn.y >= 0) {
-                double w = w0.y * ((fb.x * pb.x) + (fb.y * pb.y));
-                w = w * (ae.y * scale);
+                const double w = weight_reference(w0.y, f1.x, f1.y, pb.x, pb.y, ae.y, scale);
                 accumulate(bn.y, w, w * w);
             }
         }
@@ -673,8 +688,7 @@ hist_accumulate_kernel(const HistArgs a, unsigned long long *__restrict__ g_limb
             if (bn >= 0) {
                 double2 pp = nd >= 0 ? tab[nd] : make_double2(0.0, 0.0);
                 double2 f = flux2[i];
-                double w = C.w0[i] * ((f.x * pp.x) + (f.y * pp.y));
-                w = w * (C.aeff[i] * scale);
+                const double w = weight_reference(C.w0[i], f.x, f.y, pp.x, pp.y, C.aeff[i], scale);
                 accumulate(bn, w, w * w);
             }
         }
@@ -737,16 +751,16 @@ hist_accumulate_kernel(const HistArgs a, unsigned long long *__restrict__ g_limb
                 const double2 *__restrict__ z2 = reinterpret_cast<const double2 *>(C.s[2]);
                 const double2 zero = make_double2(0.0, 0.0);
                 const int64_t n_wg1 = a.blk_start[c + 1] - a.blk_start[c];
-                for (int64_t q = lb * nthreads + threadIdx.x; q < (C.n >> 1); q += n_wg1 * nthreads) {
-                    const double2 gx = gx2[q];
-                    const double2 gy = g2 ? gy2[q] : zero;
-                    const double2 fa = flux2[2 * q], fb = flux2[2 * q + 1];
-                    const double2 w0 = w02[q], ae = ae2[q];
-                    const double2 x = x2[q];
-                    const double2 y = OD > 1 ? y2[q] : zero;
-                    const double2 z = OD > 2 ? z2[q] : zero;
-                    event(gx.x, gy.x, fa, w0.x, ae.x, x.x, y.x, z.x);
-                    event(gx.y, gy.y, fb, w0.y, ae.y, x.y, y.y, z.y);
+                for (int64_t i = lb * nthreads + threadIdx.x; i < (C.n >> 1); i += n_wg1 * nthreads) {
+                    const double2 gx = gx2[i];
+                    const double2 gy = g2 ? gy2[i] : zero;
+                    const double2 f0 = flux2[2 * i], f1 = flux2[2 * i + 1];
+                    const double2 w0 = w02[i], ae = ae2[i];
+                    const double2 x = x2[i];
+                    const double2 y = OD > 1 ? y2[i] : zero;
+                    const double2 z = OD > 2 ? z2[i] : zero;
+                    event(gx.x, gy.x, f0, w0.x, ae.x, x.x, y.x, z.x);
+                    event(gx.y, gy.y, f1, w0.y, ae.y, x.y, y.y, z.y);
                 }
                 if ((C.n & 1) && lb == 0 && threadIdx.x == 0) {  // odd tail of the container
                     const int64_t i = C.n - 1;
@@ -777,11 +791,11 @@ hist_accumulate_kernel(const HistArgs a, unsigned long long *__restrict__ g_limb
                 const double2 *__restrict__ z2 = reinterpret_cast<const double2 *>(C.s[2]);
                 const double2 zero = make_double2(0.0, 0.0), one = make_double2(1.0, 1.0);
                 const int64_t n_wg1 = a.blk_start[c + 1] - a.blk_start[c];
-                for (int64_t q = lb * nthreads + threadIdx.x; q < (C.n >> 1); q += n_wg1 * nthreads) {
-                    const double2 w = weighted ? w2[q] : one;
-                    const double2 x = x2[q];
-                    const double2 y = OD > 1 ? y2[q] : zero;
-                    const double2 z = OD > 2 ? z2[q] : zero;
+                for (int64_t i = lb * nthreads + threadIdx.x; i < (C.n >> 1); i += n_wg1 * nthreads) {
+                    const double2 w = weighted ? w2[i] : one;
+                    const double2 x = x2[i];
+                    const double2 y = OD > 1 ? y2[i] : zero;
+                    const double2 z = OD > 2 ? z2[i] : zero;
                     event(w.x, x.x, y.x, z.x);
                     event(w.y, x.y, y.y, z.y);
                 }
@@ -930,24 +944,18 @@ hist_accumulate_multi_kernel(const MultiArgs a, unsigned long long *__restrict__
                         // outside the calc grid: P = 0; the products are still formed, as in the single-point
                         // kernel (a non-finite flux is flagged there too)
                         const double2 pk = node != 0xffffu ? p[k] : zero2;
-                        const double w = ((g[e].x * pk.x) + (g[e].y * pk.y)) * sc[k];
+                        const double w = weight_compact(g[e].x, g[e].y, pk.x, pk.y, sc[k]);
                         unsigned long long *acc = s_units + k * n_acc + (int)bin;
-                        auto add0 = [&](int j, long long d) { atomicAdd(&acc[(j * 2 + 0) * n_bins], (unsigned long long)d); };
-                        auto add1 = [&](int j, long long d) { atomicAdd(&acc[(j * 2 + 1) * n_bins], (unsigned long long)d); };
-                        auto add30 = [&](int j, unsigned long long d0, unsigned long long d1, unsigned long long d2) {
-                            unsigned long long *t0 = acc + __mul24(j * 2 + 0, n_bins);
-                            atomicAdd(t0, d0);
-                            atomicAdd(t0 - 2 * n_bins, d1);
-                            atomicAdd(t0 - 4 * n_bins, d2);
+                        // (the digits of both quantities: LDS only, addressed from the bin's accumulator of slab 0)
+                        auto add = [&](int qn, int j, long long d) { lds_add(&acc[(j * 2 + qn) * n_bins], (unsigned long long)d); };
+                        auto add3 = [&](int qn, int j, unsigned long long d0, unsigned long long d1, unsigned long long d2) {
+                            unsigned long long *t0 = acc + __mul24(j * 2 + qn, n_bins);
+                            lds_add(t0, d0); lds_add(t0 - 2 * n_bins, d1); lds_add(t0 - 4 * n_bins, d2);
                         };
-                        auto add31 = [&](int j, unsigned long long d0, unsigned long long d1, unsigned long long d2) {
-                            unsigned long long *t0 = acc + __mul24(j * 2 + 1, n_bins);
-                            atomicAdd(t0, d0);
-                            atomicAdd(t0 - 2 * n_bins, d1);
-                            atomicAdd(t0 - 4 * n_bins, d2);
-                        };
-                        bool ok = deposit_units(w, add30, add0);
-                        ok = deposit_units(w * w, add31, add1) && ok;
+                        bool ok = deposit_units(w, [&](int j, unsigned long long d0, unsigned long long d1, unsigned long long d2) { add3(0, j, d0, d1, d2); },
+                                                [&](int j, long long d) { add(0, j, d); });
+                        ok = deposit_units(w * w, [&](int j, unsigned long long d0, unsigned long long d1, unsigned long long d2) { add3(1, j, d0, d1, d2); },
+                                           [&](int j, long long d) { add(1, j, d); }) && ok;
                         if (!ok) bad = true;
                     }
                 }
@@ -966,24 +974,13 @@ hist_accumulate_multi_kernel(const MultiArgs a, unsigned long long *__restrict__
     }
     if (bad && status) atomicOr(status, 1);
     __syncthreads();
-    // slab accumulators -> integer units, added to the points' global limbs (global order, rotated
-    // start: see hist_accumulate_kernel)
-    const int rot = (int)((lb * 7 * 64) % n_acc);
+    // slab accumulators -> integer units, added to the points' global limbs (flush_window)
+    const int rot = flush_rotation(lb, n_acc);
 #pragma unroll 1
     for (int k = 0; k < KP; k++) {
-        unsigned long long *g_out = g_limbs + (int64_t)k * a.limb_stride +
-                                    (int64_t)(a.cont_base + c) * n_bins * 2 * NL;
-        const unsigned long long *acc = s_units + k * n_acc;
-        for (int g0 = threadIdx.x; g0 < n_acc; g0 += nthreads) {
-            int gi = g0 + rot;
-            if (gi >= n_acc) gi -= n_acc;
-            const int bin = gi / (2 * NL);
-            const int rem = gi - bin * 2 * NL;
-            const int qq = rem / NL;
-            const int j = rem - qq * NL;
-            const unsigned long long v = acc[(j * 2 + qq) * n_bins + bin];
-            if (v != 0ull) atomicAdd(&g_out[gi], v);
-        }
+        unsigned long long *g_out = g_limbs + (int64_t)k * a.limb_stride + (int64_t)(a.cont_base + c) * n_bins * 2 * NL;
+        flush_window(s_units + k * n_acc, 1, n_bins, n_acc, rot, nthreads,
+                     [&](int g, int, unsigned long long v) { atomicAdd(&g_out[g], v); });
     }
 }
 
@@ -1361,6 +1358,25 @@ static int hist_threads() {
 // hist launch (bench.py measures the dominant kernel with them)
 static thread_local hipEvent_t g_prof_start = nullptr, g_prof_stop = nullptr;
 
+// The instantiations of hist_accumulate_kernel: (mode, dimensions of the calc grid, of the output binning) -> kernel with
+// LDS accumulators, kernel without (none: modes 3, 5 and 7 always have all bins or a window of them in LDS, run_hist).
+typedef void (*hist_kernel_t)(const HistArgs, unsigned long long *, int32_t *);
+static const struct HistForm { int mode, gd, od; hist_kernel_t lds, no_lds; } hist_forms[] = {
+    {7, 0, 0, hist_accumulate_kernel<7, true>, nullptr},
+    {5, 0, 0, hist_accumulate_kernel<5, true>, nullptr},
+    {3, 0, 0, hist_accumulate_kernel<3, true>, nullptr},
+    {2, 0, 0, hist_accumulate_kernel<2, true>, hist_accumulate_kernel<2, false>},
+    {1, 1, 1, hist_accumulate_kernel<1, true, 4 * 1 + 1>, hist_accumulate_kernel<1, false, 4 * 1 + 1>},
+    {1, 1, 2, hist_accumulate_kernel<1, true, 4 * 1 + 2>, hist_accumulate_kernel<1, false, 4 * 1 + 2>},
+    {1, 1, 3, hist_accumulate_kernel<1, true, 4 * 1 + 3>, hist_accumulate_kernel<1, false, 4 * 1 + 3>},
+    {1, 2, 1, hist_accumulate_kernel<1, true, 4 * 2 + 1>, hist_accumulate_kernel<1, false, 4 * 2 + 1>},
+    {1, 2, 2, hist_accumulate_kernel<1, true, 4 * 2 + 2>, hist_accumulate_kernel<1, false, 4 * 2 + 2>},
+    {1, 2, 3, hist_accumulate_kernel<1, true, 4 * 2 + 3>, hist_accumulate_kernel<1, false, 4 * 2 + 3>},
+    {0, 0, 1, hist_accumulate_kernel<0, true, 1>, hist_accumulate_kernel<0, false, 1>},
+    {0, 0, 2, hist_accumulate_kernel<0, true, 2>, hist_accumulate_kernel<0, false, 2>},
+    {0, 0, 3, hist_accumulate_kernel<0, true, 3>, hist_accumulate_kernel<0, false, 3>},
+};
+
 static int run_hist(const ContDev *conts, int n_cont, int mode, const DevBinning *grid,
                     int64_t n_nodes, const double *prob_nu, const double *prob_nubar,
                     const double *pepmu, const DevBinning &outb, int64_t n_bins,
@@ -1461,31 +1477,14 @@ static int run_hist(const ContDev *conts, int n_cont, int mode, const DevBinning
         }
         unsigned long long *out = reinterpret_cast<unsigned long long *>(d_limbs);
         if (g_prof_start) PISA_TRY_HIP(hipEventRecord(g_prof_start, s));
-#define LAUNCH(M, L) hipLaunchKernelGGL((hist_accumulate_kernel<M, L>), grid_dim, block, shmem, s, a, out, d_status)
-        if (mode == 7) LAUNCH(7, true);
-        else if (mode == 5) LAUNCH(5, true);    // (modes 3, 5 and 7: all bins or a window of them in LDS, see above)
-        else if (mode == 3) LAUNCH(3, true);
-        else if (mode == 2) { if (lds) LAUNCH(2, true); else LAUNCH(2, false); }
-        else if (mode == 1) {
-            // dimensions as template parameters (uniform branches around the loads and 64-bit index
-            // arithmetic otherwise: 1 080 instructions per pair of events)
-            const int gd = a.grid.ndim, od = a.outb.ndim;
-            if (gd < 1 || gd > 2 || od < 1 || od > 3 || n_nodes >= (1LL << 31) / 9) return PISA_HIP_ERR_INVALID;
-#define LAUNCH1(G, O) do { if (lds) hipLaunchKernelGGL((hist_accumulate_kernel<1, true, 4 * G + O>), grid_dim, block, shmem, s, a, out, d_status); \
-                           else hipLaunchKernelGGL((hist_accumulate_kernel<1, false, 4 * G + O>), grid_dim, block, shmem, s, a, out, d_status); } while (0)
-            if (gd == 1) { if (od == 1) LAUNCH1(1, 1); else if (od == 2) LAUNCH1(1, 2); else LAUNCH1(1, 3); }
-            else { if (od == 1) LAUNCH1(2, 1); else if (od == 2) LAUNCH1(2, 2); else LAUNCH1(2, 3); }
-#undef LAUNCH1
-        }
-        else {
-            const int od = a.outb.ndim;
-            if (od < 1 || od > 3) return PISA_HIP_ERR_INVALID;
-#define LAUNCH0(O) do { if (lds) hipLaunchKernelGGL((hist_accumulate_kernel<0, true, O>), grid_dim, block, shmem, s, a, out, d_status); \
-                        else hipLaunchKernelGGL((hist_accumulate_kernel<0, false, O>), grid_dim, block, shmem, s, a, out, d_status); } while (0)
-            if (od == 1) LAUNCH0(1); else if (od == 2) LAUNCH0(2); else LAUNCH0(3);
-#undef LAUNCH0
-        }
-#undef LAUNCH
+        // (dimensions as template parameters: uniform branches and 64-bit index arithmetic otherwise, 1 080 instructions per pair)
+        const int form = mode == 7 || mode == 5 || mode == 3 || mode == 2 || mode == 1 ? mode : 0;
+        const int gd = form == 1 ? a.grid.ndim : 0, od = form <= 1 ? a.outb.ndim : 0;
+        if (form == 1 && (gd < 1 || gd > 2 || od < 1 || od > 3 || n_nodes >= (1LL << 31) / 9)) return PISA_HIP_ERR_INVALID;
+        if (form == 0 && (od < 1 || od > 3)) return PISA_HIP_ERR_INVALID;
+        for (const HistForm &f : hist_forms)
+            if (f.mode == form && f.gd == gd && f.od == od)
+                hipLaunchKernelGGL(lds || !f.no_lds ? f.lds : f.no_lds, grid_dim, block, shmem, s, a, out, d_status);
         PISA_CHECK_LAUNCH("hist_accumulate_kernel");
         if (g_prof_stop) PISA_TRY_HIP(hipEventRecord(g_prof_stop, s));
     }
