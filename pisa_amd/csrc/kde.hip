@@ -47,18 +47,20 @@
 #include <string.h>
 
 #include <algorithm>
+#include <memory>
+#include <type_traits>
 #include <vector>
 
 #include <hipcub/hipcub.hpp>
 #include <rocprim/rocprim.hpp>
 
 #include "common.hpp"
+#include "kde_plan.hpp"
 
 namespace pisa {
 
 // ------------------------------------------------------------------ all pairs (exact) form
-constexpr int KDE_TILE = 1024;
-constexpr int KDE_THREADS = 256;
+// (the constants and the structs the kernels take by value: kde_plan.hpp)
 
 template <int D>
 __global__ void __launch_bounds__(KDE_THREADS)
@@ -151,33 +153,6 @@ static int kde_scratch(size_t bytes, hipStream_t s, double **out) {
 }
 
 // =================================================================== estimator object
-constexpr int RED_BLOCKS = 256;   // fixed reduction geometry => fixed summation order
-constexpr int RED_THREADS = 256;
-constexpr int Q_PER_THREAD = 2;
-constexpr int Q_CHUNK = KDE_THREADS * Q_PER_THREAD;   // queries per workgroup
-constexpr int SRC_TILE = 512;                          // sources per LDS tile
-constexpr int64_t KEY_OFF = 1 << 20;                   // tile coordinates are stored + 2^20
-constexpr int MAX_CELLS = 1 << 22;
-// the cell grid never has more than max(4096, 4 n) cells (larger cells beyond that: less pruning,
-// same results), so that the workspace scales with the number of sources
-static inline int64_t cells_cap(int64_t n) { return std::min<int64_t>(MAX_CELLS, std::max<int64_t>(4096, 4 * n)); }
-
-struct KdeGeom {
-    int32_t dim;
-    int32_t nc[3];       // cells per dimension (1 for unused dimensions)
-    double ylo[3];       // lower corner of the cell grid in whitened coordinates
-    double cell, inv_cell;
-    double rcut2;        // 2 ln(1/tol); <= 0: no cut-off
-    double U[9];         // whitening: y = U (x - mean), upper triangular, row-major 3x3
-    double mean[3];
-};
-
-struct KdeBlock {        // one workgroup of the pair kernel
-    int32_t q_begin, q_count;
-    int32_t c0[3], c1[3];   // cell bounds of the queries' tile (inclusive; may lie outside the grid)
-    int32_t head;           // index of the tile among the non-empty tiles (sorted order)
-};
-
 __device__ inline double block_sum(double v, double *lds) {
     const int t = threadIdx.x;
     __syncthreads();
@@ -599,13 +574,6 @@ kde_combine_kernel(const double *__restrict__ partial, int n_split, int64_t n,
 // to a few hundred, < 3e-13 relative for R = 32.  A strip is skipped for a source only if every
 // one of its points is beyond the cut-off, so the stated tolerance holds.  Fixed order (sources
 // in sorted order inside a share, shares added in order): bit-reproducible.
-struct KdeLattice {
-    double ya0, yb0;   // whitened coordinates of lattice point (0, 0)
-    double da;         // y_a step of index 0 (> 0)
-    double sa, db;     // (y_a, y_b) step of index 1
-    int32_t n0, n1, strips_a;   // strips_a = ceil(n0 / R)
-    int32_t sw, lpw, n_colblk;  // a wavefront's sub-patch: sw strips of lpw consecutive lines (sw lpw = LG lanes, 64 / LG lane groups); column blocks per line
-};
 
 // up = h exp(t), dn = h exp(-t), |t| <= 700: one range reduction and the even / odd halves of the same
 // degree-13 polynomial serve both (exp(+-r) = C(r^2) +- r S(r^2))
@@ -643,11 +611,9 @@ __device__ inline void exp_pair(double t, double h, double &up, double &dn) {
 // In GLOBAL memory a record is its first eight numbers only (LAT_GREC, 64 B; round 6): the Q table is rebuilt in LDS when a
 // piece is staged, Q_k = Q_{k-1} h^(2 (k - 1)) -- two multiplications per entry by one lane per record.  A record is fetched
 // ~11 times per launch (once per sub-patch and lane group within its reach): 0.9 GB per estimator at 192 B, a quarter of it now.
-constexpr int LAT_GREC = 8;
 constexpr int LAT_REC = 24;
 constexpr int LAT_Q0 = 8;
 constexpr int LAT_QMAX = 16;
-constexpr int LAT_SHARE = 64;   // sources per share (= the workgroup of kde_lattice_prep_kernel, which writes the share's box)
 __global__ void __launch_bounds__(64)
 kde_lattice_prep_kernel(const double *__restrict__ ys, const double *__restrict__ coef,
                         const double *__restrict__ s2, int64_t n, double da, double rcut2, double *__restrict__ rec,
@@ -1169,12 +1135,6 @@ kde_cell_s2min_kernel(const double *__restrict__ s2, const int32_t *__restrict__
 // at or below the cut-off tolerance.  A target then costs P^2 + 4 P + 40 multiply-adds per dense
 // cell within the cut-off instead of 23 per SOURCE: N * 250 cells * 500 instead of N * 0.2 N * 23
 // (x 90 at N = 4e5).  Without local expansions, cells with fewer than HERMITE_MIN_SERIES sources are summed directly.
-constexpr int HERMITE_MIN_DEFAULT = 1;   // with local expansions (see pisa_hip_kde_create)
-constexpr int HERMITE_MIN_SERIES = 24;   // series evaluated per target
-static int hermite_min() {
-    static const int v = [] { const int x = PISA_DEV_INT("KDE_HERMITE_MIN", 0); return x > 0 ? x : HERMITE_MIN_DEFAULT; }();
-    return v;
-}
 constexpr double RSQRT2 = 0.70710678118654752440;
 
 __global__ void __launch_bounds__(256)
@@ -1476,7 +1436,6 @@ kde_hermite_pilot_kernel(KdeGeom g, const KdeBlock *__restrict__ blocks, const d
 // and multiplied by H(d1) once per column: (cells + columns) P^3 multiply-adds per target cell.
 // Truncation at k, l < P costs the same (rho sqrt2)^P / sqrt(P!) as the Hermite series.  The Hankel
 // entries h_n(j * cell / sqrt2), n < 2P - 1, |j| <= reach, come from the host (long double recurrence).
-constexpr int H2L_MAX_REACH = 12;
 
 // The translation is done in two separable passes over the cell grid (like a separable
 // convolution), with the SQUARE |d1|, |d2| <= reach of source cells instead of the disc -- the cells
@@ -1992,6 +1951,7 @@ kde_local_pilot_wave_kernel(KdeGeom g, const KdeBlock *__restrict__ blocks, cons
 }
 
 // ------------------------------------------------------------------ host side
+// What is decided here is decided in kde_plan.hpp; this part owns the workspace, the launches and their order.
 struct Arena {   // carves the caller's workspace
     char *base;
     size_t size, used;
@@ -2026,6 +1986,48 @@ static size_t sort_temp_bytes(int64_t n) {
     return std::max(bytes, b2) + 256;
 }
 
+// f(std::integral_constant<int, V>) for the V of Vs... that equals v: the dispatch on a template argument (the
+// dimension, the series order, the lattice's strip length and lane-group width)
+template <int... Vs, class F>
+static inline void dispatch(int v, F &&f) {
+    (void)((v == Vs ? (f(std::integral_constant<int, Vs>{}), true) : false) || ...);
+}
+
+// ---- development probes (constants in the product library, see common.hpp)
+static int hermite_min() {
+    static const int v = [] { const int x = PISA_DEV_INT("KDE_HERMITE_MIN", 0); return x > 0 ? x : HERMITE_MIN_DEFAULT; }();
+    return v;
+}
+
+// marginal cost of a phase = wall time with it run twice.  `bit`: 1 lattice kernel, 2 pilot expansion, 4 sort
+static int probe_repeats(int bit) {
+    static const int twice = PISA_DEV_INT("KDE_TWICE", 0);
+    return (twice & bit) ? 2 : 1;
+}
+
+#ifdef PISA_DEV_PROBES
+// per-wavefront stamps, 32 bytes each: zeroed device memory where `path` is set, then written to the file
+static int stamps_begin(const char *path, size_t n, hipStream_t s, unsigned long long **stamps) {
+    if (!path) return PISA_HIP_OK;
+    PISA_TRY_HIP(hipMalloc((void **)stamps, n * 32));
+    PISA_TRY_HIP(hipMemsetAsync(*stamps, 0, n * 32, s));
+    return PISA_HIP_OK;
+}
+
+static int stamps_dump(unsigned long long *stamps, size_t n, const char *path, const char *mode, const long long *hdr4) {
+    if (!stamps) return PISA_HIP_OK;
+    std::vector<unsigned long long> h(n * 4);
+    PISA_TRY_HIP(hipMemcpy(h.data(), stamps, h.size() * 8, hipMemcpyDeviceToHost));
+    (void)hipFree(stamps);
+    if (FILE *f = fopen(path, mode)) {
+        if (hdr4) fwrite(hdr4, 8, 4, f);
+        fwrite(h.data(), 8, h.size(), f);
+        fclose(f);
+    }
+    return PISA_HIP_OK;
+}
+#endif
+
 }  // namespace pisa
 
 using namespace pisa;
@@ -2052,49 +2054,30 @@ struct pisa_hip_kde {
 
 namespace pisa {
 
+struct KdeFree { void operator()(pisa_hip_kde *k) const { free(k); } };
+
+// the workgroups of sorted queries: a tile's queries (equal keys) in equal shares of `chunk` at most
 static int query_blocks(const uint64_t *d_keys, int64_t m, int tile, int chunk, char *d_temp, size_t temp_bytes,
                         uint8_t *d_flags, int32_t *d_starts, int32_t *d_count, uint64_t *d_head_keys,
-                        std::vector<KdeBlock> &blocks, hipStream_t s,
-                        std::vector<int32_t> *starts_out = nullptr, std::vector<uint64_t> *keys_out = nullptr,
-                        int64_t max_heads = 0) {
+                        std::vector<KdeBlock> &blocks, hipStream_t s) {
     hipLaunchKernelGGL(kde_heads_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, d_keys, m, d_flags);
     PISA_CHECK_LAUNCH("kde_heads_kernel");
     PISA_TRY_HIP(hipcub::DeviceSelect::Flagged(d_temp, temp_bytes, hipcub::CountingInputIterator<int32_t>(0),
                                                d_flags, d_starts, d_count, (int)m, s));
     int32_t n_heads = 0;
-    std::vector<int32_t> starts;
-    std::vector<uint64_t> hk;
     PISA_TRY_HIP(hipMemcpyAsync(&n_heads, d_count, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    if (max_heads > 0 && max_heads <= 65536) {
-        // the caller bounds the number of tiles (cells of the grid): the kernel takes the count from the
-        // device and everything comes back behind ONE synchronisation
-        const int64_t cap = std::min<int64_t>(max_heads, m);
-        hipLaunchKernelGGL(kde_head_keys_kernel, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, s,
-                           d_keys, d_starts, d_count, d_head_keys);
-        PISA_CHECK_LAUNCH("kde_head_keys_kernel");
-        starts.resize(cap);
-        hk.resize(cap);
-        PISA_TRY_HIP(hipMemcpyAsync(starts.data(), d_starts, cap * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        PISA_TRY_HIP(hipMemcpyAsync(hk.data(), d_head_keys, cap * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-        PISA_TRY_HIP(hipStreamSynchronize(s));
-        if (n_heads <= 0 || n_heads > cap) return PISA_HIP_ERR_INVALID;
-        starts.resize(n_heads);
-        hk.resize(n_heads);
-    } else {
-        PISA_TRY_HIP(hipStreamSynchronize(s));
-        if (n_heads <= 0) return PISA_HIP_ERR_INVALID;
-        hipLaunchKernelGGL(kde_head_keys_kernel, dim3((unsigned)((n_heads + 255) / 256)), dim3(256), 0, s,
-                           d_keys, d_starts, d_count, d_head_keys);
-        PISA_CHECK_LAUNCH("kde_head_keys_kernel");
-        starts.resize(n_heads);
-        hk.resize(n_heads);
-        PISA_TRY_HIP(hipMemcpyAsync(starts.data(), d_starts, n_heads * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        PISA_TRY_HIP(hipMemcpyAsync(hk.data(), d_head_keys, n_heads * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-        PISA_TRY_HIP(hipStreamSynchronize(s));
-    }
+    PISA_TRY_HIP(hipStreamSynchronize(s));
+    if (n_heads <= 0) return PISA_HIP_ERR_INVALID;
+    hipLaunchKernelGGL(kde_head_keys_kernel, dim3((unsigned)((n_heads + 255) / 256)), dim3(256), 0, s,
+                       d_keys, d_starts, d_count, d_head_keys);
+    PISA_CHECK_LAUNCH("kde_head_keys_kernel");
+    std::vector<int32_t> starts(n_heads);
+    std::vector<uint64_t> hk(n_heads);
+    PISA_TRY_HIP(hipMemcpyAsync(starts.data(), d_starts, n_heads * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    PISA_TRY_HIP(hipMemcpyAsync(hk.data(), d_head_keys, n_heads * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    PISA_TRY_HIP(hipStreamSynchronize(s));
     blocks.clear();
     for (int32_t h = 0; h < n_heads; h++) {
-        const int64_t begin = starts[h], end = h + 1 < n_heads ? starts[h + 1] : m;
         KdeBlock b;
         b.head = h;
         for (int d = 0; d < 3; d++) {
@@ -2102,17 +2085,8 @@ static int query_blocks(const uint64_t *d_keys, int64_t m, int tile, int chunk, 
             b.c0[d] = (int32_t)(t * tile);
             b.c1[d] = (int32_t)(t * tile + tile - 1);
         }
-        // equal shares: a tile of 300 queries becomes 150 + 150, not 256 + 44
-        const int64_t parts = (end - begin + chunk - 1) / chunk;
-        for (int64_t p = 0; p < parts; p++) {
-            const int64_t q0 = begin + (end - begin) * p / parts, q1 = begin + (end - begin) * (p + 1) / parts;
-            b.q_begin = (int32_t)q0;
-            b.q_count = (int32_t)(q1 - q0);
-            blocks.push_back(b);
-        }
+        split_evenly(starts[h], h + 1 < n_heads ? starts[h + 1] : m, chunk, b, blocks);
     }
-    if (starts_out) starts_out->swap(starts);
-    if (keys_out) keys_out->swap(hk);
     return PISA_HIP_OK;
 }
 
@@ -2120,44 +2094,323 @@ template <bool VAR_BW, int QPT>
 static int launch_pairs(const pisa_hip_kde *k, const KdeBlock *d_blocks, int n_blocks, int n_split,
                         const double *qy, int64_t m, double *partial, hipStream_t s) {
     dim3 grid((unsigned)n_blocks, (unsigned)n_split), block(KDE_THREADS);
-#define KDE_PAIRS(DD) hipLaunchKernelGGL((kde_pairs_kernel<DD, VAR_BW, QPT>), grid, block, 0, s, k->g, d_blocks, qy, m, k->ys, k->n, k->coef, k->s2, k->cell_start, k->cell_s2min, k->scalars + 1, n_split, partial, k->pair_count)
-    if (k->dim == 1) KDE_PAIRS(1);
-    else if (k->dim == 2) KDE_PAIRS(2);
-    else KDE_PAIRS(3);
-#undef KDE_PAIRS
+    dispatch<1, 2, 3>(k->dim, [&](auto D) {
+        hipLaunchKernelGGL((kde_pairs_kernel<decltype(D)::value, VAR_BW, QPT>), grid, block, 0, s, k->g, d_blocks, qy, m,
+                           k->ys, k->n, k->coef, k->s2, k->cell_start, k->cell_s2min, k->scalars + 1, n_split, partial,
+                           k->pair_count);
+    });
     PISA_CHECK_LAUNCH("kde_pairs_kernel");
     return PISA_HIP_OK;
 }
 
-static int pick_split(int n_blocks) {
-    int n_split = 1;
-    if (n_blocks < 1024) n_split = std::min(32, (1024 + n_blocks - 1) / n_blocks);
-    return n_split;
+// ---- create, step 1: sum w, mean and box of the sample (pass 1), sum w^2 and second moments about the mean (pass 2).
+// The per-workgroup partial results come back and are joined here, in kde_final_reduce_kernel's order: one launch
+// less per pass on a chain that is launch-latency bound for small samples.
+struct KdeMoments {
+    double sw, mean[3], xmin[3], xmax[3];
+    double h2[7];   // sum w^2, sum w xc_d xc_e (d <= e)
+};
+
+static int reduce_moments(int dim, const double *d_x, const double *d_w, int64_t n, double *partial, hipStream_t s,
+                          KdeMoments &mo) {
+    double h1[10], hp[RED_BLOCKS * 10];
+    dispatch<1, 2, 3>(dim, [&](auto D) {
+        hipLaunchKernelGGL(kde_moments1_kernel<decltype(D)::value>, dim3(RED_BLOCKS), dim3(RED_THREADS), 0, s, d_x, d_w, n, partial);
+    });
+    PISA_TRY_HIP(hipMemcpyAsync(hp, partial, (size_t)RED_BLOCKS * (1 + 3 * dim) * sizeof(double), hipMemcpyDeviceToHost, s));
+    PISA_TRY_HIP(hipStreamSynchronize(s));
+    final_reduce_host(hp, 1 + 3 * dim, 1 + dim, dim, h1);
+    mo = KdeMoments();
+    mo.sw = h1[0];
+    if (!(mo.sw > 0.0) || !std::isfinite(mo.sw)) return PISA_HIP_ERR_INVALID;
+    for (int d = 0; d < dim; d++) {
+        mo.mean[d] = h1[1 + d] / mo.sw;
+        mo.xmin[d] = h1[1 + dim + d];
+        mo.xmax[d] = h1[1 + 2 * dim + d];
+    }
+    dispatch<1, 2, 3>(dim, [&](auto D) {
+        hipLaunchKernelGGL(kde_moments2_kernel<decltype(D)::value>, dim3(RED_BLOCKS), dim3(RED_THREADS), 0, s, d_x, d_w, n,
+                           mo.mean[0], mo.mean[1], mo.mean[2], partial);
+    });
+    PISA_TRY_HIP(hipMemcpyAsync(hp, partial, (size_t)RED_BLOCKS * 7 * sizeof(double), hipMemcpyDeviceToHost, s));
+    PISA_TRY_HIP(hipStreamSynchronize(s));
+    final_reduce_host(hp, 7, 7, 0, mo.h2);
+    return PISA_HIP_OK;
 }
 
-// bytes of the create-time workspace that stay in use for the lifetime of the estimator
-static size_t resident_bytes(int dim, int64_t n, int64_t n_cells) {
-    auto r = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    return r((size_t)dim * n * 8) + 3 * r((size_t)n * 8) + r((size_t)(n_cells + 1) * 4) +
-           r((size_t)n_cells * 8) + r(64) + r(64);
+// ---- create, step 2: bandwidth matrix, whitening and cell grid (kde_plan.hpp) into the estimator
+static int plan_estimator(pisa_hip_kde *k, const KdeMoments &mo, int bw_method) {
+    KdeBandwidth bw;
+    k->sum_w = mo.sw;
+    for (int d = 0; d < 3; d++) k->mean[d] = mo.mean[d];
+    if (!bandwidth_matrix(mo.h2, mo.sw, k->n, k->dim, bw_method, bw)) return PISA_HIP_ERR_INVALID;
+    k->factor = bw.factor;
+    k->norm = bw.norm;
+    memcpy(k->cov, bw.cov, sizeof(k->cov));
+    memcpy(k->inv_cov, bw.inv_cov, sizeof(k->inv_cov));
+    if (!cell_grid(bw.U, k->mean, mo.xmin, mo.xmax, k->dim, k->tol, k->n, k->g, k->n_cells, k->r_cut))
+        return PISA_HIP_ERR_INVALID;
+    return PISA_HIP_OK;
+}
+
+// ---- create, step 3: the resident arrays; sources whitened, sorted by cell and gathered; the cell table
+static int sort_sources(pisa_hip_kde *k, const double *d_x, const double *d_w, Arena &ar, hipStream_t s) {
+    const int64_t n = k->n;
+    const int dim = k->dim;
+    const unsigned nb = (unsigned)((n + 255) / 256);
+    k->ys = ar.take<double>((size_t)dim * n);
+    k->wn = ar.take<double>(n);
+    k->coef = ar.take<double>(n);
+    k->s2 = ar.take<double>(n);
+    k->cell_start = ar.take<int32_t>(k->n_cells + 1);
+    k->cell_s2min = ar.take<double>(k->n_cells);
+    k->scalars = ar.take<double>(8);
+    k->pair_count = ar.take<unsigned long long>(8);
+    // transient
+    double *rec = ar.take<double>((size_t)4 * n);      // (y, weight) per source, 32 bytes
+    uint64_t *keys_a = ar.take<uint64_t>(n);
+    uint32_t *idx_a = ar.take<uint32_t>(n), *idx_b = ar.take<uint32_t>(n);
+    size_t temp_bytes = sort_temp_bytes(n);
+    char *temp = ar.take<char>(temp_bytes);
+    if (!ar.ok) return PISA_HIP_ERR_NOMEM;
+    PISA_TRY_HIP(hipMemsetAsync(k->pair_count, 0, 64, s));
+    uint32_t *flat_a = (uint32_t *)keys_a, *flat_b = flat_a + n;   // (the key arrays of the general form hold two 32-bit ones)
+    unsigned bits = 1;
+    while (bits < 32 && ((int64_t)1 << bits) < k->n_cells) bits++;
+    // cell and source index in one 32-bit word where both fit ((cell << pack) | index): the sort moves keys only -- half the
+    // bytes per pass --, sorted on the cell's bits; the order is the stable order of the pair sort (the indices ascend)
+    const int pack = (bits < 32 && n <= ((int64_t)1 << (32 - bits))) ? (int)(32 - bits) : 0;
+    dispatch<1, 2, 3>(dim, [&](auto D) {
+        hipLaunchKernelGGL(kde_whiten_flat_kernel<decltype(D)::value>, dim3(nb), dim3(256), 0, s, d_x, d_w, n, k->g, rec, flat_a, idx_a, pack);
+    });
+#ifdef PISA_DEV_PROBES
+    {   // development (EXPERIMENTS R6-7): N empty launches per estimator -- is the evaluation bound by the number of runtime calls?
+        static const int extra = PISA_DEV_INT("KDE_EXTRA_LAUNCHES", 0);
+        for (int e = 0; e < extra; e++) hipLaunchKernelGGL(kde_noop_kernel, dim3(1), dim3(64), 0, s, k->scalars);
+    }
+#endif
+    for (int rep = 0; rep < probe_repeats(4); rep++) {
+        if (pack)
+            PISA_TRY_HIP(rocprim::radix_sort_keys<FlatSortConfig>(temp, temp_bytes, flat_a, flat_b, (size_t)n, (unsigned)pack, 32u, s));
+        else
+            PISA_TRY_HIP(rocprim::radix_sort_pairs<FlatSortConfig>(temp, temp_bytes, flat_a, flat_b, idx_a, idx_b, (size_t)n, 0u, bits, s));
+    }
+    dispatch<1, 2, 3>(dim, [&](auto D) {
+        hipLaunchKernelGGL(kde_gather_sources_kernel<decltype(D)::value>, dim3(nb), dim3(256), 0, s, rec, 1.0 / k->sum_w, 1.0 / k->norm,
+                           pack ? flat_b : idx_b, pack ? (uint32_t)(((uint64_t)1 << pack) - 1) : 0xFFFFFFFFu, n, k->ys, k->wn,
+                           k->coef, k->adaptive ? (double *)nullptr : k->s2);
+    });
+    hipLaunchKernelGGL(kde_cell_start_flat_kernel, dim3((unsigned)((n + 256) / 256)), dim3(256), 0, s, flat_b, n,
+                       k->n_cells, k->cell_start, pack);
+    PISA_CHECK_LAUNCH("kde setup kernels");
+    return PISA_HIP_OK;
+}
+
+// ---- create, step 4: the pilot density at the sources
+// what the host builds for the pilot; uploaded asynchronously, so it lives until adaptive_bandwidths has synchronised
+struct PilotHost {
+    std::vector<KdeBlock> blocks;
+    std::vector<int32_t> cells, starts;   // flat index and first source of every non-empty cell
+    std::vector<int32_t> dense;           // the cells that get a Hermite series
+    std::vector<double> hankel;
+};
+
+struct PilotRun {   // arguments of the expansion kernels
+    const pisa_hip_kde *k;
+    hipStream_t s;
+    const KdeBlock *d_blocks;
+    int n_blocks, n_split, nd, n_heads, reach, h2l_split;
+    int32_t *d_dense, *slot, *hslot;
+    double *herm, *local, *d_hankel, *d_V;
+    uint8_t *d_vflag;
+    double *part, *pilot;
+    unsigned long long *pstamps;
+};
+
+// no local expansions: the Hermite series evaluated target by target
+template <int P>
+static void series_chain(const PilotRun &r) {
+    const pisa_hip_kde *k = r.k;
+    hipLaunchKernelGGL(kde_hermite_coef_kernel<P>, dim3((unsigned)r.nd), dim3(HC_THREADS), 0, r.s, k->g, r.d_dense,
+                       k->cell_start, k->ys, k->n, k->coef, r.herm);
+    hipLaunchKernelGGL(kde_hermite_pilot_kernel<P>, dim3((unsigned)r.n_blocks, (unsigned)r.n_split), dim3(KDE_THREADS), 0, r.s,
+                       k->g, r.d_blocks, k->ys, k->n, k->coef, k->cell_start, r.slot, r.herm, r.n_split, r.part, k->pair_count);
+}
+
+// P <= 16 (the matrix-core translation reads the coefficients transposed: the two go together); where the local
+// expansions are all there is, a wavefront per block evaluates them.  Returns the work counted here instead of by
+// the kernel (kde_local_pilot_wave_kernel).
+template <int P>
+static unsigned long long local_mfma_chain(const PilotRun &r) {
+    const pisa_hip_kde *k = r.k;
+    const KdeGeom &g = k->g;
+    hipLaunchKernelGGL(kde_hermite_coef_mfma_kernel, dim3((unsigned)r.nd), dim3(64 * FGT_WAVES), 0, r.s, g, r.d_dense, r.nd,
+                       k->cell_start, k->ys, k->n, k->coef, P, r.herm);
+    hipLaunchKernelGGL(kde_h2l_mfma_kernel<0>, dim3((unsigned)g.nc[0], (unsigned)((g.nc[1] + H2LM_T - 1) / H2LM_T)),
+                       dim3(64 * FGT_WAVES), 0, r.s, g, r.hslot, r.slot, r.herm, r.d_hankel, r.reach, P, r.d_V, r.d_vflag, r.local);
+    hipLaunchKernelGGL(kde_h2l_mfma_kernel<1>, dim3((unsigned)((g.nc[0] + H2LM_T - 1) / H2LM_T), (unsigned)g.nc[1]),
+                       dim3(64 * FGT_WAVES), 0, r.s, g, r.hslot, r.slot, r.herm, r.d_hankel, r.reach, P, r.d_V, r.d_vflag, r.local);
+    if (r.nd == r.n_heads) {
+        hipLaunchKernelGGL(kde_local_pilot_wave_kernel<P>, dim3((unsigned)r.n_blocks, (unsigned)(Q_CHUNK / (64 * FGT_WAVES))),
+                           dim3(64 * FGT_WAVES), 0, r.s, g, r.d_blocks, k->ys, k->n, r.local, r.pilot, r.pstamps);
+        return (unsigned long long)(P * P / 23 + 1) * (unsigned long long)k->n;
+    }
+    hipLaunchKernelGGL((kde_local_pilot_kernel<P, true>), dim3((unsigned)r.n_blocks), dim3(KDE_THREADS), 0, r.s, g, r.d_blocks,
+                       k->ys, k->n, k->coef, k->cell_start, r.slot, r.local, r.n_heads, r.h2l_split, r.pilot, k->pair_count);
+    return 0;
+}
+
+// P > 16
+template <int P>
+static void local_valu_chain(const PilotRun &r) {
+    const pisa_hip_kde *k = r.k;
+    const KdeGeom &g = k->g;
+    hipLaunchKernelGGL(kde_hermite_coef_kernel<P>, dim3((unsigned)r.nd), dim3(HC_THREADS), 0, r.s, g, r.d_dense,
+                       k->cell_start, k->ys, k->n, k->coef, r.herm);
+    hipLaunchKernelGGL((kde_h2l4_kernel<P, 0>), dim3((unsigned)g.nc[0], (unsigned)((g.nc[1] + H2L4_T - 1) / H2L4_T), (unsigned)r.h2l_split),
+                       dim3(H2L_THREADS), 0, r.s, g, r.hslot, r.slot, r.herm, r.d_hankel, r.reach, r.d_V, r.d_vflag, r.local, r.n_heads);
+    hipLaunchKernelGGL((kde_h2l4_kernel<P, 1>), dim3((unsigned)((g.nc[0] + H2L4_T - 1) / H2L4_T), (unsigned)g.nc[1], (unsigned)r.h2l_split),
+                       dim3(H2L_THREADS), 0, r.s, g, r.hslot, r.slot, r.herm, r.d_hankel, r.reach, r.d_V, r.d_vflag, r.local, r.n_heads);
+    if (r.nd < r.n_heads)
+        hipLaunchKernelGGL((kde_local_pilot_kernel<P, true>), dim3((unsigned)r.n_blocks), dim3(KDE_THREADS), 0, r.s, g, r.d_blocks,
+                           k->ys, k->n, k->coef, k->cell_start, r.slot, r.local, r.n_heads, r.h2l_split, r.pilot, k->pair_count);
+    else
+        hipLaunchKernelGGL((kde_local_pilot_kernel<P, false>), dim3((unsigned)r.n_blocks), dim3(KDE_THREADS), 0, r.s, g, r.d_blocks,
+                           k->ys, k->n, k->coef, k->cell_start, r.slot, r.local, r.n_heads, r.h2l_split, r.pilot, k->pair_count);
+}
+
+// Pilot by expansion: a Hermite series of every cell of `h.dense`, then the series target by target into `part`
+// (split partial sums) or, with local expansions, translated and evaluated into `pilot` (complete).
+// `host_pairs`: work to add to the kernels' own count.
+static int pilot_by_expansion(pisa_hip_kde *k, const KdePilotPlan &plan, PilotHost &h, const KdeBlock *d_blocks,
+                              int n_split, double *part, double *pilot, Arena &ar, hipStream_t s,
+                              unsigned long long &host_pairs) {
+    const int nd = (int)h.dense.size(), n_heads = (int)h.starts.size();
+    PilotRun r = {k, s, d_blocks, (int)h.blocks.size(), n_split, nd, n_heads, plan.reach, plan.h2l_split};
+    r.part = part;
+    r.pilot = pilot;
+#ifdef PISA_DEV_PROBES
+    const size_t n_pstamps = (size_t)r.n_blocks * (Q_CHUNK / 64);
+    static const char *pstamp_path = PISA_DEV_STR("KDE_PILOT_STAMPS");   // development: per-wavefront (start, inputs, end, targets of the block)
+    int rc_p = stamps_begin(pstamp_path, n_pstamps, s, &r.pstamps);
+    if (rc_p != PISA_HIP_OK) return rc_p;
+#endif
+    // Hermite / local coefficients live in a grow-only scratch of the library (sized by what this call needs, not
+    // by the workspace's worst case)
+    const KdePilotScratch lay = pilot_scratch(plan, nd, n_heads, k->n_cells);
+    int rc = kde_scratch(lay.bytes > g_kde_scratch_bytes ? lay.bytes + lay.bytes / 2 : lay.bytes, s, &r.herm);
+    if (rc != PISA_HIP_OK) return rc;
+    r.local = r.herm + lay.local;
+    r.d_hankel = r.herm + lay.hankel;
+    r.d_V = r.herm + lay.V;
+    r.d_vflag = (uint8_t *)(r.herm + lay.vflag);
+    r.d_dense = ar.take<int32_t>(h.dense.size());
+    r.slot = ar.take<int32_t>(k->n_cells);
+    int32_t *d_tcells = ar.take<int32_t>(n_heads);
+    r.hslot = ar.take<int32_t>(k->n_cells);   // cell -> index among the non-empty cells
+    if (!ar.ok) return PISA_HIP_ERR_NOMEM;
+    PISA_TRY_HIP(hipMemcpyAsync(r.d_dense, h.dense.data(), h.dense.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    PISA_TRY_HIP(hipMemsetAsync(r.slot, 0xFF, (size_t)k->n_cells * sizeof(int32_t), s));
+    hipLaunchKernelGGL(kde_slot_scatter_kernel, dim3((unsigned)((nd + 255) / 256)), dim3(256), 0, s, r.d_dense, nd, r.slot);
+    if (plan.local_ok) {
+        h.hankel = hankel_table(plan.reach, plan.P, k->g.cell);
+        PISA_TRY_HIP(hipMemcpyAsync(r.d_hankel, h.hankel.data(), h.hankel.size() * sizeof(double), hipMemcpyHostToDevice, s));
+        if (nd == n_heads) {
+            // every non-empty cell has a series: its slot IS its index among the non-empty cells
+            // (both lists are in cell order), and the list of target cells is the list of series
+            r.hslot = r.slot;
+        } else {
+            PISA_TRY_HIP(hipMemcpyAsync(d_tcells, h.cells.data(), h.cells.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+            PISA_TRY_HIP(hipMemsetAsync(r.hslot, 0xFF, (size_t)k->n_cells * sizeof(int32_t), s));
+            hipLaunchKernelGGL(kde_slot_scatter_kernel, dim3((unsigned)((n_heads + 255) / 256)), dim3(256), 0, s,
+                               d_tcells, n_heads, r.hslot);
+        }
+    }
+    for (int rep = 0; rep < probe_repeats(2); rep++)
+        dispatch<14, 16, 18, 20>(plan.P, [&](auto PP) {
+            constexpr int P = decltype(PP)::value;
+            if (!plan.local_ok) series_chain<P>(r);
+            else if constexpr (P <= 16) host_pairs = local_mfma_chain<P>(r);
+            else local_valu_chain<P>(r);
+        });
+    PISA_CHECK_LAUNCH("kde expansion kernels");
+#ifdef PISA_DEV_PROBES
+    if (r.pstamps) PISA_TRY_HIP(hipStreamSynchronize(s));
+    rc_p = stamps_dump(r.pstamps, n_pstamps, pstamp_path, "wb", nullptr);
+    if (rc_p != PISA_HIP_OK) return rc_p;
+#endif
+    k->n_dense = nd;
+    return PISA_HIP_OK;
+}
+
+// ---- create, step 5: local bandwidths from the pilot density at the sources themselves: queries = sorted sources,
+// tiles = cells.  The non-empty cells ("heads") and the workgroups over their sources come from the cell table, read
+// back once.
+static int adaptive_bandwidths(pisa_hip_kde *k, double *partial, Arena &ar, hipStream_t s) {
+    const int64_t n = k->n;
+    PilotHost h;
+    {
+        std::vector<int32_t> cs((size_t)k->n_cells + 1);
+        PISA_TRY_HIP(hipMemcpyAsync(cs.data(), k->cell_start, cs.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        PISA_TRY_HIP(hipStreamSynchronize(s));
+        pilot_blocks(cs.data(), k->g, k->n_cells, h.blocks, h.cells, h.starts);
+        if (h.starts.empty()) return PISA_HIP_ERR_INVALID;
+    }
+    const int n_blocks = (int)h.blocks.size();
+    const int n_split = pick_split(n_blocks);
+    unsigned long long pilot_host_pairs = 0;
+    KdeBlock *d_blocks = ar.take<KdeBlock>(h.blocks.size());
+    double *pilot = ar.take<double>(n);
+    double *part = n_split > 1 ? ar.take<double>((size_t)n_split * n) : pilot;
+    if (!ar.ok) return PISA_HIP_ERR_NOMEM;
+    PISA_TRY_HIP(hipMemcpyAsync(d_blocks, h.blocks.data(), h.blocks.size() * sizeof(KdeBlock), hipMemcpyHostToDevice, s));
+    const KdePilotPlan plan = pilot_plan(k->g, k->n_cells, n, k->tol, g_kde_expansion, hermite_min());
+    if (plan.expand)   // (2-D: the flat index of a cell is what the kernels of the series take)
+        for (size_t c = 0; c < h.starts.size(); c++)
+            if ((c + 1 < h.starts.size() ? h.starts[c + 1] : n) - h.starts[c] >= plan.dense_min) h.dense.push_back(h.cells[c]);
+    if (!h.dense.empty()) {
+        int rc = pilot_by_expansion(k, plan, h, d_blocks, n_split, part, pilot, ar, s, pilot_host_pairs);
+        if (rc != PISA_HIP_OK) return rc;
+        if (plan.local_ok) part = pilot;   // complete (no split)
+    } else {
+        int rc = launch_pairs<false, Q_PER_THREAD>(k, d_blocks, n_blocks, n_split, k->ys, n, part, s);
+        if (rc != PISA_HIP_OK) return rc;
+    }
+    if (n_split > 1 && part != pilot)
+        hipLaunchKernelGGL(kde_combine_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, part, n_split, n,
+                           (const uint32_t *)nullptr, pilot);
+    hipLaunchKernelGGL(kde_logsum_kernel, dim3(RED_BLOCKS), dim3(RED_THREADS), 0, s, pilot, k->wn, n, partial);
+    double *partial_mm = partial + 2 * RED_BLOCKS;   // (its own region: the logsum partials are still being read)
+    hipLaunchKernelGGL(kde_bandwidth_kernel, dim3(RED_BLOCKS), dim3(RED_THREADS), 0, s, pilot, k->wn, n,
+                       partial, k->alpha, k->dim, 1.0 / k->norm, k->coef, k->s2, partial_mm);
+    hipLaunchKernelGGL(kde_final_reduce_kernel, dim3(1), dim3(RED_THREADS), 0, s, partial_mm, 2, 0, 1,
+                       k->scalars + 1);   // [1] min s2, [2] max s2
+    PISA_CHECK_LAUNCH("kde pilot kernels");
+    PISA_TRY_HIP(hipMemcpyAsync(k->s2_range, k->scalars + 1, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
+    PISA_TRY_HIP(hipMemcpyAsync(&k->pairs_pilot, k->pair_count, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    PISA_TRY_HIP(hipMemsetAsync(k->pair_count, 0, 64, s));
+    // one synchronisation for the uploads of the host tables (`h`), the two read-backs and the reset
+    PISA_TRY_HIP(hipStreamSynchronize(s));
+    k->pairs_pilot += pilot_host_pairs;
+    return PISA_HIP_OK;
+}
+
+// ---- the lattice form's launch shape for an estimator (kde_plan.hpp), with the development knobs
+static int lattice_strip(const pisa_hip_kde *k, const double *step, const int64_t *count) {
+    static const int forced = PISA_DEV_INT("KDE_LATTICE_R", -1);
+    return lattice_strip(k->g, k->s2_range[1], step, count, forced);
+}
+
+static int64_t lattice_waves(int R, int sw, int lpw, const int64_t *count) {
+    static const int waves = PISA_DEV_INT("KDE_LATTICE_WAVES", 6144);
+    return lattice_waves(R, sw, lpw, count, waves);
 }
 
 }  // namespace pisa
 
-// split partial sums exist only below 1024 workgroups, i.e. below 2^19 queries
-static size_t split_bytes(int64_t m) { return (size_t)32 * 8 * (size_t)std::min<int64_t>(m, 1 << 19); }
-
 PISA_API int64_t pisa_hip_kde_workspace_bytes(int32_t dim, int64_t n_src) {
     if (dim < 1 || dim > 3 || n_src < 1 || n_src > 0x7FFFFFF0LL) return -1;
-    const size_t n = (size_t)n_src;
-    size_t total = resident_bytes(dim, n_src, cells_cap(n_src)) + (size_t)RED_BLOCKS * 16 * 8;
-    total += 4 * n * 8 + n * 8 + 2 * n * 4;              // (y, weight) records, flat keys x2, idx x2
-    total += n + n * 4 + n * 8;                          // flags, starts, head keys
-    total += n * 8 + split_bytes(n_src);                 // pilot, split partials
-    total += sort_temp_bytes(n_src) + (n / Q_CHUNK + (size_t)cells_cap(n_src)) * sizeof(KdeBlock);
-    if (dim == 2)   // cell -> slot map, lists of dense / non-empty cells (the coefficients live in library scratch)
-        total += (n / hermite_min() + 1) * 4 + (size_t)cells_cap(n_src) * 12 + 4096;   // dense list: one entry per cell at most
-    return (int64_t)(total + 64 * 256);
+    return (int64_t)create_workspace_bytes(dim, n_src, sort_temp_bytes(n_src), hermite_min());
 }
 
 PISA_API int pisa_hip_kde_release_scratch(void) {
@@ -2194,436 +2447,27 @@ PISA_API int pisa_hip_kde_create(int32_t dim, const double *d_x, const double *d
         return PISA_HIP_ERR_INVALID;
     hipStream_t s = as_stream(stream);
     Arena ar(d_work, (size_t)work_bytes);
-    pisa_hip_kde *k = (pisa_hip_kde *)calloc(1, sizeof(pisa_hip_kde));
+    std::unique_ptr<pisa_hip_kde, KdeFree> k((pisa_hip_kde *)calloc(1, sizeof(pisa_hip_kde)));
     if (!k) return PISA_HIP_ERR_NOMEM;
     k->dim = dim; k->n = n; k->adaptive = adaptive; k->alpha = alpha; k->tol = tol;
-#define KDE_FAIL(rc) do { free(k); return (rc); } while (0)
-#define KDE_TRY(expr) do { int _rc = (expr); if (_rc != PISA_HIP_OK) KDE_FAIL(_rc); } while (0)
-#define KDE_TRY_HIP(expr) do { int _rc = ::pisa::check_hip((expr), #expr); if (_rc != PISA_HIP_OK) KDE_FAIL(_rc); } while (0)
-    // ---- resident part of the workspace (a first guess of the cell count is fixed up below)
     double *partial = ar.take<double>((size_t)RED_BLOCKS * 16);
     (void)ar.take<double>(16);   // (was the device-side join of the moment partials: the workspace layout is unchanged)
-    if (!ar.ok) KDE_FAIL(PISA_HIP_ERR_NOMEM);
-    const unsigned nb = (unsigned)((n + 255) / 256);
-    // ---- moments
-    double h1[10], h2[7];
-#define KDE_D(KERNEL, ...) do { if (dim == 1) hipLaunchKernelGGL(KERNEL<1>, __VA_ARGS__); else if (dim == 2) hipLaunchKernelGGL(KERNEL<2>, __VA_ARGS__); else hipLaunchKernelGGL(KERNEL<3>, __VA_ARGS__); } while (0)
-    // (the per-workgroup partial results come back and are joined here, in kde_final_reduce_kernel's order: one
-    //  launch less per pass on a chain that is launch-latency bound for small samples)
-    double hp[RED_BLOCKS * 10];
-    KDE_D(kde_moments1_kernel, dim3(RED_BLOCKS), dim3(RED_THREADS), 0, s, d_x, d_w, n, partial);
-    KDE_TRY_HIP(hipMemcpyAsync(hp, partial, (size_t)RED_BLOCKS * (1 + 3 * dim) * sizeof(double), hipMemcpyDeviceToHost, s));
-    KDE_TRY_HIP(hipStreamSynchronize(s));
-    final_reduce_host(hp, 1 + 3 * dim, 1 + dim, dim, h1);
-    const double sw = h1[0];
-    if (!(sw > 0.0) || !std::isfinite(sw)) KDE_FAIL(PISA_HIP_ERR_INVALID);
-    double xmin[3] = {0, 0, 0}, xmax[3] = {0, 0, 0};
-    for (int d = 0; d < dim; d++) {
-        k->mean[d] = h1[1 + d] / sw;
-        xmin[d] = h1[1 + dim + d];
-        xmax[d] = h1[1 + 2 * dim + d];
-    }
-    KDE_D(kde_moments2_kernel, dim3(RED_BLOCKS), dim3(RED_THREADS), 0, s, d_x, d_w, n, k->mean[0],
-          k->mean[1], k->mean[2], partial);
-    KDE_TRY_HIP(hipMemcpyAsync(hp, partial, (size_t)RED_BLOCKS * 7 * sizeof(double), hipMemcpyDeviceToHost, s));
-    KDE_TRY_HIP(hipStreamSynchronize(s));
-    final_reduce_host(hp, 7, 7, 0, h2);
-    // ---- bandwidth matrix (unbiased weighted covariance x factor^2), its inverse, whitening
-    k->sum_w = sw;
-    const double denom = 1.0 - h2[0] / (sw * sw);
-    double cov[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
-    {
-        int idx = 1;
-        for (int d = 0; d < dim; d++)
-            for (int e = d; e < dim; e++) {
-                cov[d][e] = cov[e][d] = h2[idx] / sw / denom;
-                idx++;
-            }
-    }
-    k->factor = bw_method == 0 ? pow((double)n * (dim + 2) / 4.0, -1.0 / (dim + 4))   // silverman
-                               : pow((double)n, -1.0 / (dim + 4));                      // scott
-    double H[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
-    for (int d = 0; d < dim; d++)
-        for (int e = 0; e < dim; e++) H[d][e] = cov[d][e] * k->factor * k->factor;
-    const double det = H[0][0] * (H[1][1] * H[2][2] - H[1][2] * H[2][1]) -
-                       H[0][1] * (H[1][0] * H[2][2] - H[1][2] * H[2][0]) +
-                       H[0][2] * (H[1][0] * H[2][1] - H[1][1] * H[2][0]);
-    if (!(det > 0.0) || !std::isfinite(det)) KDE_FAIL(PISA_HIP_ERR_INVALID);
-    double inv[3][3];
-    inv[0][0] = (H[1][1] * H[2][2] - H[1][2] * H[2][1]) / det;
-    inv[0][1] = (H[0][2] * H[2][1] - H[0][1] * H[2][2]) / det;
-    inv[0][2] = (H[0][1] * H[1][2] - H[0][2] * H[1][1]) / det;
-    inv[1][0] = (H[1][2] * H[2][0] - H[1][0] * H[2][2]) / det;
-    inv[1][1] = (H[0][0] * H[2][2] - H[0][2] * H[2][0]) / det;
-    inv[1][2] = (H[0][2] * H[1][0] - H[0][0] * H[1][2]) / det;
-    inv[2][0] = (H[1][0] * H[2][1] - H[1][1] * H[2][0]) / det;
-    inv[2][1] = (H[0][1] * H[2][0] - H[0][0] * H[2][1]) / det;
-    inv[2][2] = (H[0][0] * H[1][1] - H[0][1] * H[1][0]) / det;
-    k->norm = sqrt(pow(2.0 * M_PI, dim) * det);
-    for (int d = 0; d < 3; d++)
-        for (int e = 0; e < 3; e++) {
-            k->cov[d * 3 + e] = (d < dim && e < dim) ? H[d][e] : 0.0;
-            k->inv_cov[d * 3 + e] = (d < dim && e < dim) ? inv[d][e] : 0.0;
-        }
-    // Cholesky inv = L L^T, U = L^T  =>  |U v|^2 = v^T inv v
-    double L[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
-    for (int i = 0; i < dim; i++)
-        for (int j = 0; j <= i; j++) {
-            double sum = inv[i][j];
-            for (int p = 0; p < j; p++) sum -= L[i][p] * L[j][p];
-            if (i == j) {
-                if (!(sum > 0.0)) KDE_FAIL(PISA_HIP_ERR_INVALID);
-                L[i][i] = sqrt(sum);
-            } else L[i][j] = sum / L[j][j];
-        }
-    KdeGeom &g = k->g;
-    memset(&g, 0, sizeof(g));
-    g.dim = dim;
-    for (int d = 0; d < 3; d++) {
-        g.mean[d] = k->mean[d];
-        for (int e = 0; e < 3; e++) g.U[d * 3 + e] = (d < dim && e < dim) ? L[e][d] : 0.0;
-    }
-    // ---- cell grid over the whitened bounding box (image of the corners of the x box)
-    double ylo[3] = {0, 0, 0}, yhi[3] = {0, 0, 0};
-    for (int d = 0; d < dim; d++) { ylo[d] = INFINITY; yhi[d] = -INFINITY; }
-    for (int corner = 0; corner < (1 << dim); corner++) {
-        double xc[3] = {0, 0, 0};
-        for (int d = 0; d < dim; d++) xc[d] = ((corner >> d) & 1 ? xmax[d] : xmin[d]) - k->mean[d];
-        for (int d = 0; d < dim; d++) {
-            double a = 0.0;
-            for (int e = d; e < dim; e++) a += g.U[d * 3 + e] * xc[e];
-            ylo[d] = std::min(ylo[d], a);
-            yhi[d] = std::max(yhi[d], a);
-        }
-    }
-    const bool cut = tol > 0.0;
-    g.rcut2 = cut ? 2.0 * log(1.0 / tol) : 0.0;
-    k->r_cut = cut ? sqrt(g.rcut2) : INFINITY;
-    double extent = 0.0;
-    for (int d = 0; d < dim; d++) extent = std::max(extent, yhi[d] - ylo[d]);
-    if (!std::isfinite(extent)) KDE_FAIL(PISA_HIP_ERR_INVALID);
-    double cell = cut ? k->r_cut / (dim == 3 ? 4.0 : 8.0) : (extent > 0 ? 2.0 * extent : 1.0);
-    for (;;) {   // keep the grid below MAX_CELLS and every coordinate below 2^20
-        double total = 1.0;
-        bool ok = true;
-        for (int d = 0; d < dim; d++) {
-            const double c = floor((yhi[d] - ylo[d]) / cell) + 1.0;
-            total *= c;
-            ok = ok && c < (double)(KEY_OFF / 16);
-        }
-        if (ok && total <= (double)cells_cap(n)) break;
-        cell *= 1.25;
-    }
-    g.cell = cell;
-    g.inv_cell = 1.0 / cell;
-    k->n_cells = 1;
-    for (int d = 0; d < 3; d++) {
-        g.nc[d] = d < dim ? (int)(floor((yhi[d] - ylo[d]) / cell) + 1.0) : 1;
-        g.ylo[d] = d < dim ? ylo[d] : 0.0;
-        k->n_cells *= g.nc[d];
-    }
-    // ---- resident arrays
-    k->ys = ar.take<double>((size_t)dim * n);
-    k->wn = ar.take<double>(n);
-    k->coef = ar.take<double>(n);
-    k->s2 = ar.take<double>(n);
-    k->cell_start = ar.take<int32_t>(k->n_cells + 1);
-    k->cell_s2min = ar.take<double>(k->n_cells);
-    k->scalars = ar.take<double>(8);
-    k->pair_count = ar.take<unsigned long long>(8);
-    // ---- transient arrays
-    double *rec = ar.take<double>((size_t)4 * n);      // (y, weight) per source, 32 bytes
-    uint64_t *keys_a = ar.take<uint64_t>(n);
-    uint32_t *idx_a = ar.take<uint32_t>(n), *idx_b = ar.take<uint32_t>(n);
-    const size_t temp_bytes = sort_temp_bytes(n);
-    char *temp = ar.take<char>(temp_bytes);
-    if (!ar.ok) KDE_FAIL(PISA_HIP_ERR_NOMEM);
-    KDE_TRY_HIP(hipMemsetAsync(k->pair_count, 0, 64, s));
-    // ---- whiten, sort by cell, cell table
-    uint32_t *flat_a = (uint32_t *)keys_a, *flat_b = flat_a + n;   // (the key arrays of the general form hold two 32-bit ones)
-    unsigned bits = 1;
-    while (bits < 32 && ((int64_t)1 << bits) < k->n_cells) bits++;
-    // cell and source index in one 32-bit word where both fit ((cell << pack) | index): the sort moves keys only -- half the
-    // bytes per pass --, sorted on the cell's bits; the order is the stable order of the pair sort (the indices ascend)
-    const int pack = (bits < 32 && n <= ((int64_t)1 << (32 - bits))) ? (int)(32 - bits) : 0;
-    KDE_D(kde_whiten_flat_kernel, dim3(nb), dim3(256), 0, s, d_x, d_w, n, g, rec, flat_a, idx_a, pack);
-#ifdef PISA_DEV_PROBES
-    {   // development (EXPERIMENTS R6-7): N empty launches per estimator -- is the evaluation bound by the number of runtime calls?
-        static const int extra = PISA_DEV_INT("KDE_EXTRA_LAUNCHES", 0);
-        for (int e = 0; e < extra; e++) hipLaunchKernelGGL(kde_noop_kernel, dim3(1), dim3(64), 0, s, k->scalars);
-    }
-#endif
-    size_t tb = temp_bytes;
-    {
-        static const int twice = PISA_DEV_INT("KDE_TWICE", 0);   // development: marginal cost of a phase = wall time with it run twice
-        for (int rep = 0; rep < ((twice & 4) ? 2 : 1); rep++) {
-            if (pack)
-                KDE_TRY_HIP(rocprim::radix_sort_keys<FlatSortConfig>(temp, tb, flat_a, flat_b, (size_t)n, (unsigned)pack, 32u, s));
-            else
-                KDE_TRY_HIP(rocprim::radix_sort_pairs<FlatSortConfig>(temp, tb, flat_a, flat_b, idx_a, idx_b, (size_t)n, 0u, bits, s));
-        }
-    }
-    KDE_D(kde_gather_sources_kernel, dim3(nb), dim3(256), 0, s, rec, 1.0 / sw, 1.0 / k->norm, pack ? flat_b : idx_b,
-          pack ? (uint32_t)(((uint64_t)1 << pack) - 1) : 0xFFFFFFFFu, n, k->ys, k->wn,
-          k->coef, adaptive ? (double *)nullptr : k->s2);
-    hipLaunchKernelGGL(kde_cell_start_flat_kernel, dim3((unsigned)((n + 256) / 256)), dim3(256), 0, s, flat_b, n,
-                       k->n_cells, k->cell_start, pack);
-    KDE_TRY(check_hip(hipGetLastError(), "kde setup kernels"));
-    if (!adaptive) {
-        k->s2_range[0] = k->s2_range[1] = 1.0;
-        KDE_TRY_HIP(hipMemcpyAsync(k->scalars + 1, k->s2_range, 2 * sizeof(double), hipMemcpyHostToDevice, s));
+    if (!ar.ok) return PISA_HIP_ERR_NOMEM;
+    KdeMoments mo;
+    int rc = reduce_moments(dim, d_x, d_w, n, partial, s, mo);
+    if (rc == PISA_HIP_OK) rc = plan_estimator(k.get(), mo, bw_method);
+    if (rc == PISA_HIP_OK) rc = sort_sources(k.get(), d_x, d_w, ar, s);
+    if (rc != PISA_HIP_OK) return rc;
+    if (adaptive) {
+        rc = adaptive_bandwidths(k.get(), partial, ar, s);
+        if (rc != PISA_HIP_OK) return rc;
     } else {
-        // pilot estimate at the sources themselves: queries = sorted sources, tiles = cells.  The non-empty cells
-        // ("heads") and the workgroups over their sources come from the cell table, read back once.
-        std::vector<KdeBlock> blocks;
-        std::vector<int32_t> h_starts;
-        std::vector<uint64_t> h_keys;
-        {
-            std::vector<int32_t> cs((size_t)k->n_cells + 1);
-            KDE_TRY_HIP(hipMemcpyAsync(cs.data(), k->cell_start, cs.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-            KDE_TRY_HIP(hipStreamSynchronize(s));
-            const int64_t nx = g.nc[0], nxy = (int64_t)g.nc[0] * g.nc[1];
-            for (int64_t c = 0; c < k->n_cells; c++) {
-                const int64_t begin = cs[c], end = cs[c + 1];
-                if (end <= begin) continue;
-                const int64_t cz = c / nxy, cy = (c - cz * nxy) / nx, cx = c - cz * nxy - cy * nx;
-                KdeBlock b;
-                b.head = (int32_t)h_starts.size();
-                b.c0[0] = b.c1[0] = (int32_t)cx; b.c0[1] = b.c1[1] = (int32_t)cy; b.c0[2] = b.c1[2] = (int32_t)cz;
-                h_starts.push_back((int32_t)begin);
-                h_keys.push_back(((uint64_t)(cz + KEY_OFF) << 42) | ((uint64_t)(cy + KEY_OFF) << 21) | (uint64_t)(cx + KEY_OFF));
-                // equal shares: a cell of 600 sources becomes 300 + 300, not 512 + 88
-                const int64_t parts = (end - begin + Q_CHUNK - 1) / Q_CHUNK;
-                for (int64_t pp = 0; pp < parts; pp++) {
-                    const int64_t q0 = begin + (end - begin) * pp / parts, q1 = begin + (end - begin) * (pp + 1) / parts;
-                    b.q_begin = (int32_t)q0;
-                    b.q_count = (int32_t)(q1 - q0);
-                    blocks.push_back(b);
-                }
-            }
-            if (h_starts.empty()) KDE_FAIL(PISA_HIP_ERR_INVALID);
-        }
-        const int n_blocks = (int)blocks.size();
-        const int n_split = pick_split(n_blocks);
-        unsigned long long pilot_host_pairs = 0;   // work counted here instead of by the kernel (kde_local_pilot_wave_kernel)
-        KdeBlock *d_blocks = ar.take<KdeBlock>(blocks.size());
-        double *pilot = ar.take<double>(n);
-        double *part = n_split > 1 ? ar.take<double>((size_t)n_split * n) : pilot;
-        if (!ar.ok) KDE_FAIL(PISA_HIP_ERR_NOMEM);
-        KDE_TRY_HIP(hipMemcpyAsync(d_blocks, blocks.data(), blocks.size() * sizeof(KdeBlock),
-                                   hipMemcpyHostToDevice, s));
-        // dense cells get a Hermite series (2-D, with a cut-off, enough sources to pay)
-        // host tables uploaded asynchronously below: they live until the synchronisation at the end
-        std::vector<int32_t> dense, tcells;
-        std::vector<double> hankel;
-        // Order of the Hermite / local series: the smallest of 14, 16, 18, 20 whose truncation bound (see above: 2.3 K^2
-        // (cell / 2)^P / sqrt(P!) of a cell's weight, all of it at a corner of the cell) is within 4 x tol.  The cells are
-        // r_cut / 8 wide, so the bound depends on tol through the cell size as well: 20 at 1e-14 (1.8e-15), 16 at 1e-12
-        // (2.8e-12; round 4 took 18 there: 3.5e-14, 28 x finer than the cut-off it sits beside), 14 at 1e-10.  The pilot's
-        // error reaches a density only through lambda = (pilot / g)^-alpha, i.e. scaled by alpha (<= 1).
-        // The cells are wider than r_cut / 8 where the grid had to fit cells_cap(n) (a far outlier, with or without weight,
-        // widens the bounding box): if order 20 misses the bound as well there is no expansion, the pilot is the direct
-        // pair sum (n_dense = 0).  Before, 20 was taken unchecked: pilot errors of 5e-6 of a cell's weight at cell = 3.8.
-        int P = 0;
-        for (int cand : {14, 16, 18, 20}) {
-            double bound = 2.3 * 1.09 * 1.09, fact = 1.0;
-            for (int i = 1; i <= cand; i++) { bound *= 0.5 * g.cell; fact *= (double)i; }
-            if (bound / sqrt(fact) <= 4.0 * tol) { P = cand; break; }
-        }
-        const bool series_ok = P != 0;
-        if (!series_ok) P = 20;   // (sizes below only)
-        // local expansions need the intermediate V of every cell of the grid: bounded
-        const bool local_ok = g_kde_expansion >= 2 && ceil(sqrt(g.rcut2) * g.inv_cell) <= (double)H2L_MAX_REACH &&
-                              (double)k->n_cells * (P * P) * 8.0 < 2.0e9;
-        // with local expansions a series costs its cell 400 multiply-adds per source and nothing per
-        // target, so every non-empty cell gets one; evaluated target by target (no local expansions) a
-        // series pays from ~24 sources
-        const int dense_min = local_ok ? hermite_min() : std::max(hermite_min(), HERMITE_MIN_SERIES);
-        constexpr int64_t expansion_min_n = 1000;
-        // (1 000: C3-shaped evaluations of 1e5 / 3e5 events take 11.5 / 27.5 ms with the round-2 threshold of 20 000 sources per
-        //  estimator -- direct pair sums below it --, 5.7 / 5.9 ms with this one)
-        if (g_kde_expansion && series_ok && dim == 2 && cut && n >= expansion_min_n) {
-            for (size_t h = 0; h < h_starts.size(); h++) {
-                const int64_t end = h + 1 < h_starts.size() ? h_starts[h + 1] : n;
-                if (end - h_starts[h] < dense_min) continue;
-                const int64_t cx = (int64_t)(h_keys[h] & 0x1FFFFF) - KEY_OFF;
-                const int64_t cy = (int64_t)((h_keys[h] >> 21) & 0x1FFFFF) - KEY_OFF;
-                dense.push_back((int32_t)(cy * g.nc[0] + cx));
-            }
-        }
-        if (!dense.empty()) {
-            const int nd = (int)dense.size();
-            const int n_heads = (int)h_starts.size();
-            const int reach = (int)ceil(sqrt(g.rcut2) * g.inv_cell);
-            const bool local_exp = local_ok;
-            // Hermite / local coefficients live in a grow-only scratch of the library (up to
-            // 3.2 KB per cell: sized by what this call needs, not by the workspace's worst case)
-            const size_t pp = (size_t)(P * P);
-            // translation passes: on the matrix cores where the series order allows (<= 16), in one part; else four targets
-            // per workgroup on the vector units, in two parts of the source positions (see kde_h2l4_kernel): V, its flags
-            // and the local expansions once per part
-            const int h2l_split = P <= 16 ? 1 : 2;
-            unsigned long long *pstamps = nullptr;
-#ifdef PISA_DEV_PROBES
-            const size_t n_pstamps = (size_t)n_blocks * (Q_CHUNK / 64);
-            static const char *pstamp_path = PISA_DEV_STR("KDE_PILOT_STAMPS");   // development: per-wavefront (start, inputs, end, targets of the block)
-            if (pstamp_path) {
-                KDE_TRY_HIP(hipMalloc((void **)&pstamps, n_pstamps * 32));
-                KDE_TRY_HIP(hipMemsetAsync(pstamps, 0, n_pstamps * 32, s));
-            }
-#endif
-            const size_t need = (nd * pp + (local_exp ? h2l_split * (n_heads + (size_t)k->n_cells) * pp + (2 * reach + 1) * (2 * P - 1) : 0))
-                                * sizeof(double) + (local_exp ? (size_t)h2l_split * k->n_cells : 0) + 8192;
-            double *herm = nullptr;
-            KDE_TRY(kde_scratch(need > g_kde_scratch_bytes ? need + need / 2 : need, s, &herm));
-            double *local = herm + nd * pp;
-            double *d_hankel = local + (local_exp ? h2l_split * n_heads * pp : 0);
-            double *d_V = d_hankel + (2 * reach + 1) * (2 * P - 1);
-            uint8_t *d_vflag = (uint8_t *)(d_V + (local_exp ? (size_t)h2l_split * k->n_cells * pp : 0));
-            int32_t *d_dense = ar.take<int32_t>(dense.size());
-            int32_t *slot = ar.take<int32_t>(k->n_cells);
-            int32_t *d_tcells = ar.take<int32_t>(n_heads);
-            int32_t *hslot = ar.take<int32_t>(k->n_cells);   // cell -> index among the non-empty cells
-            if (!ar.ok) KDE_FAIL(PISA_HIP_ERR_NOMEM);
-            KDE_TRY_HIP(hipMemcpyAsync(d_dense, dense.data(), dense.size() * sizeof(int32_t),
-                                       hipMemcpyHostToDevice, s));
-            KDE_TRY_HIP(hipMemsetAsync(slot, 0xFF, (size_t)k->n_cells * sizeof(int32_t), s));
-            hipLaunchKernelGGL(kde_slot_scatter_kernel, dim3((unsigned)((nd + 255) / 256)), dim3(256), 0, s,
-                               d_dense, nd, slot);
-            tcells.assign(n_heads, 0);
-            hankel.clear();
-            if (local_exp) {
-                for (int h = 0; h < n_heads; h++) {
-                    const int64_t cx = (int64_t)(h_keys[h] & 0x1FFFFF) - KEY_OFF;
-                    const int64_t cy = (int64_t)((h_keys[h] >> 21) & 0x1FFFFF) - KEY_OFF;
-                    tcells[h] = (int32_t)(cy * g.nc[0] + cx);
-                }
-                const int nh = 2 * P - 1;
-                hankel.resize((size_t)(2 * reach + 1) * nh);
-                for (int j = -reach; j <= reach; j++) {
-                    // h_n(d), d = j * cell / sqrt 2: h_0 = exp(-d^2), h_1 = 2 d h_0, h_{n+1} = 2 d h_n - 2 n h_{n-1}
-                    const long double d = (long double)j * (long double)g.cell * 0.70710678118654752440084436210485L;
-                    long double h0 = expl(-d * d), h1 = 2.0L * d * h0;
-                    double *row = hankel.data() + (size_t)(j + reach) * nh;
-                    row[0] = (double)h0;
-                    row[1] = (double)h1;
-                    for (int m = 1; m + 1 < nh; m++) {
-                        const long double h2 = 2.0L * d * h1 - 2.0L * m * h0;
-                        row[m + 1] = (double)h2;
-                        h0 = h1;
-                        h1 = h2;
-                    }
-                }
-                KDE_TRY_HIP(hipMemcpyAsync(d_hankel, hankel.data(), hankel.size() * sizeof(double),
-                                           hipMemcpyHostToDevice, s));
-                if (nd == n_heads) {
-                    // every non-empty cell has a series: its slot IS its index among the non-empty cells
-                    // (both lists are in cell order), and the list of target cells is the list of series
-                    hslot = slot;
-                    d_tcells = d_dense;
-                } else {
-                    KDE_TRY_HIP(hipMemcpyAsync(d_tcells, tcells.data(), tcells.size() * sizeof(int32_t),
-                                               hipMemcpyHostToDevice, s));
-                    KDE_TRY_HIP(hipMemsetAsync(hslot, 0xFF, (size_t)k->n_cells * sizeof(int32_t), s));
-                    hipLaunchKernelGGL(kde_slot_scatter_kernel, dim3((unsigned)((n_heads + 255) / 256)), dim3(256), 0, s,
-                                       d_tcells, n_heads, hslot);
-                }
-            }
-            dim3 grid((unsigned)n_blocks, (unsigned)n_split);
-            // no local expansions: the Hermite series evaluated target by target
-#define KDE_SERIES(PP) do { \
-                hipLaunchKernelGGL(kde_hermite_coef_kernel<PP>, dim3((unsigned)nd), dim3(HC_THREADS), 0, s, g, d_dense, \
-                                   k->cell_start, k->ys, n, k->coef, herm); \
-                hipLaunchKernelGGL(kde_hermite_pilot_kernel<PP>, grid, dim3(KDE_THREADS), 0, s, g, d_blocks, \
-                                   k->ys, n, k->coef, k->cell_start, slot, herm, n_split, part, k->pair_count); \
-            } while (0)
-            // P <= 16 (the matrix-core translation reads the coefficients transposed: the two go together); where the local
-            // expansions are all there is, a wavefront per block evaluates them
-#define KDE_LOCAL_MFMA(PP) do { \
-                hipLaunchKernelGGL(kde_hermite_coef_mfma_kernel, dim3((unsigned)nd), dim3(64 * FGT_WAVES), 0, s, g, d_dense, nd, \
-                                   k->cell_start, k->ys, n, k->coef, PP, herm); \
-                hipLaunchKernelGGL(kde_h2l_mfma_kernel<0>, dim3((unsigned)g.nc[0], (unsigned)((g.nc[1] + H2LM_T - 1) / H2LM_T)), \
-                                   dim3(64 * FGT_WAVES), 0, s, g, hslot, slot, herm, d_hankel, reach, PP, d_V, d_vflag, local); \
-                hipLaunchKernelGGL(kde_h2l_mfma_kernel<1>, dim3((unsigned)((g.nc[0] + H2LM_T - 1) / H2LM_T), (unsigned)g.nc[1]), \
-                                   dim3(64 * FGT_WAVES), 0, s, g, hslot, slot, herm, d_hankel, reach, PP, d_V, d_vflag, local); \
-                if (nd == n_heads) { \
-                    hipLaunchKernelGGL(kde_local_pilot_wave_kernel<PP>, dim3((unsigned)n_blocks, (unsigned)(Q_CHUNK / (64 * FGT_WAVES))), dim3(64 * FGT_WAVES), 0, s, g, \
-                                       d_blocks, k->ys, n, local, pilot, pstamps); \
-                    pilot_host_pairs = (unsigned long long)(PP * PP / 23 + 1) * (unsigned long long)n; \
-                } else \
-                    hipLaunchKernelGGL((kde_local_pilot_kernel<PP, true>), dim3((unsigned)n_blocks), dim3(KDE_THREADS), 0, s, g, \
-                                       d_blocks, k->ys, n, k->coef, k->cell_start, slot, local, n_heads, h2l_split, pilot, k->pair_count); \
-            } while (0)
-            // P > 16
-#define KDE_LOCAL_VALU(PP) do { \
-                hipLaunchKernelGGL(kde_hermite_coef_kernel<PP>, dim3((unsigned)nd), dim3(HC_THREADS), 0, s, g, d_dense, \
-                                   k->cell_start, k->ys, n, k->coef, herm); \
-                hipLaunchKernelGGL((kde_h2l4_kernel<PP, 0>), dim3((unsigned)g.nc[0], (unsigned)((g.nc[1] + H2L4_T - 1) / H2L4_T), (unsigned)h2l_split), \
-                                   dim3(H2L_THREADS), 0, s, g, hslot, slot, herm, d_hankel, reach, d_V, d_vflag, local, n_heads); \
-                hipLaunchKernelGGL((kde_h2l4_kernel<PP, 1>), dim3((unsigned)((g.nc[0] + H2L4_T - 1) / H2L4_T), (unsigned)g.nc[1], (unsigned)h2l_split), \
-                                   dim3(H2L_THREADS), 0, s, g, hslot, slot, herm, d_hankel, reach, d_V, d_vflag, local, n_heads); \
-                if (nd < n_heads) \
-                    hipLaunchKernelGGL((kde_local_pilot_kernel<PP, true>), dim3((unsigned)n_blocks), dim3(KDE_THREADS), 0, s, g, \
-                                       d_blocks, k->ys, n, k->coef, k->cell_start, slot, local, n_heads, h2l_split, pilot, k->pair_count); \
-                else \
-                    hipLaunchKernelGGL((kde_local_pilot_kernel<PP, false>), dim3((unsigned)n_blocks), dim3(KDE_THREADS), 0, s, g, \
-                                       d_blocks, k->ys, n, k->coef, k->cell_start, slot, local, n_heads, h2l_split, pilot, k->pair_count); \
-            } while (0)
-            static const int twice = PISA_DEV_INT("KDE_TWICE", 0);
-            for (int rep = 0; rep < ((twice & 2) ? 2 : 1); rep++) {
-                if (!local_exp) {
-                    if (P == 14) KDE_SERIES(14); else if (P == 16) KDE_SERIES(16); else if (P == 18) KDE_SERIES(18); else KDE_SERIES(20);
-                } else if (P == 14) KDE_LOCAL_MFMA(14);
-                else if (P == 16) KDE_LOCAL_MFMA(16);
-                else if (P == 18) KDE_LOCAL_VALU(18);
-                else KDE_LOCAL_VALU(20);
-            }
-#undef KDE_SERIES
-#undef KDE_LOCAL_MFMA
-#undef KDE_LOCAL_VALU
-            KDE_TRY(check_hip(hipGetLastError(), "kde expansion kernels"));
-#ifdef PISA_DEV_PROBES
-            if (pstamps) {
-                std::vector<unsigned long long> h(n_pstamps * 4);
-                KDE_TRY_HIP(hipStreamSynchronize(s));
-                KDE_TRY_HIP(hipMemcpy(h.data(), pstamps, h.size() * 8, hipMemcpyDeviceToHost));
-                (void)hipFree(pstamps);
-                if (FILE *f = fopen(pstamp_path, "wb")) {
-                    fwrite(h.data(), 8, h.size(), f);
-                    fclose(f);
-                }
-            }
-#endif
-            k->n_dense = nd;
-            if (local_exp) part = pilot;   // complete (no split)
-        } else {
-            KDE_TRY((launch_pairs<false, Q_PER_THREAD>(k, d_blocks, n_blocks, n_split, k->ys, n, part, s)));
-        }
-        if (n_split > 1 && part != pilot)
-            hipLaunchKernelGGL(kde_combine_kernel, dim3(nb), dim3(256), 0, s, part, n_split, n,
-                               (const uint32_t *)nullptr, pilot);
-        hipLaunchKernelGGL(kde_logsum_kernel, dim3(RED_BLOCKS), dim3(RED_THREADS), 0, s, pilot, k->wn, n, partial);
-        double *partial_mm = partial + 2 * RED_BLOCKS;   // (its own region: the logsum partials are still being read)
-        hipLaunchKernelGGL(kde_bandwidth_kernel, dim3(RED_BLOCKS), dim3(RED_THREADS), 0, s, pilot, k->wn, n,
-                           partial, alpha, dim, 1.0 / k->norm, k->coef, k->s2, partial_mm);
-        hipLaunchKernelGGL(kde_final_reduce_kernel, dim3(1), dim3(RED_THREADS), 0, s, partial_mm, 2, 0, 1,
-                           k->scalars + 1);   // [1] min s2, [2] max s2
-        KDE_TRY(check_hip(hipGetLastError(), "kde pilot kernels"));
-        KDE_TRY_HIP(hipMemcpyAsync(k->s2_range, k->scalars + 1, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
-        // the host copy of the blocks must outlive the asynchronous upload
-        KDE_TRY_HIP(hipMemcpyAsync(&k->pairs_pilot, k->pair_count, sizeof(unsigned long long),
-                                   hipMemcpyDeviceToHost, s));
-        KDE_TRY_HIP(hipMemsetAsync(k->pair_count, 0, 64, s));
-        // one synchronisation for the uploads of this block, the two read-backs and the reset
-        KDE_TRY_HIP(hipStreamSynchronize(s));
-        k->pairs_pilot += pilot_host_pairs;
+        k->s2_range[0] = k->s2_range[1] = 1.0;
+        PISA_TRY_HIP(hipMemcpyAsync(k->scalars + 1, k->s2_range, 2 * sizeof(double), hipMemcpyHostToDevice, s));
+        PISA_TRY_HIP(hipStreamSynchronize(s));
     }
-    if (!adaptive) KDE_TRY_HIP(hipStreamSynchronize(s));
     k->cell_s2min_valid = 0;   // per-cell widest kernel: only the point evaluation needs it
-#undef KDE_FAIL
-#undef KDE_TRY
-#undef KDE_TRY_HIP
-    *out = k;
+    *out = k.release();
     return PISA_HIP_OK;
 }
 
@@ -2634,11 +2478,7 @@ PISA_API int64_t pisa_hip_kde_resident_bytes(const pisa_hip_kde *k) {
 
 PISA_API int64_t pisa_hip_kde_eval_workspace_bytes(const pisa_hip_kde *k, int64_t n_qry) {
     if (!k || n_qry < 1 || n_qry > 0x7FFFFFF0LL) return -1;
-    const int64_t m = n_qry;
-    size_t total = 2 * (size_t)k->dim * m * 8 + 2 * (size_t)m * 8 + 2 * (size_t)m * 4 + (size_t)m +
-                   (size_t)m * 4 + (size_t)m * 8 + split_bytes(m) + (size_t)m * 8 + sort_temp_bytes(m) +
-                   ((size_t)m / 128 + (size_t)std::min<int64_t>(m, 1 << 22) + 16) * sizeof(KdeBlock);
-    return (int64_t)(total + 64 * 256);
+    return (int64_t)eval_workspace_bytes(k->dim, n_qry, sort_temp_bytes(n_qry));
 }
 
 PISA_API int pisa_hip_kde_evaluate(pisa_hip_kde *k, const double *d_qry, int64_t m, void *d_work,
@@ -2650,21 +2490,7 @@ PISA_API int pisa_hip_kde_evaluate(pisa_hip_kde *k, const double *d_qry, int64_t
     Arena ar(d_work, (size_t)work_bytes);
     const int dim = k->dim;
     const KdeGeom &g = k->g;
-    // Tile size (cells per side).  A tile's queries are cut into equal workgroups of <= 256 (one
-    // query per thread); per query the cost is ~ (cells within reach of the tile) / (share of the
-    // 256 lanes in use).  Assumes the queries cover the source grid evenly (a map's bin centres).
-    int tile = 1;
-    if (g.rcut2 > 0.0) {
-        const double per_cell = (double)m / (double)k->n_cells;
-        const double reach = 1.5 * sqrt(g.rcut2) * g.inv_cell;
-        double best = INFINITY;
-        for (int t = 1; t <= 64; t++) {
-            const double cnt = per_cell * pow((double)t, dim);
-            const double util = cnt / (KDE_THREADS * ceil(cnt / KDE_THREADS));
-            const double cost = pow(t + 2.0 * reach, dim) / util;
-            if (cost < best) { best = cost; tile = t; }
-        }
-    }
+    const int tile = eval_tile(g, k->n_cells, m);
     double *qy = ar.take<double>((size_t)dim * m), *qys = ar.take<double>((size_t)dim * m);
     uint64_t *keys_a = ar.take<uint64_t>(m), *keys_b = ar.take<uint64_t>(m);
     uint32_t *idx_a = ar.take<uint32_t>(m), *idx_b = ar.take<uint32_t>(m);
@@ -2676,11 +2502,15 @@ PISA_API int pisa_hip_kde_evaluate(pisa_hip_kde *k, const double *d_qry, int64_t
     char *temp = ar.take<char>(temp_bytes);
     if (!ar.ok) return PISA_HIP_ERR_NOMEM;
     const unsigned nb = (unsigned)((m + 255) / 256);
-    KDE_D(kde_whiten_key_kernel, dim3(nb), dim3(256), 0, s, d_qry, m, g, tile, 0, qy, keys_a, idx_a);
+    dispatch<1, 2, 3>(dim, [&](auto D) {
+        hipLaunchKernelGGL(kde_whiten_key_kernel<decltype(D)::value>, dim3(nb), dim3(256), 0, s, d_qry, m, g, tile, 0, qy, keys_a, idx_a);
+    });
     size_t tb = temp_bytes;
     PISA_TRY_HIP(hipcub::DeviceRadixSort::SortPairs(temp, tb, keys_a, keys_b, idx_a, idx_b, (int)m, 0, 63, s));
-    KDE_D(kde_gather_kernel, dim3(nb), dim3(256), 0, s, qy, (const double *)nullptr, 1.0, idx_b, m, qys,
-          (double *)nullptr);
+    dispatch<1, 2, 3>(dim, [&](auto D) {
+        hipLaunchKernelGGL(kde_gather_kernel<decltype(D)::value>, dim3(nb), dim3(256), 0, s, qy, (const double *)nullptr, 1.0, idx_b, m, qys,
+                           (double *)nullptr);
+    });
     PISA_CHECK_LAUNCH("kde evaluate setup");
     std::vector<KdeBlock> blocks;
     int rc = query_blocks(keys_b, m, tile, KDE_THREADS, temp, temp_bytes, flags, starts, d_count, head_keys, blocks, s);
@@ -2708,75 +2538,9 @@ PISA_API int pisa_hip_kde_evaluate(pisa_hip_kde *k, const double *d_qry, int64_t
     PISA_TRY_HIP(hipMemsetAsync(k->pair_count, 0, 64, s));
     return PISA_HIP_OK;
 }
-#undef KDE_D
 
 // ---- evaluation on a lattice of points  x[d] = origin[d] + i_d step[d],  0 <= i_d < count[d],
 //      out[(i_0 n_1 + i_1) n_2 + i_2]  (numpy.meshgrid(indexing="ij") order)
-static int lattice_strip(const pisa_hip_kde *k, const double *step, const int64_t *count) {
-    // (rcut2 <= 138, i.e. tol >= 1e-30: the strip's middle value must stay a normal number, see the kernel)
-    if (k->dim != 2 || !(k->g.rcut2 > 0.0) || k->g.rcut2 > 138.0 || count[0] * count[1] > 0x7FFFFFF0LL) return 0;
-    const double da = k->g.U[0] * step[0];
-    if (!(da > 0.0) || !std::isfinite(da) || !(k->s2_range[1] > 0.0)) return 0;
-    static const int forced = PISA_DEV_INT("KDE_LATTICE_R", -1);
-    if (forced == 0) return 0;
-    const double lim = 50.0 / (da * sqrt(k->s2_range[1]));
-    for (int R : {32, 16, 8})
-        if ((double)R <= lim && (forced < 0 || R <= forced)) return R;
-    return 0;
-}
-
-// Sub-patch of a wavefront: sw strips of lpw consecutive lines, sw lpw = LG lanes (the wavefront's 64 / LG lane groups
-// work different shares on the same sub-patch).  A source costs one pass per sub-patch within its reach, whatever the
-// number of strips it reaches there, so the sub-patch should be as compact as the kernel discs: the expected number
-// of sub-patches a unit-bandwidth source touches (sources spread evenly over the lattice and its margin) picks sw for
-// a given LG; LG = 8 (eight shares side by side: scripts/dev/kde_pass_model.py) unless the lattice then has more
-// than 4 096 sub-patches (every sub-patch has a wavefront, partial sums and a share list of its own).
-static int64_t lattice_patches(int R, int sw, int lpw, const int64_t *count) {
-    const int64_t strips_a = (count[0] + R - 1) / R;
-    return ((strips_a + sw - 1) / sw) * ((count[1] + lpw - 1) / lpw);
-}
-
-static void lattice_shape(const pisa_hip_kde *k, int R, const double *step, const int64_t *count, int &sw_out, int &lg_out) {
-    const int strips_a = (int)((count[0] + R - 1) / R);
-    const double rp = sqrt(k->g.rcut2) / fabs(k->g.U[0] * step[0]), rl = sqrt(k->g.rcut2) / fabs(k->g.U[4] * step[1]);
-    const double n0 = (double)count[0], n1 = (double)count[1];
-    for (int lg : {8, 16, 32, 64}) {
-        int best = 1;
-        double best_cost = INFINITY;
-        for (int sw = 1; sw <= lg; sw *= 2) {
-            if (sw > 1 && sw / 2 >= strips_a) continue;
-            const int lpw = lg / sw;
-            double rows = 0.0, cols = 0.0;
-            for (int64_t j = 0; j < count[1]; j += lpw)
-                rows += std::min(1.0, (2.0 * rl + (double)std::min<int64_t>(lpw, count[1] - j)) / (n1 + 2.0 * rl));
-            for (int64_t i = 0; i < count[0]; i += (int64_t)sw * R)
-                cols += std::min(1.0, (2.0 * rp + (double)std::min<int64_t>((int64_t)sw * R, count[0] - i)) / (n0 + 2.0 * rp));
-            const double cost = rows * cols;
-            if (cost < best_cost * (1.0 - 1e-9)) { best_cost = cost; best = sw; }
-        }
-        sw_out = best;
-        lg_out = lg;
-        // (every sub-patch also has a list of the shares within reach of it, n_shares entries at most: 256 MB in all)
-        const int64_t n_shares = k->n / LAT_SHARE + 1;
-        const int64_t cap = std::min<int64_t>(4096, std::max<int64_t>(1, ((int64_t)64 << 20) / n_shares));
-        if (lattice_patches(R, best, lg / best, count) <= cap || lg == 64) return;
-    }
-}
-
-// number of wavefronts of the lattice kernel (>= one per patch)
-static int64_t lattice_waves(int R, int sw, int lpw, const int64_t *count, int64_t n) {
-    const int64_t patches = lattice_patches(R, sw, lpw, count);
-    // 6 144 = TWICE the wavefronts the chip holds of this kernel (3 per SIMD): with exactly one resident set every
-    // SIMD's three wavefronts have equal work, the oldest is served first and the youngest runs the last third of the
-    // launch alone at ~40 % issue rate; with half-size wavefronts the second set fills in as the first finishes
-    // (round 5: 278 -> 226 us per estimator; 8 192: the same)
-    static const int waves = PISA_DEV_INT("KDE_LATTICE_WAVES", 6144);
-    int64_t w = std::max<int64_t>(patches, waves);
-    w = std::min<int64_t>(w, std::max<int64_t>(patches, (int64_t)(128 << 20) / (R * sw * lpw * 8)));     // partial sums <= 128 MB
-    (void)n;   // (the plan gives a patch no more wavefronts than it has shares within reach)
-    return w;
-}
-
 PISA_API int64_t pisa_hip_kde_lattice_workspace_bytes(const pisa_hip_kde *k, const double *h_step,
                                                       const int64_t *h_count) {
     if (!k || !h_step || !h_count) return -1;
@@ -2786,15 +2550,11 @@ PISA_API int64_t pisa_hip_kde_lattice_workspace_bytes(const pisa_hip_kde *k, con
         m *= h_count[d];
     }
     const int R = lattice_strip(k, h_step, h_count);
-    if (R)
-    {
+    if (R) {
         int sw = 1, lg = 64;
-        lattice_shape(k, R, h_step, h_count, sw, lg);
-        const size_t waves = (size_t)lattice_waves(R, sw, lg / sw, h_count, k->n);
-        const size_t patches = (size_t)lattice_patches(R, sw, lg / sw, h_count);
-        return (int64_t)(((size_t)k->n + LAT_SHARE) * LAT_GREC * 8 + waves * R * lg * 8 + ((size_t)k->n / LAT_SHARE + 1) * 32 +
-                         patches * ((size_t)k->n / LAT_SHARE + 1) * 4 +   /* lists of the shares within reach of each sub-patch */
-                         (patches + 1) * 8 + 4096);
+        lattice_shape(k->g, k->n, R, h_step, h_count, sw, lg);
+        return (int64_t)lattice_workspace_bytes(k->n, R, lg, (size_t)lattice_waves(R, sw, lg / sw, h_count),
+                                                (size_t)lattice_patches(R, sw, lg / sw, h_count));
     }
     const int64_t general = pisa_hip_kde_eval_workspace_bytes(k, m);
     return general < 0 ? -1 : general + (int64_t)k->dim * m * 8 + 4096;
@@ -2838,12 +2598,12 @@ PISA_API int pisa_hip_kde_evaluate_lattice(pisa_hip_kde *k, const double *h_orig
     L.n1 = (int32_t)h_count[1];
     L.strips_a = (L.n0 + R - 1) / R;
     int sw = 1, lg = 64;
-    lattice_shape(k, R, h_step, h_count, sw, lg);
+    lattice_shape(g, k->n, R, h_step, h_count, sw, lg);
     L.sw = sw;
     L.lpw = lg / sw;
     L.n_colblk = (L.strips_a + L.sw - 1) / L.sw;
     const int n_patches = (int)lattice_patches(R, L.sw, L.lpw, h_count);
-    const int n_waves = (int)lattice_waves(R, L.sw, L.lpw, h_count, k->n);
+    const int n_waves = (int)lattice_waves(R, L.sw, L.lpw, h_count);
     const int64_t n_shares = (k->n + LAT_SHARE - 1) / LAT_SHARE;
     double *rec = ar.take<double>(((size_t)k->n + LAT_SHARE) * LAT_GREC);   // padded by a whole share of records
     double *part = ar.take<double>((size_t)n_waves * R * lg);
@@ -2862,19 +2622,16 @@ PISA_API int pisa_hip_kde_evaluate_lattice(pisa_hip_kde *k, const double *h_orig
     unsigned long long *stamps = nullptr;
 #ifdef PISA_DEV_PROBES
     static const char *stamp_path = PISA_DEV_STR("KDE_LATTICE_STAMPS");   // development: per-wavefront (start, end, steps, passes | patch)
-    if (stamp_path) {
-        PISA_TRY_HIP(hipMalloc((void **)&stamps, (size_t)n_waves * 32));
-        PISA_TRY_HIP(hipMemsetAsync(stamps, 0, (size_t)n_waves * 32, s));
-    }
+    int rc_p = stamps_begin(stamp_path, (size_t)n_waves, s, &stamps);
+    if (rc_p != PISA_HIP_OK) return rc_p;
 #endif
-#define KDE_LAT(RR, LL) hipLaunchKernelGGL((kde_lattice_kernel<RR, LL>), dim3((unsigned)n_waves), dim3(64), 0, s, L, g.rcut2, rec, k->n, lists, load, wstart, n_patches, part, k->pair_count, stamps)
-#define KDE_LAT_R(RR) do { if (lg == 8) KDE_LAT(RR, 8); else if (lg == 16) KDE_LAT(RR, 16); else if (lg == 32) KDE_LAT(RR, 32); else KDE_LAT(RR, 64); } while (0)
-    static const int twice = PISA_DEV_INT("KDE_TWICE", 0);
-    for (int rep = 0; rep < ((twice & 1) ? 2 : 1); rep++) {
-        if (R == 32) KDE_LAT_R(32); else if (R == 16) KDE_LAT_R(16); else KDE_LAT_R(8);
-    }
-#undef KDE_LAT_R
-#undef KDE_LAT
+    for (int rep = 0; rep < probe_repeats(1); rep++)
+        dispatch<32, 16, 8>(R, [&](auto RR) {
+            dispatch<8, 16, 32, 64>(lg, [&](auto LL) {
+                hipLaunchKernelGGL((kde_lattice_kernel<decltype(RR)::value, decltype(LL)::value>), dim3((unsigned)n_waves), dim3(64), 0, s,
+                                   L, g.rcut2, rec, k->n, lists, load, wstart, n_patches, part, k->pair_count, stamps);
+            });
+        });
     hipLaunchKernelGGL(kde_lattice_combine_kernel, dim3((unsigned)(n_patches * R)), dim3(256), 0, s, part, L, R, wstart, d_out);
     PISA_CHECK_LAUNCH("kde lattice kernels");
     PISA_TRY_HIP(hipMemcpyAsync(&k->pairs_eval, k->pair_count, sizeof(unsigned long long),
@@ -2882,17 +2639,9 @@ PISA_API int pisa_hip_kde_evaluate_lattice(pisa_hip_kde *k, const double *h_orig
     PISA_TRY_HIP(hipStreamSynchronize(s));
     PISA_TRY_HIP(hipMemsetAsync(k->pair_count, 0, 64, s));
 #ifdef PISA_DEV_PROBES
-    if (stamps) {
-        std::vector<unsigned long long> h((size_t)n_waves * 4);
-        PISA_TRY_HIP(hipMemcpy(h.data(), stamps, h.size() * 8, hipMemcpyDeviceToHost));
-        (void)hipFree(stamps);
-        if (FILE *f = fopen(stamp_path, "ab")) {
-            const long long hdr[4] = {(long long)n_waves, (long long)n_patches, (long long)k->n, (long long)lg};
-            fwrite(hdr, 8, 4, f);
-            fwrite(h.data(), 8, h.size(), f);
-            fclose(f);
-        }
-    }
+    const long long hdr[4] = {(long long)n_waves, (long long)n_patches, (long long)k->n, (long long)lg};
+    rc_p = stamps_dump(stamps, (size_t)n_waves, stamp_path, "ab", hdr);
+    if (rc_p != PISA_HIP_OK) return rc_p;
 #endif
     return PISA_HIP_OK;
 }
@@ -2959,11 +2708,10 @@ PISA_API int pisa_hip_kde_eval(int32_t dim, const double *d_src, const double *d
         if (rc_s) return rc_s;
     }
     dim3 block(KDE_THREADS), grid(qblocks, (unsigned)n_split);
-#define KDE_LAUNCH(DD) hipLaunchKernelGGL(kde_eval_kernel<DD>, grid, block, 0, s, d_src, d_coef, d_s2, n_src, d_qry, n_qry, c00, c01, c02, c11, c12, c22, src_chunk, dst)
-    if (dim == 1) KDE_LAUNCH(1);
-    else if (dim == 2) KDE_LAUNCH(2);
-    else KDE_LAUNCH(3);
-#undef KDE_LAUNCH
+    dispatch<1, 2, 3>(dim, [&](auto D) {
+        hipLaunchKernelGGL(kde_eval_kernel<decltype(D)::value>, grid, block, 0, s, d_src, d_coef, d_s2, n_src, d_qry, n_qry,
+                           c00, c01, c02, c11, c12, c22, src_chunk, dst);
+    });
     PISA_CHECK_LAUNCH("kde_eval_kernel");
     if (n_split > 1) {
         hipLaunchKernelGGL(kde_reduce_kernel, dim3(qblocks), dim3(256), 0, s, dst, n_split, n_qry, d_out);

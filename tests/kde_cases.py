@@ -55,9 +55,9 @@ TINY = 2.0 ** -1074
 KERNEL_FACTOR = mc.KERNEL_FACTOR
 LATTICE_LAMBDA = 3e-13
 TOLS = (1e-10, 1e-12, 1e-13, 1e-14)
-Q_CHUNK = 512               # csrc/kde.hip: queries per workgroup of the pilot
-HERMITE_MIN_SERIES = 24     # csrc/kde.hip: a series evaluated per target pays from this many sources
-EXPANSION_MIN_N = 1000      # csrc/kde.hip, pisa_hip_kde_create: no expansion below
+Q_CHUNK = 512               # csrc/kde_plan.hpp: queries per workgroup of the pilot
+HERMITE_MIN_SERIES = 24     # csrc/kde_plan.hpp: a series evaluated per target pays from this many sources
+EXPANSION_MIN_N = 1000      # csrc/kde_plan.hpp, expansion_min_n: no expansion below
 
 # family: (pilot, eval) -- worst |fp64 restatement - exact| / (eps S); `None`: the stage is not gated for the family
 G_REF = {
@@ -418,8 +418,9 @@ def match_sources(est_ys, inv_cov, mean, x):
 
 
 # ------------------------------------------------------------------ the cell grid of pisa_hip_kde_create, restated
+# (`cell_grid` and `series_order` of csrc/kde_plan.hpp; tests/test_host_kde_plan.py holds the two together on the CPU)
 def series_bound(cell, order):
-    """kde.hip: 2.3 K^2 (cell / 2)^P / sqrt(P!) of a cell's weight, K = 1.09"""
+    """`series_order` (csrc/kde_plan.hpp): 2.3 K^2 (cell / 2)^P / sqrt(P!) of a cell's weight, K = 1.09"""
     bound, fact = 2.3 * 1.09 * 1.09, 1.0
     for i in range(1, order + 1):
         bound *= 0.5 * cell
@@ -461,7 +462,7 @@ def grid_rule(x, w, bw, tol):
 
 # ------------------------------------------------------------------ the lattice kernel's launch shape, restated
 def lattice_strip(da_s, tol):
-    """strip length of `lattice_strip` (kde.hip) for da_s = da sqrt(max s2): the largest R of 32, 16, 8 with
+    """strip length of `lattice_strip` (csrc/kde_plan.hpp) for da_s = da sqrt(max s2): the largest R of 32, 16, 8 with
     R da_s <= 50, else 0 (the points are written out and evaluated one by one)"""
     if not tol > 0:
         return 0
@@ -469,7 +470,7 @@ def lattice_strip(da_s, tol):
 
 
 def lattice_shape(n, tol, u00, u11, step, count, R):
-    """(sw, LG) of `lattice_shape` (kde.hip): the lane-group width moves from 8 to 16, 32, 64 while the lattice has
+    """(sw, LG) of `lattice_shape` (csrc/kde_plan.hpp): the lane-group width moves from 8 to 16, 32, 64 while the lattice has
     more than 4096 sub-patches of LG strips"""
     r_cut = np.sqrt(2.0 * np.log(1.0 / tol))
     strips_a = (count[0] + R - 1) // R
