@@ -11,8 +11,14 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
+#include <map>
+#include <type_traits>
+#include <vector>
+
 #include "common.hpp"
 #include "prob3_device.hpp"
+#include "prob3_plan.hpp"
 
 namespace pisa {
 
@@ -158,19 +164,25 @@ __device__ __forceinline__ void mat_mul_fma(const mat3 &A, const mat3 &B, mat3 &
 // from the stage-A records `terms` of the layer's density (a pair belongs to one row, so nothing
 // is computed twice, and the records -- 2 x n_unique x 26 x n_e doubles -- stay in the L2 where
 // the amplitudes, 12-18 doubles per pair and energy, had to travel through HBM).
-// G = 0: PACKED launch.  Every workgroup has four waves and holds rows by their length -- one long
-// row split over four waves, two medium rows over two waves each, or four short rows with a
-// wave each (`blk`, built with the plan): what bounds this kernel is the dependent sequence of
-// layer matrices per wave of the longest rows (13 for a 24-layer row, ~2 us each), and
-// four-wave workgroups for EVERY row do not fit the chip at once (250 VGPRs: two workgroups per
-// CU).  Packed, the ~360 workgroups of a 200 x 100 grid are all resident and a 24-layer row has
-// four matrices per wave instead of seven.
+// G = 0: PACKED launch (prob3_plan.hpp decides all of it on the host).  Every workgroup has four waves and holds
+// rows by their length -- one long row split over four waves, two medium rows over two waves each, or four short
+// rows with a wave each: what bounds this kernel is the dependent sequence of layer matrices per wave of the
+// longest rows (13 for a 24-layer row; a step is ~460 vector instructions, ~1 us where a SIMD is shared), and
+// four-wave workgroups for EVERY row do not fit the chip at once (230 VGPRs, 54 KB of LDS: two workgroups per CU).
+// A 200 x 100 PREM-12 grid has 19 rows of >= 14 layers and 81 shorter ones: 60 row blocks per energy tile.  Its
+// fourth tile has 8 live energies; there the rows of one class (same densities in the same order, same mirrored
+// steps: 12 classes) share a wave, eight rows side by side, 13 blocks instead of 60: 386 workgroups where 480
+// issued a quarter of their instructions for 8 lanes of 64.  The workgroups are launched longest rows first
+// over all tiles; the dispatcher puts workgroup 256 + k on the CU of workgroup k, so what a long row shares its
+// SIMDs with is decided by this order (EXPERIMENTS R11-1).
 // Development build (make EXTRA=-DPISA_CHAIN_STAMPS, scripts/dev/chain_stamps.py): wall-clock stamps of lane 0 of
-// every wavefront of the packed one-point launch at seven points of the kernel.
+// every wavefront of the first (point, sign) column of the packed launch at seven points of the kernel, and the XCC,
+// shader engine, CU and SIMD it ran on.
 #ifdef PISA_CHAIN_STAMPS
 __device__ unsigned long long g_chain_stamps[8 * 4096];
-#define CSTAMP(k) do { if (G == 0 && (threadIdx.x & 63) == 0 && blockIdx.y == 0 && blockIdx.z == 0 && blockIdx.x < 1024) \
-        g_chain_stamps[8 * (blockIdx.x * 4 + (threadIdx.x >> 6)) + (k)] = wall_clock64(); } while (0)
+#define CSTAMP_SLOT (blockIdx.y + gridDim.y * blockIdx.z)
+#define CSTAMP_ON (G == 0 && (threadIdx.x & 63) == 0 && blockIdx.x == 0 && CSTAMP_SLOT < 1024)
+#define CSTAMP(k) do { if (CSTAMP_ON) g_chain_stamps[8 * (CSTAMP_SLOT * 4 + (threadIdx.x >> 6)) + (k)] = wall_clock64(); } while (0)
 #else
 #define CSTAMP(k) do {} while (0)
 #endif
@@ -188,26 +200,26 @@ prob3_chain_kernel(const CS cs, int n_e, const int32_t *__restrict__ row_start,
                     double *__restrict__ prob_nu, double *__restrict__ prob_nubar,
                     double2 *__restrict__ pepmu, const double *__restrict__ energy,
                     const int32_t *__restrict__ pair_u, const double *__restrict__ pair_dist,
-                    int n_unique, const int32_t *__restrict__ blk, int n_points, int n_tiles) {
+                    int n_unique, const int32_t *__restrict__ slots, const int2 *__restrict__ lanes, int n_slots,
+                    int n_points, int n_tiles) {
     auto MM = [](const mat3 &A_, const mat3 &B_, mat3 &C_) { mat_mul_fma(A_, B_, C_); };
     CSTAMP(0);
-    // Several points, packed launch (n_tiles > 0): a 1-D grid in which the (point, sign, energy tile)
-    // index runs FASTEST and the row-block index slowest -- the plan lists the row blocks longest rows
-    // first, so the long rows of every point, sign and tile start first and the short ones fill the tail
-    // (with several points the workgroups no longer fit the chip at once).  The fast index is rotated by
-    // the row block: consecutive workgroups go to consecutive XCDs, and without the rotation an XCD would
-    // see the same few (point, sign, tile) records from all of its CUs at the same moment.  One point:
-    // the 3-D grid (row block fastest), all workgroups resident at once.
-    const bool lin = G == 0 && n_tiles > 0;
-    const int n_yz = lin ? 2 * n_points * n_tiles : 1;
-    const int bx = lin ? (int)(blockIdx.x / n_yz) : (int)blockIdx.x;
-    const int byz = lin ? (int)((blockIdx.x + bx) % n_yz) : 0;
-    const int by = lin ? byz % (2 * n_points) : (int)blockIdx.y;
-    const int bz = lin ? byz / (2 * n_points) : (int)blockIdx.z;
-    if (!lin) n_tiles = gridDim.z;
+    // Packed launch: grid = (2 x points, slots): the (point, sign) index runs FASTEST and the slot -- a workgroup's
+    // four wave records, which name its energy tile as well (prob3_plan.hpp) -- slowest.  The plan lists the slots
+    // longest rows first, so the long rows of every point, sign and tile start first and the short ones come last:
+    // what the chip takes beyond one workgroup per CU is the short work.  The fast index is rotated by the slot:
+    // consecutive workgroups go to consecutive XCDs, and without the rotation an XCD would see the same few
+    // (point, sign) records from all of its CUs at the same moment.
+    constexpr bool PACKED = G == 0;
+    const int n2 = 2 * n_points;
+    const int bx = PACKED ? (int)(blockIdx.y + gridDim.y * blockIdx.z) : (int)blockIdx.x;
+    if (PACKED && bx >= n_slots) return;   // (the grid's last y-z plane may be partly empty)
+    const int rot = (int)blockIdx.x + bx;
+    const int by = !PACKED ? (int)blockIdx.y : ((n2 & (n2 - 1)) == 0 ? (rot & (n2 - 1)) : (rot % n2));
+    int bz = PACKED ? 0 : (int)blockIdx.z;
+    if (!PACKED) n_tiles = gridDim.z;
     const int pt = by >> 1;     // parameter point (0 in the one-point form)
     const Prob3Consts &c = cs.at(pt);
-    constexpr bool PACKED = G == 0;
     __shared__ double s_part[(PACKED ? 3 : (G > 1 ? G - 1 : 1)) * 2 * 18 * 64];  // [partial][L|R][18][lane]
     const int lane = threadIdx.x & 63;
     // wave index: uniform within a wave, which the compiler cannot see -- without this the loop
@@ -216,23 +228,41 @@ prob3_chain_kernel(const CS cs, int n_e, const int32_t *__restrict__ row_start,
     // row, group of this wave within the row, groups of the row; partial slot of a writer wave
     int jcz = bx, g = wv, Gr = G;
     int k0_blk = 0, cnt_blk = 0;
+    // ragged last tile: the wave holds several rows of one class side by side, lane = row-in-group x r + energy.
+    // Row, chain start and (per step) layer length are then per lane; density index, chain length, the pattern of
+    // mirrored steps and the step bounds are the class's and stay scalar.
+    bool ragged = false;
+    int jl = 0, k0l = 0, e_in = lane;
     if (PACKED) {
-        // (row | g << 16 | groups << 24 (-1: idle wave), first position and length of the row's chain, 0): one 16-byte
-        // scalar load instead of the code and then row_start / row_cnt behind it
-        const int4 rec = reinterpret_cast<const int4 *>(blk)[bx * 4 + wv];
+        // (unit | g << 16 | groups << 24 (-1: idle wave), first position and length of the row's chain, energy tile):
+        // one 16-byte scalar load instead of the code and then row_start / row_cnt behind it
+        const int4 rec = reinterpret_cast<const int4 *>(slots)[bx * 4 + wv];
         const int32_t code = __builtin_amdgcn_readfirstlane(rec.x);
         k0_blk = __builtin_amdgcn_readfirstlane(rec.y);
         cnt_blk = __builtin_amdgcn_readfirstlane(rec.z);
         jcz = code < 0 ? -1 : (code & 0xffff);
         g = code < 0 ? 0 : ((code >> 16) & 0xff);
         Gr = code < 0 ? 1 : ((code >> 24) & 0xff);
+        const int32_t tile = __builtin_amdgcn_readfirstlane(rec.w);
+        ragged = (tile & PROB3_RAGGED_BIT) != 0;
+        bz = tile & ~PROB3_RAGGED_BIT;
+        jl = jcz;
+        k0l = k0_blk;
+        if (ragged && jcz >= 0) {
+            const int2 lt = lanes[jcz * 64 + lane];
+            jl = lt.x < 0 ? -1 : (lt.x & 0xffff);
+            e_in = lt.x < 0 ? 0 : (lt.x >> 16);
+            k0l = lt.y;
+        }
+    } else {
+        jl = jcz;
     }
     const int part_w = PACKED ? wv - 1 : g - 1;   // where a wave with g > 0 leaves its partials
     const int part_0 = PACKED ? wv : 0;           // leader: partner h reads slot part_0 + h - 1
     const int side = by & 1;
     const bool decay = AMP == 0 ? c.decay != 0 : AMP == 2;  // full 3x3 matrices stored / formed
-    const int ie = bz * 64 + lane;
-    const bool live = ie < n_e && jcz >= 0;
+    const int ie = bz * 64 + e_in;
+    const bool live = ie < n_e && jcz >= 0 && jl >= 0;
     double *out = side == 0 ? prob_nu : prob_nubar;
     const Prob3Side &S = c.side[side];
     const int k0 = PACKED ? k0_blk : (jcz >= 0 ? row_start[jcz] : 0);
@@ -252,7 +282,8 @@ prob3_chain_kernel(const CS cs, int n_e, const int32_t *__restrict__ row_start,
             // `amp` holds the stage-A records here
             const double *r = amp + ((int64_t)((pt * 2 + side) * n_unique + pair_u[pos]) * PROB3_NF) * ns + 2 * (int64_t)ie;
             auto load = [&](int f) { return r[(int64_t)(f >> 1) * (2 * ns) + (f & 1)]; };
-            amplitude_from_terms<AMP == 2>(load, pair_dist[pos] * inv_e, A);
+            const double len = (PACKED && ragged) ? pair_dist[k0l + (pos - k0_blk)] : pair_dist[pos];
+            amplitude_from_terms<AMP == 2>(load, len * inv_e, A);
             if (AMP == 1) su3_complete(A);
             return;
         }
@@ -269,8 +300,11 @@ prob3_chain_kernel(const CS cs, int n_e, const int32_t *__restrict__ row_start,
     bool have_l = false, have_r = false;
     CSTAMP(1);
 #ifdef PISA_CHAIN_STAMPS
-    if (G == 0 && (threadIdx.x & 63) == 0 && blockIdx.y == 0 && blockIdx.z == 0 && blockIdx.x < 1024)
-        g_chain_stamps[8 * (blockIdx.x * 4 + (threadIdx.x >> 6)) + 7] = (unsigned long long)cnt | ((unsigned long long)g << 16) | ((unsigned long long)Gr << 24) | ((unsigned long long)(s1 - s0) << 32) | (jcz >= 0 ? 1ull << 48 : 0ull);
+    if (CSTAMP_ON)
+        g_chain_stamps[8 * (CSTAMP_SLOT * 4 + (threadIdx.x >> 6)) + 7] = (unsigned long long)cnt | ((unsigned long long)g << 16) | ((unsigned long long)Gr << 24) | ((unsigned long long)(s1 - s0) << 32) | (jcz >= 0 ? 1ull << 48 : 0ull) |
+            // where the wavefront runs: HW_ID bits 4..15 (SIMD, pipe, CU, shader array, shader engine) and the XCC number
+            ((unsigned long long)((__builtin_amdgcn_s_getreg((31 << 11) | 4) >> 4) & 0xfff) << 49) |
+            ((unsigned long long)(__builtin_amdgcn_s_getreg((31 << 11) | 20) & 0x7) << 61);
 #endif
     if (live && cnt > 0 && s1 > s0) {
         mat3 A, An;
@@ -315,7 +349,7 @@ prob3_chain_kernel(const CS cs, int n_e, const int32_t *__restrict__ row_start,
     __syncthreads();
     CSTAMP(3);
     if (g != 0 || !live) return;
-    chain_tail<G, AMP>(c, S, L, R, T, have_l, have_r, s_part, part_0, lane, Gr, n_steps, cnt, mid, e_major, ie, n_e, n_cz, jcz, side, n_points, pt,
+    chain_tail<G, AMP>(c, S, L, R, T, have_l, have_r, s_part, part_0, lane, Gr, n_steps, cnt, mid, e_major, ie, n_e, n_cz, jl, side, n_points, pt,
                        out, pepmu);
 }
 
@@ -402,6 +436,8 @@ static int make_consts(const pisa_hip_prob3_params *p, Prob3Consts &c) {
 using namespace pisa;
 
 // ------------------------------------------------------------ grid plan (host)
+struct LaunchLists { int32_t *d_slots, *d_lanes; int n_slots; };   // the packed chain launch for one energy count
+
 struct pisa_hip_grid_plan {
     int n_cz, n_layers, n_unique, n_pairs, n_items, n_chain;
     int32_t *d_item_u;     // [n_items] distinct-density index of the item
@@ -415,10 +451,16 @@ struct pisa_hip_grid_plan {
     double *d_amp;         // stage-AB amplitudes [2][n_pairs][18][n_e]
     int n_e_alloc;
     int32_t *d_pair_u;     // [n_pairs] distinct-density index of each pair
-    int32_t *d_blk;        // [4 * n_blk][4] packed launch, per wave: row | group << 16 | groups << 24 (-1 idle), chain start, chain length, 0
-    int n_blk;
     int chain_packed;      // 1 (default): packed chain launch; 0 (n_cz > 0xffff; development library, PISA_HIP_CHAIN_MODE=split):
                            // one row per workgroup of CHAIN_GROUPS_DEFAULT waves
+    // the packed launch (prob3_plan.hpp): a list per energy count the plan has been used with, and the one of
+    // `launch_n_e` (pointers into `launches`)
+    std::map<int, LaunchLists> *launches;
+    Prob3LayerPlan *layers;
+    Prob3PackOpts pack;
+    int32_t *d_slots;      // [n_slots][4 waves][4]
+    int32_t *d_lanes;      // [n_groups][64][2] rows and chain starts of the lanes of a ragged tile
+    int n_slots, launch_n_e;
     int32_t *d_chain_u;    // [n_chain] the same per chain entry (position in d_row_pairs)
     double *d_chain_dist;  // [n_chain] layer length per chain entry
     double *d_terms;       // stage-A records [points][2][n_unique][PROB3_NF][n_e] (AMP mode)
@@ -436,16 +478,30 @@ struct pisa_hip_grid_plan {
     int items_for_n_e;
 };
 
+static void free_launches(pisa_hip_grid_plan *p) {
+    if (!p->launches) return;
+    for (auto &kv : *p->launches) {
+        (void)hipFree(kv.second.d_slots);
+        (void)hipFree(kv.second.d_lanes);
+    }
+    p->launches->clear();
+    p->d_slots = p->d_lanes = nullptr;
+    p->n_slots = p->launch_n_e = 0;
+}
+
 PISA_API int pisa_hip_grid_plan_destroy(pisa_hip_grid_plan *p) {
     if (!p) return PISA_HIP_OK;
     void *ptrs[] = {p->d_item_u, p->d_item_p0, p->d_item_cnt, p->d_pair_dist, p->d_row_start,
                     p->d_row_cnt, p->d_row_pairs, p->d_rho, p->d_amp, p->d_pair_u, p->d_terms,
-                    p->d_chain_u, p->d_chain_dist, p->d_blk};
+                    p->d_chain_u, p->d_chain_dist};
     for (void *q : ptrs)
         if (q) (void)hipFree(q);
     if (p->d_consts) (void)hipFree(p->d_consts);
     if (p->h_consts) (void)hipHostFree(p->h_consts);
     delete[] p->h_pair_u;
+    free_launches(p);
+    delete p->launches;
+    delete p->layers;
     delete p;
     return PISA_HIP_OK;
 }
@@ -484,139 +540,84 @@ static int cut_items(pisa_hip_grid_plan *p, int n_e) {
     return rc;
 }
 
+// The slots of the packed chain launch for n_e energies, on the device.  A list is made the first time a plan sees an
+// energy count (two allocations and two blocking copies, before anything of the evaluation is queued -- like d_terms,
+// not under stream capture) and kept: a plan used with several energy counts in turn makes each list once.
+static int make_launch(pisa_hip_grid_plan *p, int n_e) {
+    auto it = p->launches->find(n_e);
+    if (it == p->launches->end()) {
+        Prob3LaunchPlan l;
+        if (!prob3_launch_plan(*p->layers, n_e, p->pack, l)) return PISA_HIP_ERR_INVALID;
+        if (p->launches->size() >= 64) free_launches(p);   // (a caller sweeping energy counts: start over)
+        LaunchLists d = {nullptr, nullptr, l.n_slots};
+        int rc = check_hip(hipMalloc(&d.d_slots, std::max<size_t>(l.slots.size(), 1) * 4), "hipMalloc");
+        if (!rc) rc = check_hip(hipMalloc(&d.d_lanes, std::max<size_t>(l.lanes.size(), 2) * 4), "hipMalloc");
+        if (!rc && !l.slots.empty()) rc = check_hip(hipMemcpy(d.d_slots, l.slots.data(), l.slots.size() * 4, hipMemcpyHostToDevice), "h2d");
+        if (!rc && !l.lanes.empty()) rc = check_hip(hipMemcpy(d.d_lanes, l.lanes.data(), l.lanes.size() * 4, hipMemcpyHostToDevice), "h2d");
+        if (rc) {
+            if (d.d_slots) (void)hipFree(d.d_slots);
+            if (d.d_lanes) (void)hipFree(d.d_lanes);
+            return rc;
+        }
+        it = p->launches->emplace(n_e, d).first;
+    }
+    p->d_slots = it->second.d_slots;
+    p->d_lanes = it->second.d_lanes;
+    p->n_slots = it->second.n_slots;
+    p->launch_n_e = n_e;
+    return PISA_HIP_OK;
+}
+
 PISA_API int pisa_hip_grid_plan_create(const double *d_densities, const double *d_distances,
                                        int32_t n_cz, int32_t n_layers,
                                        pisa_hip_grid_plan **out) {
     if (!out || n_cz < 1 || n_layers < 1 || !d_densities || !d_distances) return PISA_HIP_ERR_INVALID;
     if (n_layers > PISA_HIP_MAX_LAYERS) return PISA_HIP_ERR_LAYERS;
-    size_t n = (size_t)n_cz * n_layers;
-    double *rho = new double[n], *dist = new double[n], *pdist = new double[n + 1];
-    int32_t *pu = new int32_t[n + 1], *rstart = new int32_t[n_cz], *rcnt = new int32_t[n_cz];
-    int32_t *chain = new int32_t[n + 1], *layer_pair = new int32_t[n_layers];
-    double *uniq = new double[n + 1];
-    int nu = 0, np = 0, nc = 0;
-    int rc = check_hip(hipMemcpy(rho, d_densities, n * 8, hipMemcpyDeviceToHost), "d2h");
-    if (!rc) rc = check_hip(hipMemcpy(dist, d_distances, n * 8, hipMemcpyDeviceToHost), "d2h");
-    if (!rc) {
-        for (int r = 0; r < n_cz; r++) {
-            const double *rr = rho + (size_t)r * n_layers, *dd = dist + (size_t)r * n_layers;
-            rstart[r] = nc;
-            for (int i = 0; i < n_layers; i++) {
-                layer_pair[i] = -1;
-                if (!(dd[i] > 0.0)) continue;
-                // follow the reference's cache matches (numba_osc_kernels.py:236-249)
-                // to the layer whose matrix is actually computed
-                int cur = i;
-                double cr = rr[i], cd = dd[i];
-                while (true) {
-                    int found = -1;
-                    for (int j = 0; j < cur; j++)
-                        if (dd[j] > 0.0 && fabs(rr[j] - cr) < 1e-5 && fabs(dd[j] - cd) < 1e-5) found = j;
-                    if (found < 0) break;
-                    cur = found; cr = rr[cur]; cd = dd[cur];
-                }
-                if (cur != i) {
-                    layer_pair[i] = layer_pair[cur];  // the same matrix, stored once
-                } else {
-                    int u = -1;
-                    for (int k = 0; k < nu; k++)
-                        if (uniq[k] == cr) { u = k; break; }
-                    if (u < 0) { u = nu; uniq[nu++] = cr; }
-                    pu[np] = u;
-                    pdist[np] = cd;
-                    layer_pair[i] = np++;
-                }
-                chain[nc++] = layer_pair[i];
-            }
-            rcnt[r] = nc - rstart[r];
-        }
-    }
-    // renumber the pairs sorted by density so that an item is a run of consecutive pairs
-    int32_t *order = new int32_t[np + 1], *newid = new int32_t[np + 1];
-    double *sdist = new double[np + 1];
-    int32_t *su = new int32_t[np + 1];
-    {
-        int w = 0;
-        for (int u = 0; u < nu; u++)
-            for (int k = 0; k < np; k++)
-                if (pu[k] == u) order[w++] = k;
-        for (int k = 0; k < np; k++) { newid[order[k]] = k; sdist[k] = pdist[order[k]]; su[k] = pu[order[k]]; }
-        for (int k = 0; k < nc; k++) chain[k] = newid[chain[k]];
-    }
+    const size_t n = (size_t)n_cz * n_layers;
+    std::vector<double> rho(n), dist(n);
+    int rc = check_hip(hipMemcpy(rho.data(), d_densities, n * 8, hipMemcpyDeviceToHost), "d2h");
+    if (!rc) rc = check_hip(hipMemcpy(dist.data(), d_distances, n * 8, hipMemcpyDeviceToHost), "d2h");
     pisa_hip_grid_plan *p = nullptr;
     if (!rc) {
         p = new pisa_hip_grid_plan();
         memset(p, 0, sizeof(*p));
+        p->layers = new Prob3LayerPlan();
+        p->launches = new std::map<int, LaunchLists>();
+        Prob3LayerPlan &lp = *p->layers;
+        prob3_layer_plan(rho.data(), dist.data(), n_cz, n_layers, lp);
+        const int np = lp.n_pairs, nc = lp.n_chain;
         p->n_cz = n_cz; p->n_layers = n_layers;
-        p->n_unique = nu > 0 ? nu : 1;
+        p->n_unique = lp.n_unique;
         p->n_pairs = np;
         p->n_chain = nc;
-        p->h_pair_u = su;
-        su = nullptr;
+        p->h_pair_u = new int32_t[np + 1];
+        std::copy(lp.pair_u.begin(), lp.pair_u.end(), p->h_pair_u);
         p->fused_amp = PISA_DEV_INT("PROB3_FUSED_AMP", 1) != 0;
-        if (nu == 0) uniq[0] = 0.0;
-        size_t npa = np > 0 ? np : 1, nca = nc > 0 ? nc : 1;
-        rc = check_hip(hipMalloc(&p->d_pair_dist, npa * 8), "hipMalloc");
-        if (!rc) rc = check_hip(hipMalloc(&p->d_row_start, (size_t)n_cz * 4), "hipMalloc");
-        if (!rc) rc = check_hip(hipMalloc(&p->d_row_cnt, (size_t)n_cz * 4), "hipMalloc");
-        if (!rc) rc = check_hip(hipMalloc(&p->d_row_pairs, nca * 4), "hipMalloc");
-        if (!rc) rc = check_hip(hipMalloc(&p->d_rho, (size_t)p->n_unique * 8), "hipMalloc");
         {
-            // packed chain launch: rows by length, longest first; 4 waves per workgroup =
-            // one long row x 4 groups | two medium rows x 2 | four short rows x 1
+            // packed chain launch (prob3_plan.hpp); the development library can take every part of it back
             const char *m = PISA_DEV_STR("CHAIN_MODE");
-            p->chain_packed = (m && strcmp(m, "split") == 0) ? 0 : 1;
-            int32_t *code = new int32_t[((size_t)4 * n_cz + 4) * 4];   // per wave: code, chain start, chain length, 0
-            int nb = 0;
-            int t4 = 14, t2 = 0;  // crossed layers from which a row gets four / two waves (measured: 22.1 us; 14/6: 23.4; one row per workgroup: 24.4)
-            t4 = PISA_DEV_INT("PACK_T4", t4);
-            t2 = PISA_DEV_INT("PACK_T2", t2);
-            auto groups_of = [&](int c_) { return c_ >= t4 ? 4 : (c_ >= t2 ? 2 : 1); };
-            for (int want = 4; want >= 1; want >>= 1) {
-                int fill = 0;  // wave slots used in the open workgroup
-                for (int r = 0; r < n_cz && n_cz <= 0xffff; r++) {
-                    if (groups_of(rcnt[r]) != want) continue;
-                    for (int gi = 0; gi < want; gi++) {
-                        int32_t *w = code + (size_t)(nb * 4 + fill + gi) * 4;
-                        w[0] = r | (gi << 16) | (want << 24); w[1] = rstart[r]; w[2] = rcnt[r]; w[3] = 0;
-                    }
-                    fill += want;
-                    if (fill == 4) { nb++; fill = 0; }
-                }
-                if (fill > 0) {
-                    for (int k = fill; k < 4; k++) {
-                        int32_t *w = code + (size_t)(nb * 4 + k) * 4;
-                        w[0] = -1; w[1] = w[2] = w[3] = 0;
-                    }
-                    nb++;
-                }
-            }
-            if (n_cz > 0xffff) p->chain_packed = 0;
-            p->n_blk = nb;
-            if (!rc) rc = check_hip(hipMalloc(&p->d_blk, (size_t)(nb > 0 ? nb : 1) * 64), "hipMalloc");
-            if (!rc && nb > 0) rc = check_hip(hipMemcpy(p->d_blk, code, (size_t)nb * 64, hipMemcpyHostToDevice), "h2d");
-            delete[] code;
+            p->chain_packed = (m && strcmp(m, "split") == 0) || n_cz > PROB3_MAX_PACKED_ROWS ? 0 : 1;
+            p->pack = Prob3PackOpts();
+            p->pack.t4 = PISA_DEV_INT("PACK_T4", p->pack.t4);
+            p->pack.t2 = PISA_DEV_INT("PACK_T2", p->pack.t2);
+            p->pack.ragged = PISA_DEV_INT("PACK_RAGGED", p->pack.ragged);
+            p->pack.sorted = PISA_DEV_INT("PACK_SORTED", p->pack.sorted);
         }
-        if (!rc) rc = check_hip(hipMalloc(&p->d_chain_u, nca * 4), "hipMalloc");
-        if (!rc) rc = check_hip(hipMalloc(&p->d_chain_dist, nca * 8), "hipMalloc");
-        if (!rc && nc > 0) {
-            int32_t *cu = new int32_t[nc];
-            double *cd = new double[nc];
-            for (int k = 0; k < nc; k++) { cu[k] = p->h_pair_u[chain[k]]; cd[k] = sdist[chain[k]]; }
-            rc = check_hip(hipMemcpy(p->d_chain_u, cu, (size_t)nc * 4, hipMemcpyHostToDevice), "h2d");
-            if (!rc) rc = check_hip(hipMemcpy(p->d_chain_dist, cd, (size_t)nc * 8, hipMemcpyHostToDevice), "h2d");
-            delete[] cu; delete[] cd;
-        }
-        if (!rc) rc = check_hip(hipMalloc(&p->d_pair_u, npa * 4), "hipMalloc");
-        if (!rc && np > 0) rc = check_hip(hipMemcpy(p->d_pair_u, p->h_pair_u, (size_t)np * 4, hipMemcpyHostToDevice), "h2d");
-        if (!rc && np > 0) rc = check_hip(hipMemcpy(p->d_pair_dist, sdist, (size_t)np * 8, hipMemcpyHostToDevice), "h2d");
-        if (!rc) rc = check_hip(hipMemcpy(p->d_row_start, rstart, (size_t)n_cz * 4, hipMemcpyHostToDevice), "h2d");
-        if (!rc) rc = check_hip(hipMemcpy(p->d_row_cnt, rcnt, (size_t)n_cz * 4, hipMemcpyHostToDevice), "h2d");
-        if (!rc && nc > 0) rc = check_hip(hipMemcpy(p->d_row_pairs, chain, (size_t)nc * 4, hipMemcpyHostToDevice), "h2d");
-        if (!rc) rc = check_hip(hipMemcpy(p->d_rho, uniq, (size_t)p->n_unique * 8, hipMemcpyHostToDevice), "h2d");
+        const size_t npa = np > 0 ? np : 1, nca = nc > 0 ? nc : 1;
+        auto upload = [&](auto **dst, const auto &v, size_t n_alloc) {
+            using T = typename std::remove_reference<decltype(v)>::type::value_type;
+            if (!rc) rc = check_hip(hipMalloc(dst, n_alloc * sizeof(T)), "hipMalloc");
+            if (!rc && !v.empty()) rc = check_hip(hipMemcpy(*dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice), "h2d");
+        };
+        upload(&p->d_pair_dist, lp.pair_dist, npa);
+        upload(&p->d_pair_u, lp.pair_u, npa);
+        upload(&p->d_row_start, lp.row_start, (size_t)n_cz);
+        upload(&p->d_row_cnt, lp.row_cnt, (size_t)n_cz);
+        upload(&p->d_row_pairs, lp.row_pairs, nca);
+        upload(&p->d_chain_u, lp.chain_u, nca);
+        upload(&p->d_chain_dist, lp.chain_dist, nca);
+        upload(&p->d_rho, lp.rho, (size_t)lp.n_unique);
     }
-    delete[] rho; delete[] dist; delete[] pdist; delete[] pu; delete[] rstart; delete[] rcnt; delete[] uniq;
-    delete[] chain; delete[] layer_pair; delete[] order; delete[] newid; delete[] sdist; delete[] su;
     if (rc && p) { pisa_hip_grid_plan_destroy(p); p = nullptr; }
     *out = p;
     return rc;
@@ -629,6 +630,10 @@ static int launch_planned(const CS &cs, bool decay, int n_points, pisa_hip_grid_
                           int32_t n_e, int32_t e_major, double *d_prob_nu, double *d_prob_nubar, double *d_pepmu,
                           hipStream_t s) {
     const unsigned tiles = (unsigned)((n_e + 63) / 64);
+    if (plan->chain_packed && plan->launch_n_e != n_e) {
+        int rc = make_launch(plan, n_e);
+        if (rc) return rc;
+    }
     if (plan->n_e_terms < n_e || plan->n_pt_terms < n_points) {
         if (plan->d_terms) (void)hipFree(plan->d_terms);
         plan->d_terms = nullptr;
@@ -650,15 +655,14 @@ static int launch_planned(const CS &cs, bool decay, int n_points, pisa_hip_grid_
 #define CHAIN(G, A) hipLaunchKernelGGL((prob3_chain_kernel<G, A, CS>), cgrid, cblock, 0, s, cs, (int)n_e, plan->d_row_start, \
                        plan->d_row_cnt, plan->d_row_pairs, plan->n_cz, plan->n_pairs, plan->d_terms,              \
                        (int)e_major, d_prob_nu, d_prob_nubar, (double2 *)d_pepmu, d_energy, plan->d_chain_u,      \
-                       plan->d_chain_dist, plan->n_unique, plan->d_blk, n_points, lin_tiles)
-    int lin_tiles = 0;
-    if (plan->chain_packed && plan->n_blk > 0) {
+                       plan->d_chain_dist, plan->n_unique, plan->d_slots, (const int2 *)plan->d_lanes, plan->n_slots, \
+                       n_points, (int)tiles)
+    if (plan->chain_packed) {
+        // (point, sign) fastest, then the slots in the plan's order (y, and z beyond the grid's y limit)
+        const unsigned sy = (unsigned)std::min(plan->n_slots, 32768);
         cblock = dim3(256);
-        cgrid = dim3((unsigned)plan->n_blk, 2u * n_points, tiles);
-        if (n_points > 1) {
-            lin_tiles = (int)tiles;
-            cgrid = dim3((unsigned)plan->n_blk * 2u * n_points * tiles, 1, 1);
-        }
+        cgrid = dim3(2u * n_points, sy, (unsigned)((plan->n_slots + sy - 1) / (sy > 0 ? sy : 1)));
+        if (plan->n_slots == 0) return PISA_HIP_OK;   // (no row: cannot happen, n_cz >= 1)
         if (decay) CHAIN(0, 2); else CHAIN(0, 1);
     } else if (decay) CHAIN(CHAIN_GROUPS_DEFAULT, 2);
     else CHAIN(CHAIN_GROUPS_DEFAULT, 1);
@@ -704,7 +708,7 @@ PISA_API int pisa_hip_prob3_grid_planned(const pisa_hip_prob3_params *h_params,
     hipLaunchKernelGGL((prob3_chain_kernel<CHAIN_GROUPS_DEFAULT, 0, ConstsByValue>), cgrid, cblock, 0, s, cv, (int)n_e, plan->d_row_start,
                        plan->d_row_cnt, plan->d_row_pairs, plan->n_cz, plan->n_pairs, plan->d_amp,
                        (int)e_major, d_prob_nu, d_prob_nubar, (double2 *)d_pepmu, d_energy, plan->d_pair_u,
-                       plan->d_pair_dist, plan->n_unique, plan->d_blk, 1, 0);
+                       plan->d_pair_dist, plan->n_unique, nullptr, nullptr, 0, 1, 0);
     PISA_CHECK_LAUNCH("prob3_chain_kernel");
     return PISA_HIP_OK;
 }

@@ -1,6 +1,8 @@
-"""time stamps inside prob3_chain_kernel (library built with EXTRA=-DPISA_CHAIN_STAMPS; sign 0, energy tile 0):
+"""time stamps inside prob3_chain_kernel (library built with EXTRA=-DPISA_CHAIN_STAMPS; the workgroups with blockIdx.x = 0, one of
+the two signs of every slot, in launch order):
 per wavefront: entry, set-up done, own steps done, barrier passed, join done, final product done, stored -- in us
-relative to the first wavefront's entry (wall_clock64 = 100 MHz)"""
+relative to the first wavefront's entry (wall_clock64 = 100 MHz); then where the dispatcher put the workgroups: XCC, shader
+engine / array, CU and SIMD from HW_ID, by position in the launch"""
 import ctypes as C
 import sys
 
@@ -22,6 +24,7 @@ lib.pisa_hip_debug_chain_stamps.argtypes = [C.c_void_p]
 assert lib.pisa_hip_debug_chain_stamps(buf) == 0
 raw = np.frombuffer(buf, dtype=np.uint64).reshape(4096, 8)
 used = raw[:, 0] > 0
+wave_no = np.nonzero(used)[0]
 raw = raw[used]
 info = raw[:, 7]
 cnt = (info & 0xffff).astype(int); g = ((info >> 16) & 0xff).astype(int); Gr = ((info >> 24) & 0xff).astype(int)
@@ -46,3 +49,25 @@ for sel, lab in ((live == 1, "all live"), ((live == 1) & (Gr == 4) & (g == 0), "
 order = np.argsort(-np.nan_to_num(np.nanmax(t, axis=1)))[:6]
 for i in order:
     print("slow: layers %2d g %d/%d steps %d : %s" % (cnt[i], g[i], Gr[i], steps[i], " ".join("%6.2f" % v for v in t[i])))
+
+# placement: one line per workgroup (its first wavefront), in launch order; the grid is (2 signs, slots), so slot s is
+# workgroup 2 s or 2 s + 1 of the launch
+hw = ((info >> 49) & 0xfff).astype(int)
+xcc = ((info >> 61) & 0x7).astype(int)
+simd, cu, sh, se = hw & 3, (hw >> 4) & 0xf, (hw >> 8) & 1, (hw >> 9) & 7
+place = {}
+for i in range(len(raw)):
+    place.setdefault(int(wave_no[i]) // 4, []).append((int(wave_no[i]) % 4, xcc[i], se[i], sh[i], cu[i], simd[i], cnt[i], t[i, 0], np.nanmax(t[i])))
+cus = {}
+print("== placement: slot, XCC, SE, SH, CU, SIMD of its waves, layers, entry us, end us; then the slots that shared its CU")
+for slot in sorted(place):
+    w = sorted(place[slot])
+    key = (w[0][1], w[0][2], w[0][3], w[0][4])
+    cus.setdefault(key, []).append(slot)
+for slot in sorted(place):
+    w = sorted(place[slot])
+    key = (w[0][1], w[0][2], w[0][3], w[0][4])
+    print("slot %3d xcc %d se %d sh %d cu %2d simd %s layers %2d entry %6.2f end %6.2f  cu shared with %s" % (
+        slot, *key, "".join(str(x[5]) for x in w), max(x[6] for x in w), min(x[7] for x in w), max(x[8] for x in w),
+        [s_ for s_ in cus[key] if s_ != slot]))
+print("CUs used by these workgroups: %d; XCCs: %s" % (len(cus), sorted({k[0] for k in cus})))
