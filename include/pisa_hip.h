@@ -830,6 +830,27 @@ int pisa_hip_metric_matrix_best(int32_t kind, int32_t form, const double *d_data
                                 int64_t n_templates, int64_t n_bins, double *d_best, int32_t *d_arg, double *d_at,
                                 int32_t *d_status, void *stream);
 
+/* The pseudo-data of such an ensemble drawn on the device: d_out[t][b] ~ Poisson(d_mu[b]) for n_trials trials of
+ * one template row, where the reference draws Map.fluctuate("poisson") per trial from a RandomState
+ * (pisa/core/map.py:1098-1254).  A counter-based generator cannot reproduce that stream: this one has its own
+ * definition (Philox4x32-10, Salmon et al., SC'11) and a statistical validation in the place of a bit comparison.
+ *     key     = (seed & 0xffffffff, seed >> 32)
+ *     counter = (bin b, first_trial + t, stream_id, attempt j)
+ * One block of four words gives two doubles in [0, 1): u = ((w_a >> 5) * 2^26 + (w_b >> 6)) * 2^-53 from (w0, w1)
+ * and (w2, w3).  0 < mu < 10: inversion by sequential search on the first double of attempt 0 (at most 255 steps);
+ * mu >= 10: Hoermann's transformed rejection (PTRS), one block per attempt, j = 0, 1, ... until a draw is accepted;
+ * mu = 0 gives 0, a NaN mean gives NaN and draws nothing.
+ * The value of entry (t, b) depends on (seed, stream_id, first_trial + t, b, d_mu[b]) only: not on n_trials, on how
+ * the caller splits the trials over calls through first_trial, or on the launch geometry.  stream_id separates the
+ * ensembles of one seed (analysis/ensemble.py passes the index of the true point).
+ * d_status[1] (int32, zeroed by the caller) is set to PISA_HIP_ERR_NEGATIVE for a negative mean, for +inf and for
+ * a mean above 2^52; such an entry is NaN.
+ * PISA_HIP_ERR_INVALID before any device access: a NULL pointer, a size outside [1, 2^31 - 1],
+ * first_trial + n_trials > 2^32. */
+int pisa_hip_poisson_fluctuate(const double *d_mu, int64_t n_bins, int64_t n_trials, uint64_t seed,
+                               uint32_t stream_id, uint32_t first_trial, double *d_out /* [n_trials][n_bins] */,
+                               int32_t *d_status, void *stream);
+
 /* ----------------------------------------------- binned post-histogram stages */
 
 /* d_out[i] = d_x[i] * d_scale[i] * scalar  (d_scale may be NULL = 1), then, if

@@ -4,9 +4,17 @@ frequentist analyses build on it (sensitivity bands, goodness of fit, Feldman-Co
 The reference has no such module: an analysis loops `Map.fluctuate` + `Map.metric_total` (pisa/core/map.py:1098-1254,
 1572-1604) over trials and hypotheses.  Here the templates of a grid are made once (`TemplateGrid.from_maker`: one
 sweep of the events per `MAX_POINTS` points where the pipeline allows it), the pseudo-data of a true point are drawn
-on the host from the reference's `RandomState` stream (`pseudo_data`), and the T x K metric values come from one
-launch (`kernels.metric_matrix`), or never exist at all (`kernels.metric_matrix_best`: best, arg and the value at the
-true point per trial).
+(`pseudo_data`), and the T x K metric values come from one launch (`kernels.metric_matrix`), or never exist at all
+(`kernels.metric_matrix_best`: best, arg and the value at the true point per trial).
+
+Two generators draw the pseudo-data.  `generator="host"` (the default) is the reference's `RandomState` stream: trial
+t is the t-th `Map.fluctuate("poisson")`, drawn by scipy on the host and uploaded.  `generator="device"` is the
+counter-based generator of csrc/fluctuate.hip (`kernels.poisson_fluctuate`: Philox4x32-10, inversion below a mean of
+10 and Hoermann's PTRS from there on): the draws are made where the metric kernels read them and never visit the
+host.  It cannot reproduce the reference's stream, so it has its own definition, restated draw for draw
+in tests/fluctuate_cases.py and validated statistically there.  Its entry (trial, bin) depends on (seed, stream = index
+of the true point, trial number, bin, mean) alone, so the result of `feldman_cousins` does not depend on how the
+trials are chunked.
 
 Nuisance parameters are profiled ONLY as far as they are dimensions of the grid: `delta_metric` takes the best value
 over the grid's points, no minimiser runs per trial.  A free parameter that is not a dimension of the grid stays at
@@ -15,14 +23,17 @@ the value it had when the grid was made.
 The batch evaluator is an argument (`solver=`, default `DeviceSolver`): an object with
     matrix(kind, data, expected, sigma2) -> [T, K]
     best(kind, data, expected, sigma2, offset, k0) -> (best [T], arg [T], at [T])
-so that everything around the kernels can run with a numpy restatement (tests/ensemble_cases.py).
+and, for `generator="device"`,
+    draw(mu [B], n_trials, seed, stream, first_trial=0) -> [n_trials, B]
+so that everything around the kernels can run with a numpy restatement (tests/ensemble_cases.py,
+tests/fluctuate_cases.py).
 """
 import math
 
 import numpy as np
 
-__all__ = ["METRICS", "DeviceSolver", "TemplateGrid", "grid_points", "pseudo_data", "metric_matrix", "delta_metric",
-           "critical_values", "feldman_cousins", "accepted"]
+__all__ = ["METRICS", "GENERATORS", "DeviceSolver", "TemplateGrid", "grid_points", "pseudo_data", "metric_matrix",
+           "delta_metric", "critical_values", "feldman_cousins", "accepted"]
 
 METRICS = ("llh", "poisson_llh", "chi2", "mod_chi2")      # kernels.METRIC_KIND
 _MAXIMISED = ("llh", "poisson_llh")
@@ -65,6 +76,12 @@ class DeviceSolver:
         from pisa_amd import kernels as K
 
         return self._run(K.metric_matrix_best, kind, (data, expected, sigma2, offset), k0=int(k0))
+
+    def draw(self, mu, n_trials, seed, stream, first_trial=0):
+        """[n_trials, B] Poisson draws of the row `mu` on the device (`kernels.poisson_fluctuate`)"""
+        from pisa_amd import kernels as K
+
+        return K.poisson_fluctuate(self._up(mu).reshape(-1), n_trials, seed, stream=stream, first_trial=first_trial)
 
 
 def _rescaled(param, value):
@@ -215,11 +232,31 @@ class TemplateGrid:
         return grid
 
 
-def pseudo_data(grid, k, n_trials, random_state=None):
-    """[n_trials, B] pseudo-data of template k: trial t is exactly the t-th `Map.fluctuate("poisson",
-    random_state=rs)` of that template from ONE `RandomState` rs (one `scipy.stats.poisson.rvs` call on the tiled
-    expectation consumes the stream in the same order; NaN bins stay NaN and draw nothing).  Drawn on the host: a
-    counter-based generator on the device cannot reproduce the reference's stream."""
+GENERATORS = ("host", "device")
+CHUNK_BYTES = 1 << 30          # pseudo-data of the device generator alive at a time
+
+
+def _check_generator(generator, solver):
+    if generator not in GENERATORS:
+        raise ValueError("ensemble: generator '%s' not among %s" % (generator, list(GENERATORS)))
+    if generator == "device" and not hasattr(solver, "draw"):
+        raise ValueError("ensemble: generator='device' needs a solver with draw(mu, n_trials, seed, stream, "
+                         "first_trial); %s has none" % type(solver).__name__)
+
+
+def pseudo_data(grid, k, n_trials, random_state=None, generator="host", solver=None):
+    """[n_trials, B] pseudo-data of template k.
+    generator="host": trial t is exactly the t-th `Map.fluctuate("poisson", random_state=rs)` of that template from
+    ONE `RandomState` rs (one `scipy.stats.poisson.rvs` call on the tiled expectation consumes the stream in the same
+    order; NaN bins stay NaN and draw nothing).  Drawn on the host, a host array: the reference's stream.
+    generator="device": what `solver.draw(grid.hist[k], n_trials, seed, stream=k)` returns (from `DeviceSolver`, the
+    default, a device tensor: `kernels.poisson_fluctuate`), seed = `random_state` or one draw from it if it is a
+    RandomState, as in `feldman_cousins`.  A counter-based generator of its own definition, NOT the reference's
+    stream; NaN bins stay NaN and a zero bin stays 0 here as well."""
+    if generator != "host":
+        solver = DeviceSolver() if solver is None else solver
+        _check_generator(generator, solver)
+        return solver.draw(grid.hist[k], int(n_trials), _base_seed(random_state), stream=int(k))
     from scipy.stats import poisson
 
     rs = random_state if isinstance(random_state, np.random.RandomState) else np.random.RandomState(random_state)
@@ -300,26 +337,41 @@ def _base_seed(random_state):
     return seed
 
 
-def feldman_cousins(grid, metric, n_trials, cl=(0.6827, 0.90), random_state=None, true_points=None, solver=None):
+def feldman_cousins(grid, metric, n_trials, cl=(0.6827, 0.90), random_state=None, true_points=None, solver=None,
+                    generator="host", chunk_bytes=CHUNK_BYTES):
     """Critical values of the Feldman-Cousins ordering on the grid: for every true point k0 (default: all), n_trials
     pseudo-data maps of template k0, their `delta_metric` at k0 and `critical_values` -> crit [len(true_points),
-    len(cl)].  Every true point draws from its own RandomState([seed, k0]) (seed: `random_state`, or one draw from it
-    if it is a RandomState), so a subset of true points reproduces the full run's rows.  Nuisance parameters are
-    profiled only as far as they are dimensions of the grid (module docstring)."""
+    len(cl)].  seed: `random_state`, or one draw from it if it is a RandomState.
+    generator="host": every true point draws from its own RandomState([seed, k0]) (`pseudo_data`) and the data are
+    uploaded; generator="device": every true point is the stream k0 of the solver's `draw` under the one seed, the
+    draws go from `draw` into `delta_metric` where they are, in chunks of whole trials of at most `chunk_bytes` of
+    pseudo-data (trial numbers carried through `first_trial`: the result does not depend on the chunks).  Either way
+    a subset of true points reproduces the full run's rows.  Nuisance parameters are profiled only as far as they are
+    dimensions of the grid (module docstring)."""
     _check_metric(metric)
     if n_trials < 1:
         raise ValueError("feldman_cousins: n_trials >= 1")
+    solver = DeviceSolver() if solver is None else solver
+    _check_generator(generator, solver)
     seed = _base_seed(random_state)
     points = range(len(grid)) if true_points is None else [int(k) for k in true_points]
     for k0 in points:
         if not 0 <= k0 < len(grid):
             raise ValueError("feldman_cousins: true point %d outside the grid's %d points" % (k0, len(grid)))
-    solver = DeviceSolver() if solver is None else solver
     cl = np.atleast_1d(np.asarray(cl, dtype=np.float64))
     crit = np.empty((len(points), cl.size))
+    rows = max(1, int(chunk_bytes) // (8 * grid.n_bins))
     for i, k0 in enumerate(points):
-        data = pseudo_data(grid, k0, n_trials, np.random.RandomState([seed, k0]))
-        crit[i] = critical_values(delta_metric(data, grid, metric, k0, solver), cl)
+        if generator == "host":
+            data = pseudo_data(grid, k0, n_trials, np.random.RandomState([seed, k0]))
+            delta = delta_metric(data, grid, metric, k0, solver)
+        else:
+            parts = []
+            for first in range(0, n_trials, rows):
+                data = solver.draw(grid.hist[k0], min(rows, n_trials - first), seed, stream=k0, first_trial=first)
+                parts.append(delta_metric(data, grid, metric, k0, solver))
+            delta = np.concatenate(parts)
+        crit[i] = critical_values(delta, cl)
     return crit
 
 

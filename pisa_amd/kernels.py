@@ -660,6 +660,39 @@ def metric_matrix_best(kind, data, expected, sigma2=None, offset=None, k0=0, for
     return best, arg, at
 
 
+def poisson_fluctuate(mu, n_trials, seed, stream=0, first_trial=0, out=None, status=None):
+    """Poisson pseudo-data of one template row drawn on the device (`pisa_hip_poisson_fluctuate`): mu [B] float64
+    device vector -> [n_trials, B] float64 device tensor, entry (t, b) ~ Poisson(mu[b]) from the counter-based
+    generator of csrc/fluctuate.hip.  The entry depends on (seed, stream, first_trial + t, b, mu[b]) alone: calls
+    that split the trials through `first_trial` give the rows of one call.  seed in [0, 2^64), stream and
+    first_trial in [0, 2^32).  A NaN mean gives NaN, a zero mean 0; a negative, infinite or > 2^52 mean raises
+    ValueError."""
+    if mu.dim() != 1 or mu.dtype != F8:
+        raise ValueError("poisson_fluctuate: mu is a float64 vector [n_bins]")
+    seed, stream, first_trial, n_trials = int(seed), int(stream), int(first_trial), int(n_trials)
+    if not 0 <= seed < 2 ** 64:
+        raise ValueError("poisson_fluctuate: the seed %d is outside [0, 2^64)" % seed)
+    if not (0 <= stream < 2 ** 32 and 0 <= first_trial < 2 ** 32):
+        raise ValueError("poisson_fluctuate: stream and first_trial are in [0, 2^32)")
+    mu = mu.contiguous()
+    n_bins = mu.shape[0]
+    dev = mu.device
+    if out is None:
+        out = torch.empty((max(n_trials, 0), n_bins), dtype=F8, device=dev)
+    elif tuple(out.shape) != (n_trials, n_bins) or out.dtype != F8 or not out.is_contiguous():
+        raise ValueError("poisson_fluctuate: out is a contiguous float64 [n_trials, n_bins]")
+    own_status = status is None
+    if own_status:
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+    # (a size outside [1, 2^31 - 1] or trial numbers beyond 2^32 reach the library: PISA_HIP_ERR_INVALID, nothing
+    # is launched)
+    _lib.check(_lib.lib().pisa_hip_poisson_fluctuate(_ptr(mu), n_bins, n_trials, seed, stream, first_trial, _ptr(out),
+                                                     _ptr(status), _stream()))
+    if own_status:
+        _check_status(status)
+    return out
+
+
 # --------------------------------------------------- generalized Poisson-gamma likelihood
 def _check_status(status):
     st = int(status.item())

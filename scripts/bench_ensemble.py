@@ -7,10 +7,16 @@
     and reduced; a form whose launch takes more than half a second is timed over 5 launches (`launches` says so).
     The product form's fraction of the fp64 peak counts 2 T K B flop (llh: 4 T K B, its two products);
   * the same work as a loop over `kernels.metric` on a 100 x 100 corner (all there was before these kernels);
-  * end to end: one `feldman_cousins` with T = 1e4 on a 30 x 30 grid of 128-bin templates, its wall time split into
-    host drawing, upload and kernels.
+  * the draw kernel alone (`kernels.poisson_fluctuate`), output resident, at (T, B) = (1e4, 128) and (1e4, 4800), with the
+    draws per second and the share of the HBM bandwidth its 8 T B bytes of stores come to;
+  * end to end: `feldman_cousins` with T = 1e4 on a 30 x 30 grid of 128-bin templates, its wall time split into
+    drawing, upload and kernels.  `--generator host` (the default) draws on the host, `device` on the device (no upload:
+    the draws are made where the kernels read them), `both` runs the two alternately in this one process.  After a
+    warm-up run the measurement is repeated `--e2e-reps` times: median wall time, every run's, and the split of the
+    median run.
 
-    python scripts/bench_ensemble.py [--reps 20] [--skip-e2e] [--skip-kernels] [--forms direct,product] [--true-points N]
+    python scripts/bench_ensemble.py [--reps 20] [--skip-e2e] [--skip-kernels] [--skip-draw] [--forms direct,product]
+                                     [--true-points N] [--generator host|device|both] [--e2e-reps 3]
 """
 import argparse
 import json
@@ -97,11 +103,43 @@ def kernel_lines(reps, forms=("direct", "product")):
         del d, e
 
 
+HBM_PEAK_TBS = 8.0           # MI355X: 8 TB/s
+
+
+def draw_lines(reps):
+    """the draw kernel alone: means of the end-to-end templates (50 - 150 counts per bin: the rejection sampler)"""
+    import torch
+
+    from pisa_amd import kernels as K
+
+    dev = K.device()
+    for n_t, n_b in ((10 ** 4, 128), (10 ** 4, 4800)):
+        mu = torch.from_numpy(_templates(1, n_b, seed=3)[0]).to(dev)
+        out = torch.empty((n_t, n_b), dtype=torch.float64, device=dev)
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+        res = _time(lambda: K.poisson_fluctuate(mu, n_t, 1, stream=7, out=out, status=status), reps)
+        assert int(status.item()) == 0
+        sec = res["ms_median"] * 1e-3
+        print(json.dumps(dict(workload="draw_kernel", T=n_t, B=n_b, mean_of_mu=round(float(mu.mean().item()), 2), **res,
+                              gdraws_per_s=round(n_t * n_b / sec / 1e9, 3),
+                              frac_of_hbm_peak=round(8.0 * n_t * n_b / sec / 1e12 / HBM_PEAK_TBS, 4))), flush=True)
+
+
 class _TimedSolver:
-    """`DeviceSolver` with a synchronise after the upload and after the launches: their wall times, summed"""
+    """`DeviceSolver` with a synchronise after the upload, after the launches and after a draw on the device: their wall
+    times, summed"""
 
     def __init__(self, solver, timings):
         self.solver, self.timings = solver, timings
+
+    def draw(self, mu, n_trials, seed, stream, first_trial=0):
+        import torch
+
+        t0 = time.perf_counter()
+        out = self.solver.draw(mu, n_trials, seed, stream, first_trial)
+        torch.cuda.synchronize()
+        self.timings["draw"] = self.timings.get("draw", 0.0) + (time.perf_counter() - t0)
+        return out
 
     def best(self, kind, data, expected, sigma2=None, offset=None, k0=0):
         import torch
@@ -117,9 +155,32 @@ class _TimedSolver:
         return out
 
 
-def e2e_line(n_trials, true_points):
+def _e2e_once(en, grid, n_trials, points, generator):
+    """one timed `feldman_cousins` -> (wall, timings, crit)"""
     import torch
 
+    timings = {"draw": 0.0, "upload": 0.0, "kernels": 0.0}
+    draw = en.pseudo_data
+
+    def timed_draw(*a, **k):
+        t0 = time.perf_counter()
+        out = draw(*a, **k)
+        timings["draw"] += time.perf_counter() - t0
+        return out
+
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    en.pseudo_data = timed_draw
+    try:
+        crit = en.feldman_cousins(grid, "llh", n_trials, random_state=1, true_points=points,
+                                  solver=_TimedSolver(en.DeviceSolver(), timings), generator=generator)
+    finally:
+        en.pseudo_data = draw
+    torch.cuda.synchronize()
+    return time.perf_counter() - t0, timings, crit
+
+
+def e2e_lines(n_trials, true_points, generator, reps):
     from pisa_amd import kernels as K
     from pisa_amd.analysis import ensemble as en
 
@@ -127,32 +188,24 @@ def e2e_line(n_trials, true_points):
     hist = _templates(side * side, n_b, seed=3)
     grid = en.TemplateGrid(K.to_device(hist), K.to_device(0.0 * hist), np.zeros((side * side, 2)), None, None, "llh")
     grid._host["hist"] = hist
-    timings = {}
-    draw = en.pseudo_data
-
-    def timed_draw(*a, **k):
-        t0 = time.perf_counter()
-        out = draw(*a, **k)
-        timings["draw"] = timings.get("draw", 0.0) + (time.perf_counter() - t0)
-        return out
-
     points = None if true_points is None else list(range(0, side * side, max(1, side * side // true_points)))[:true_points]
-    en.feldman_cousins(grid, "llh", 64, random_state=1, true_points=[0])       # (first launches, allocator)
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    en.pseudo_data = timed_draw
-    try:
-        crit = en.feldman_cousins(grid, "llh", n_trials, random_state=1, true_points=points,
-                                  solver=_TimedSolver(en.DeviceSolver(), timings))
-    finally:
-        en.pseudo_data = draw
-    torch.cuda.synchronize()
-    wall = time.perf_counter() - t0
-    print(json.dumps(dict(workload="feldman_cousins", grid="%dx%d" % (side, side), B=n_b, T=n_trials, metric="llh",
-                          true_points=crit.shape[0], wall_s=round(wall, 3), draw_s=round(timings["draw"], 3),
-                          upload_s=round(timings["upload"], 3), kernels_s=round(timings["kernels"], 3),
-                          other_s=round(wall - timings["draw"] - timings["upload"] - timings["kernels"], 3),
-                          crit90_mean=round(float(crit[:, 1].mean()), 6))), flush=True)
+    generators = ("host", "device") if generator == "both" else (generator,)
+    warm = points[:2] if points is not None else [0, 1]
+    for g in generators:                   # (first launches, allocator, scipy's first call: the timed shape, two points)
+        en.feldman_cousins(grid, "llh", n_trials, random_state=1, true_points=warm, generator=g)
+    runs = {g: [] for g in generators}
+    for _ in range(reps):                  # the generators alternate: what else the machine does meets both alike
+        for g in generators:
+            runs[g].append(_e2e_once(en, grid, n_trials, points, g))
+    for g in generators:
+        walls = [r[0] for r in runs[g]]
+        wall, timings, crit = sorted(runs[g], key=lambda r: r[0])[len(walls) // 2]
+        print(json.dumps(dict(workload="feldman_cousins", generator=g, grid="%dx%d" % (side, side), B=n_b, T=n_trials,
+                              metric="llh", true_points=crit.shape[0], runs=len(walls), wall_s=round(wall, 3),
+                              wall_s_all=[round(w, 3) for w in walls], draw_s=round(timings["draw"], 3),
+                              upload_s=round(timings["upload"], 3), kernels_s=round(timings["kernels"], 3),
+                              other_s=round(wall - timings["draw"] - timings["upload"] - timings["kernels"], 3),
+                              crit90_mean=round(float(crit[:, 1].mean()), 6))), flush=True)
 
 
 def main():
@@ -163,14 +216,20 @@ def main():
     ap.add_argument("--forms", default="direct,product", help="the kernel forms to time")
     ap.add_argument("--skip-e2e", action="store_true")
     ap.add_argument("--skip-kernels", action="store_true")
+    ap.add_argument("--skip-draw", action="store_true")
+    ap.add_argument("--generator", choices=("host", "device", "both"), default="host",
+                    help="who draws the pseudo-data of the end-to-end run")
+    ap.add_argument("--e2e-reps", type=int, default=3, help="timed end-to-end runs per generator (median)")
     args = ap.parse_args()
     import torch
 
     torch.cuda.set_device(0)
     if not args.skip_kernels:
         kernel_lines(args.reps, tuple(args.forms.split(",")))
+    if not args.skip_draw:
+        draw_lines(args.reps)
     if not args.skip_e2e:
-        e2e_line(int(args.trials), args.true_points)
+        e2e_lines(int(args.trials), args.true_points, args.generator, args.e2e_reps)
 
 
 if __name__ == "__main__":
