@@ -1151,6 +1151,59 @@ int pisa_hip_hypersurface_fit(const double *h_x, const int32_t *h_form, int32_t 
                               double *d_x, double *d_coef, double *d_cov, double *d_chi2, double *d_loss,
                               int32_t *d_n_iter, int32_t *d_status, void *stream);
 
+/* ------------------------------------------------------- profiled trial ensembles */
+/* pisa_hip_metric_matrix with J = n_params linearised nuisance displacements fitted per (trial, template) pair
+ * (csrc/profile.hip; DESIGN.md section 4, "Profiled trial ensembles"):
+ *     mu_b(eta) = E[k][b] + R[k][0][b] eta_0 + ... + R[k][J-1][b] eta_(J-1)      (ascending j, every product rounded)
+ *     Phi(eta)  = sum_b phi(d_b, mu_b, s2_b) + w sum_j (ips_j (eta_j + c[k][j]))^2
+ * phi = mu - d ln mu, w = 1/2 for _LLH and _POISSON_LLH; phi = (d - mu)^2 / mu for _CHI2 and (d - mu)^2 / (s2 + mu)
+ * for _MOD_CHI2, w = 1.  eta_hat minimises Phi on the domain mu_b >= 1e-10 for every bin with a non-zero response:
+ * a damped Newton iteration from eta = 0 with the exact gradient and Hessian, at most max_iter steps.  The reported
+ * entry is the metric of pisa_hip_metric_matrix (_ENSEMBLE_DIRECT) of data row t against the template row
+ * mu(eta_hat), then the prior terms w (ips_j (eta_j + c_j))^2 joined in ascending j (subtracted for the llh kinds,
+ * added for the chi2 kinds) with the rounding errors kept and added last.
+ *   d_response [n_templates][J][n_bins] with response_stride_k >= J n_bins doubles between templates, or ONE
+ *       [J][n_bins] block shared by all templates with response_stride_k = 0;
+ *   d_inv_prior_sigma [J] (NULL: no priors; an entry 0: no prior on that parameter);
+ *   d_center [n_templates][J] the value of parameter j at template k minus its prior mean (NULL: 0);
+ *   d_value [T][K]; d_eta [T][K][J] (may be NULL); d_n_iter [T][K] Newton steps taken (may be NULL);
+ *   d_pair_status [T][K] bit flags: _NOT_CONVERGED (max_iter steps, or a step that 40 halvings did not make
+ *       acceptable), _BOUNDARY (the last step was cut by the domain), _NOT_POSDEF (the Hessian has no Cholesky
+ *       factor), _START_OUTSIDE (a responding bin with E < 1e-10: eta stays 0).  A flagged pair still holds the
+ *       metric at its last accepted eta.
+ * The bits of entry (t, k) depend on row t of d_data and row k of d_expected / d_sigma2 / d_response / d_center
+ * alone: not on the number of rows, their order, or how a caller splits them over calls.
+ * d_status[1] (int32, zeroed by the caller): PISA_HIP_ERR_NEGATIVE for a negative datum or expectation.
+ * PISA_HIP_ERR_INVALID before any device access: an unknown kind, n_params outside [1, _MAX_PARAMS], max_iter
+ * outside [0, 4096], a size outside [1, 2^31 - 1], more than 2^26 (strip of 64 trials, template) pairs for the
+ * full output or strips for the reduced one (a caller splits the trials or the templates: no entry changes), a response stride that is neither 0 nor >= J n_bins, a NULL pointer where one is required, _MOD_CHI2
+ * without d_sigma2, k0 outside [0, n_templates). */
+#define PISA_HIP_PROFILE_MAX_PARAMS 8
+#define PISA_HIP_PROFILE_NOT_CONVERGED 1
+#define PISA_HIP_PROFILE_BOUNDARY 2
+#define PISA_HIP_PROFILE_NOT_POSDEF 4
+#define PISA_HIP_PROFILE_START_OUTSIDE 8
+int pisa_hip_profiled_metric_matrix(int32_t kind, const double *d_data, const double *d_expected,
+                                    const double *d_sigma2, const double *d_response, int64_t response_stride_k,
+                                    const double *d_inv_prior_sigma, const double *d_center, int32_t n_params,
+                                    int32_t max_iter, int64_t n_trials, int64_t n_templates, int64_t n_bins,
+                                    double *d_value, double *d_eta, int32_t *d_n_iter, int32_t *d_pair_status,
+                                    int32_t *d_status, void *stream);
+
+/* The same entries (+ d_offset[k] per column, may be NULL) reduced per trial as pisa_hip_metric_matrix_best does,
+ * the [T][K] matrix never written: d_best / d_arg / d_at, the fitted displacements at both columns d_eta_best and
+ * d_eta_at [T][J], and d_trial_status [T] = the pair status at arg OR the pair status at k0.  Bit for bit the
+ * reduction of the full output, whatever the sizes.  Where the trials are too few to fill the device the templates
+ * are split over workgroups and a second launch joins the ranges through a buffer that belongs to the library (one
+ * per process, as the preparation buffers of pisa_hip_metric_matrix): calls on different streams must not overlap. */
+int pisa_hip_profiled_metric_matrix_best(int32_t kind, const double *d_data, const double *d_expected,
+                                         const double *d_sigma2, const double *d_response, int64_t response_stride_k,
+                                         const double *d_inv_prior_sigma, const double *d_center,
+                                         const double *d_offset, int32_t k0, int32_t n_params, int32_t max_iter,
+                                         int64_t n_trials, int64_t n_templates, int64_t n_bins, double *d_best,
+                                         int32_t *d_arg, double *d_at, double *d_eta_best, double *d_eta_at,
+                                         int32_t *d_trial_status, int32_t *d_status, void *stream);
+
 /* ------------------------------------------------------- raw device memory */
 /* Thin wrappers so hosts without torch (a cgo/ctypes binding of the
  * reference) can own device buffers. */

@@ -16,24 +16,37 @@ in tests/fluctuate_cases.py and validated statistically there.  Its entry (trial
 of the true point, trial number, bin, mean) alone, so the result of `feldman_cousins` does not depend on how the
 trials are chunked.
 
-Nuisance parameters are profiled ONLY as far as they are dimensions of the grid: `delta_metric` takes the best value
-over the grid's points, no minimiser runs per trial.  A free parameter that is not a dimension of the grid stays at
-the value it had when the grid was made.
+Nuisance parameters are profiled in two ways.  A dimension of the grid is profiled by `delta_metric` taking the best
+value over the grid's points.  A free parameter that is NOT a dimension of the grid is fitted per (trial, point) pair
+where a `NuisanceResponse` is passed (`response=`): the template of point k is linearised in those parameters around
+the point, mu = hist[k] + sum_j response[k, j] eta_j with the binwise gradients of `DistributionMaker._fisher_templates`
+(`NuisanceResponse.from_maker`), and the displacements eta are fitted by the damped Newton iteration of
+csrc/profile.hip (`kernels.profiled_metric_matrix`, at most 8 parameters, Gaussian priors included; DESIGN.md §4,
+"Profiled trial ensembles") -- T x K small convex fits in one launch, no minimiser on the host.  The fit is exact for
+a parameter the template is linear in (aeff_scale) and a first-order profile otherwise; the fitted eta come back so
+that a caller can hold them against the parameters' ranges (no bounds are applied).  Without `response` a parameter
+that is not a dimension of the grid stays at the value it had when the grid was made, and every call gives what it
+gave before the argument existed.
 
 The batch evaluator is an argument (`solver=`, default `DeviceSolver`): an object with
     matrix(kind, data, expected, sigma2) -> [T, K]
     best(kind, data, expected, sigma2, offset, k0) -> (best [T], arg [T], at [T])
 and, for `generator="device"`,
     draw(mu [B], n_trials, seed, stream, first_trial=0) -> [n_trials, B]
+and, for `response=`,
+    profiled_matrix(kind, data, expected, response, sigma2, inv_prior_sigma, center, max_iter)
+        -> dict(value [T, K], eta [T, K, J], n_iter [T, K], status [T, K])
+    profiled_best(kind, data, expected, response, sigma2, inv_prior_sigma, center, offset, k0, max_iter)
+        -> dict(best [T], arg [T], at [T], eta_best [T, J], eta_at [T, J], status [T])
 so that everything around the kernels can run with a numpy restatement (tests/ensemble_cases.py,
-tests/fluctuate_cases.py).
+tests/fluctuate_cases.py, tests/profile_cases.py).
 """
 import math
 
 import numpy as np
 
-__all__ = ["METRICS", "GENERATORS", "DeviceSolver", "TemplateGrid", "grid_points", "pseudo_data", "metric_matrix",
-           "delta_metric", "critical_values", "feldman_cousins", "accepted"]
+__all__ = ["METRICS", "GENERATORS", "DeviceSolver", "TemplateGrid", "NuisanceResponse", "grid_points", "pseudo_data",
+           "metric_matrix", "delta_metric", "critical_values", "feldman_cousins", "accepted"]
 
 METRICS = ("llh", "poisson_llh", "chi2", "mod_chi2")      # kernels.METRIC_KIND
 _MAXIMISED = ("llh", "poisson_llh")
@@ -76,6 +89,23 @@ class DeviceSolver:
         from pisa_amd import kernels as K
 
         return self._run(K.metric_matrix_best, kind, (data, expected, sigma2, offset), k0=int(k0))
+
+    def profiled_matrix(self, kind, data, expected, response, sigma2=None, inv_prior_sigma=None, center=None,
+                        max_iter=32):
+        from pisa_amd import kernels as K
+
+        data, expected, response, sigma2, ips, center = [self._up(a) for a in (data, expected, response, sigma2,
+                                                                               inv_prior_sigma, center)]
+        return K.profiled_metric_matrix(kind, data, expected, response, sigma2, ips, center, max_iter=max_iter)
+
+    def profiled_best(self, kind, data, expected, response, sigma2=None, inv_prior_sigma=None, center=None,
+                      offset=None, k0=0, max_iter=32):
+        from pisa_amd import kernels as K
+
+        data, expected, response, sigma2, ips, center, offset = [self._up(a) for a in (
+            data, expected, response, sigma2, inv_prior_sigma, center, offset)]
+        return K.profiled_metric_matrix_best(kind, data, expected, response, sigma2, ips, center, offset, int(k0),
+                                             max_iter=max_iter)
 
     def draw(self, mu, n_trials, seed, stream, first_trial=0):
         """[n_trials, B] Poisson draws of the row `mu` on the device (`kernels.poisson_fluctuate`)"""
@@ -232,6 +262,110 @@ class TemplateGrid:
         return grid
 
 
+class NuisanceResponse:
+    """The linear response of the templates of a grid to J <= 8 nuisance parameters that are not dimensions of the
+    grid: `names` [J]; `response` [K, J, B] (or [J, B], shared by all points) the change of the template per unit of
+    the parameter (its magnitude in the parameter's units); `inv_prior_sigma` [J] = 1 / stddev of a Gaussian prior,
+    0 without one; `center` [K, J] the parameter's value at point k minus its prior mean; `prior_at_point` [K] the
+    named parameters' share of `priors_penalty` at point k, which the drivers take out of `grid.penalty` (the fit
+    adds the prior at the FITTED value: no prior is counted twice); `values` [K, J] the parameters' values at the
+    points, to which a fitted displacement eta is added.  Arrays of whatever kind the solver takes."""
+
+    def __init__(self, names, response, inv_prior_sigma=None, center=None, prior_at_point=None, values=None,
+                 max_iter=32):
+        self.names = tuple(names)
+        self.response = response
+        n_j = len(self.names)
+        if len(response.shape) not in (2, 3) or int(response.shape[-2]) != n_j:
+            raise ValueError("NuisanceResponse: response is [K, %d, B] or [%d, B] for %d names" % (n_j, n_j, n_j))
+        if not 1 <= n_j <= 8:
+            raise ValueError("NuisanceResponse: 1 to 8 parameters, got %d" % n_j)
+        self.inv_prior_sigma = np.zeros(n_j) if inv_prior_sigma is None else np.asarray(inv_prior_sigma, np.float64)
+        self.center = None if center is None else np.asarray(center, dtype=np.float64)
+        self.prior_at_point = None if prior_at_point is None else np.asarray(prior_at_point, dtype=np.float64)
+        self.values = None if values is None else np.asarray(values, dtype=np.float64)
+        self.max_iter = int(max_iter)
+        if self.inv_prior_sigma.shape != (n_j,) or np.any(self.inv_prior_sigma < 0):
+            raise ValueError("NuisanceResponse: inv_prior_sigma holds one value >= 0 per parameter")
+
+    def offset(self, grid):
+        """grid.penalty without the named parameters' share, or None if that is zero everywhere"""
+        off = grid.penalty if self.prior_at_point is None else grid.penalty - self.prior_at_point
+        return off if np.any(off != 0.0) else None
+
+    @classmethod
+    def from_maker(cls, hypo_maker, grid, names, test_vals, max_iter=32):
+        """The response of `grid`'s templates to the free parameters `names` of `hypo_maker`: at every point of
+        `grid.points` the gradients (T_hi - T_lo) / (hi - lo) of `hypo_maker._fisher_templates` (one call per
+        parameter, every other parameter at the point's own value; one sweep of the events each where the pipeline
+        has the replayable shape) between the point's own value + test_vals[name][0] and + test_vals[name][1]
+        (displacements: numbers in the parameter's units, or quantities).  1 / sigma and
+        the mean are read from a Gaussian prior; a uniform prior (or none) gives 0; any other kind raises
+        ValueError.  On return the free parameters hold the values they had at entry."""
+        from pisa_amd import kernels as K
+
+        names = list(names)
+        free = hypo_maker.params.free
+        for name in names:
+            if name not in free.names:
+                raise ValueError("NuisanceResponse: '%s' is not a free parameter (%s)" % (name, list(free.names)))
+        if len(set(names)) != len(names):
+            raise ValueError("NuisanceResponse: a parameter is named twice")
+        ips, means = np.zeros(len(names)), np.zeros(len(names))
+        for j, name in enumerate(names):
+            prm = free[name]
+            kind = "uniform" if prm.prior is None else prm.prior.kind
+            if kind == "gaussian":
+                ips[j] = 1.0 / float(prm.prior.stddev.to(prm._units).magnitude)
+                means[j] = float(prm.prior.mean.to(prm._units).magnitude)
+            elif kind != "uniform":
+                raise ValueError("NuisanceResponse: the %s prior of '%s' is not quadratic; only Gaussian and uniform "
+                                 "priors can be profiled" % (kind, name))
+        n = len(grid)
+        saved = [p.value for p in free]
+        resp = np.empty((n, len(names), grid.n_bins))
+        values, at_point = np.zeros((n, len(names))), np.zeros(n)
+        pipes = hypo_maker._pipelines
+        try:
+            for k in range(n):
+                hypo_maker._set_rescaled_free_params(grid.points[k])
+                tv = {}
+                for j, name in enumerate(names):
+                    prm = hypo_maker.params[name]
+                    at_point[k] += prm.prior_penalty(grid.metric)
+                    here = prm.value
+                    values[k, j] = float(here.m_as(prm._units))
+                    tv[name] = [here + (d if hasattr(d, "m_as") else d * here.units) for d in test_vals[name]]
+                    lo, hi = (t.m_as(prm._units) for t in tv[name])
+                    if not lo != hi:
+                        raise ValueError("NuisanceResponse: the two test values of '%s' coincide" % name)
+                    tv[name] = [t.to(prm._units) for t in tv[name]]
+                for j, name in enumerate(names):
+                    # one parameter at a time from the point itself: `_fisher_templates` leaves a parameter at its
+                    # last test value while it moves the later ones, which would shift their gradients
+                    hypo_maker._set_rescaled_free_params(grid.points[k])
+                    resp[k, j] = hypo_maker._fisher_templates([name], {name: tv[name]})["grad"].reshape(-1)
+        except BaseException:
+            if len(pipes) == 1 and getattr(pipes[0], "_plan", None) is not None:
+                plan, pipes[0]._plan = pipes[0]._plan, None
+                plan.invalidate()
+            raise
+        finally:
+            hypo_maker.set_free_params(saved)
+        center = np.where(ips[None, :] > 0, values - means[None, :], 0.0)
+        return cls(names, K.to_device(resp), ips, center, at_point, values, max_iter)
+
+
+def _check_response(response, grid, solver, what):
+    if not hasattr(solver, "profiled_matrix") or not hasattr(solver, "profiled_best"):
+        raise ValueError("ensemble: response= needs a solver with profiled_matrix and profiled_best; %s has none"
+                         % type(solver).__name__)
+    shape = tuple(response.response.shape)
+    if shape[-1] != grid.n_bins or (len(shape) == 3 and shape[0] != len(grid)):
+        raise ValueError("%s: the response does not belong to this grid (%s against %d points, %d bins)"
+                         % (what, shape, len(grid), grid.n_bins))
+
+
 GENERATORS = ("host", "device")
 CHUNK_BYTES = 1 << 30          # pseudo-data of the device generator alive at a time
 
@@ -282,34 +416,60 @@ def _data_rows(data):
     return a if a.ndim == 2 else a.reshape(1, -1)
 
 
-def metric_matrix(data, grid, metric, with_penalty=True, solver=None):
+def metric_matrix(data, grid, metric, with_penalty=True, solver=None, response=None):
     """[T, K]: `Map.metric_total(template k, metric)` of every data row (+ the priors penalty of point k).  A device
-    tensor where the solver returns one, else a host array."""
+    tensor where the solver returns one, else a host array.  With `response` (a `NuisanceResponse`) every entry is
+    profiled over the response's parameters: the metric at the fitted displacements with their prior terms, + the
+    penalty of the point's other parameters."""
     _check_metric(metric)
     solver = DeviceSolver() if solver is None else solver
-    m = solver.matrix(metric, _data_rows(data), grid.hist, grid.sigma2_for(metric))
-    if with_penalty and np.any(grid.penalty != 0.0):
+    if response is None:
+        m = solver.matrix(metric, _data_rows(data), grid.hist, grid.sigma2_for(metric))
+        penalty = grid.penalty if np.any(grid.penalty != 0.0) else None
+    else:
+        _check_response(response, grid, solver, "metric_matrix")
+        m = solver.profiled_matrix(metric, _data_rows(data), grid.hist, response.response, grid.sigma2_for(metric),
+                                   response.inv_prior_sigma, response.center, response.max_iter)["value"]
+        penalty = response.offset(grid)
+    if with_penalty and penalty is not None:
         if hasattr(m, "cpu"):
             from pisa_amd import kernels as K
 
-            m = m + K.to_device(grid.penalty)[None, :]
+            m = m + K.to_device(penalty)[None, :]
         else:
-            m = m + grid.penalty[None, :]
+            m = m + penalty[None, :]
     return m
 
 
-def delta_metric(data, grid, metric, k0, solver=None):
+def delta_metric(data, grid, metric, k0, solver=None, response=None, return_info=False):
     """[T] host array: per data row the distance of point k0 from the best point of the grid, penalties included --
     best - at for the llh metrics, at - best for the chi2 metrics (>= 0; no factor of 2 is applied).  The T x K
-    matrix is never written (`pisa_hip_metric_matrix_best`)."""
+    matrix is never written (`pisa_hip_metric_matrix_best`).  With `response` both values are profiled over the
+    response's parameters (`pisa_hip_profiled_metric_matrix_best`); `return_info=True` then returns (delta, info) with
+    info = dict(flagged: the number of trials whose pair at the best point or at k0 carries a status flag, status
+    [T], arg [T], eta_best and eta_at [T, J]: the fitted displacements at both points)."""
     _check_metric(metric)
     if not 0 <= int(k0) < len(grid):
         raise ValueError("delta_metric: k0 = %s outside the grid's %d points" % (k0, len(grid)))
     solver = DeviceSolver() if solver is None else solver
-    offset = grid.penalty if np.any(grid.penalty != 0.0) else None
-    best, _, at = solver.best(metric, _data_rows(data), grid.hist, grid.sigma2_for(metric), offset, int(k0))
-    best, at = _host(best), _host(at)
-    return best - at if metric in _MAXIMISED else at - best
+    if response is None:
+        if return_info:
+            raise ValueError("delta_metric: return_info belongs to response=")
+        offset = grid.penalty if np.any(grid.penalty != 0.0) else None
+        best, _, at = solver.best(metric, _data_rows(data), grid.hist, grid.sigma2_for(metric), offset, int(k0))
+        best, at = _host(best), _host(at)
+        return best - at if metric in _MAXIMISED else at - best
+    _check_response(response, grid, solver, "delta_metric")
+    out = solver.profiled_best(metric, _data_rows(data), grid.hist, response.response, grid.sigma2_for(metric),
+                               response.inv_prior_sigma, response.center, response.offset(grid), int(k0),
+                               response.max_iter)
+    best, at = _host(out["best"]), _host(out["at"])
+    delta = best - at if metric in _MAXIMISED else at - best
+    if not return_info:
+        return delta
+    status = _host(out["status"])
+    return delta, dict(flagged=int(np.count_nonzero(status)), status=status, arg=_host(out["arg"]),
+                       eta_best=_host(out["eta_best"]), eta_at=_host(out["eta_at"]))
 
 
 def critical_values(delta, cl):
@@ -338,7 +498,7 @@ def _base_seed(random_state):
 
 
 def feldman_cousins(grid, metric, n_trials, cl=(0.6827, 0.90), random_state=None, true_points=None, solver=None,
-                    generator="host", chunk_bytes=CHUNK_BYTES):
+                    generator="host", chunk_bytes=CHUNK_BYTES, response=None):
     """Critical values of the Feldman-Cousins ordering on the grid: for every true point k0 (default: all), n_trials
     pseudo-data maps of template k0, their `delta_metric` at k0 and `critical_values` -> crit [len(true_points),
     len(cl)].  seed: `random_state`, or one draw from it if it is a RandomState.
@@ -346,14 +506,28 @@ def feldman_cousins(grid, metric, n_trials, cl=(0.6827, 0.90), random_state=None
     uploaded; generator="device": every true point is the stream k0 of the solver's `draw` under the one seed, the
     draws go from `draw` into `delta_metric` where they are, in chunks of whole trials of at most `chunk_bytes` of
     pseudo-data (trial numbers carried through `first_trial`: the result does not depend on the chunks).  Either way
-    a subset of true points reproduces the full run's rows.  Nuisance parameters are profiled only as far as they are
-    dimensions of the grid (module docstring)."""
+    a subset of true points reproduces the full run's rows.  Without `response` nuisance parameters are profiled only
+    as far as they are dimensions of the grid (module docstring).  With `response` (a `NuisanceResponse`) every
+    distance is profiled over the response's parameters and the return value is (crit, info), info = dict(flagged
+    [len(true_points)]: per true point the number of trials whose pair at the best point or at the true point carries
+    a status flag of the fit)."""
     _check_metric(metric)
     if n_trials < 1:
         raise ValueError("feldman_cousins: n_trials >= 1")
     solver = DeviceSolver() if solver is None else solver
     _check_generator(generator, solver)
+    if response is not None:
+        _check_response(response, grid, solver, "feldman_cousins")
     seed = _base_seed(random_state)
+    flagged = []
+
+    def distances(data, k0):
+        if response is None:
+            return delta_metric(data, grid, metric, k0, solver)
+        delta, info = delta_metric(data, grid, metric, k0, solver, response, return_info=True)
+        flagged[-1] += info["flagged"]
+        return delta
+
     points = range(len(grid)) if true_points is None else [int(k) for k in true_points]
     for k0 in points:
         if not 0 <= k0 < len(grid):
@@ -362,23 +536,26 @@ def feldman_cousins(grid, metric, n_trials, cl=(0.6827, 0.90), random_state=None
     crit = np.empty((len(points), cl.size))
     rows = max(1, int(chunk_bytes) // (8 * grid.n_bins))
     for i, k0 in enumerate(points):
+        flagged.append(0)
         if generator == "host":
             data = pseudo_data(grid, k0, n_trials, np.random.RandomState([seed, k0]))
-            delta = delta_metric(data, grid, metric, k0, solver)
+            delta = distances(data, k0)
         else:
             parts = []
             for first in range(0, n_trials, rows):
                 data = solver.draw(grid.hist[k0], min(rows, n_trials - first), seed, stream=k0, first_trial=first)
-                parts.append(delta_metric(data, grid, metric, k0, solver))
+                parts.append(distances(data, k0))
             delta = np.concatenate(parts)
         crit[i] = critical_values(delta, cl)
-    return crit
+    if response is None:
+        return crit
+    return crit, dict(flagged=np.array(flagged, dtype=np.int64))
 
 
-def accepted(data_map, grid, metric, crit, solver=None):
+def accepted(data_map, grid, metric, crit, solver=None, response=None):
     """boolean [K]: point k is inside the confidence region of the observed map -- its `delta_metric` at k (one row
     of the matrix, penalties included, against the row's best) is <= crit[k] ([K]: one confidence level of
-    `feldman_cousins` over all points)"""
+    `feldman_cousins` over all points).  `response`: as in `metric_matrix`, for critical values made with it."""
     _check_metric(metric)
     crit = np.asarray(crit, dtype=np.float64)
     if crit.shape != (len(grid),):
@@ -386,6 +563,6 @@ def accepted(data_map, grid, metric, crit, solver=None):
     rows = _data_rows(data_map)
     if rows.shape[0] != 1:
         raise ValueError("accepted: one observed map")
-    m = _host(metric_matrix(rows, grid, metric, True, solver))[0]
+    m = _host(metric_matrix(rows, grid, metric, True, solver, response))[0]
     delta = m.max() - m if metric in _MAXIMISED else m - m.min()
     return delta <= crit

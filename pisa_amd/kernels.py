@@ -693,6 +693,98 @@ def poisson_fluctuate(mu, n_trials, seed, stream=0, first_trial=0, out=None, sta
     return out
 
 
+def _profile_args(what, kind, data, expected, response, sigma2, inv_prior_sigma, center, max_iter):
+    if kind not in METRIC_KIND:
+        raise ValueError("%s: metric '%s' not among %s" % (what, kind, sorted(METRIC_KIND)))
+    if data.dim() != 2 or expected.dim() != 2 or data.dtype != F8 or expected.dtype != F8:
+        raise ValueError("%s: data is [n_trials, n_bins] and expected [n_templates, n_bins], both float64" % what)
+    if sigma2 is not None and (sigma2.shape != expected.shape or sigma2.dtype != F8):
+        raise ValueError("%s: sigma2 has the shape and dtype of expected" % what)
+    if kind == "mod_chi2" and sigma2 is None:
+        raise ValueError("%s: mod_chi2 needs sigma2" % what)
+    n_k, n_b = expected.shape
+    if response.dtype != F8 or response.dim() not in (2, 3) or response.shape[-1] != n_b or (
+            response.dim() == 3 and response.shape[0] != n_k):
+        raise ValueError("%s: response is float64 [n_templates, n_params, n_bins], or [n_params, n_bins] shared by "
+                         "all templates" % what)
+    n_j = response.shape[-2]
+    if not 1 <= n_j <= _lib.PROFILE_MAX_PARAMS:
+        raise ValueError("%s: %d nuisance parameters, 1 to %d are fitted" % (what, n_j, _lib.PROFILE_MAX_PARAMS))
+    if inv_prior_sigma is not None and (inv_prior_sigma.shape != (n_j,) or inv_prior_sigma.dtype != F8):
+        raise ValueError("%s: inv_prior_sigma is float64 [n_params]" % what)
+    if center is not None and (center.shape != (n_k, n_j) or center.dtype != F8):
+        raise ValueError("%s: center is float64 [n_templates, n_params]" % what)
+    if int(max_iter) < 0:
+        raise ValueError("%s: max_iter >= 0" % what)
+    data, expected, response = data.contiguous(), expected.contiguous(), response.contiguous()
+    sigma2 = None if sigma2 is None else sigma2.contiguous()
+    inv_prior_sigma = None if inv_prior_sigma is None else inv_prior_sigma.contiguous()
+    center = None if center is None else center.contiguous()
+    stride = n_j * n_b if response.dim() == 3 else 0
+    if data.shape[1] != n_b:
+        raise ValueError("%s: data has %d bins, expected %d" % (what, data.shape[1], n_b))
+    return data, expected, response, sigma2, inv_prior_sigma, center, stride, data.shape[0], n_k, n_b, n_j
+
+
+def profiled_metric_matrix(kind, data, expected, response, sigma2=None, inv_prior_sigma=None, center=None,
+                           max_iter=32, want_eta=True, status=None):
+    """`metric_matrix` with linearised nuisance parameters fitted per (trial, template) pair
+    (`pisa_hip_profiled_metric_matrix`): the template of pair (t, k) is expected[k] + sum_j response[k, j]
+    eta_j with eta minimising the metric's own convex objective plus the Gaussian priors (inv_prior_sigma_j (eta_j +
+    center[k, j]))^2.  data [T, B], expected / sigma2 [K, B], response [K, J, B] or [J, B] (shared), inv_prior_sigma
+    [J], center [K, J]: float64 device tensors.  -> dict(value [T, K], eta [T, K, J] (None unless want_eta), n_iter
+    [T, K] int32, status [T, K] int32: the `_lib.PROFILE_*` bit flags; a flagged pair holds the metric at its last
+    accepted eta).  A negative datum or expectation raises ValueError."""
+    (data, expected, response, sigma2, ips, center, stride, n_t, n_k, n_bins, n_j) = _profile_args(
+        "profiled_metric_matrix", kind, data, expected, response, sigma2, inv_prior_sigma, center, max_iter)
+    dev = data.device
+    value = torch.empty((n_t, n_k), dtype=F8, device=dev)
+    eta = torch.empty((n_t, n_k, n_j), dtype=F8, device=dev) if want_eta else None
+    n_iter = torch.empty((n_t, n_k), dtype=torch.int32, device=dev)
+    pair_status = torch.empty((n_t, n_k), dtype=torch.int32, device=dev)
+    own_status = status is None
+    if own_status:
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+    _lib.check(_lib.lib().pisa_hip_profiled_metric_matrix(
+        METRIC_KIND[kind], _ptr(data), _ptr(expected), _ptr(sigma2), _ptr(response), stride, _ptr(ips), _ptr(center),
+        n_j, int(max_iter), n_t, n_k, n_bins, _ptr(value), _ptr(eta), _ptr(n_iter), _ptr(pair_status), _ptr(status),
+        _stream()))
+    if own_status:
+        _check_status(status)
+    return dict(value=value, eta=eta, n_iter=n_iter, status=pair_status)
+
+
+def profiled_metric_matrix_best(kind, data, expected, response, sigma2=None, inv_prior_sigma=None, center=None,
+                                offset=None, k0=0, max_iter=32, status=None):
+    """the matrix of `profiled_metric_matrix` (+ offset [K] per column) reduced per trial without being written
+    (`pisa_hip_profiled_metric_matrix_best`) -> dict(best [T], arg [T] int32, at [T]: column k0, eta_best and eta_at
+    [T, J]: the fitted displacements at both columns, status [T] int32: the flags of the pair at arg OR those of
+    the pair at k0), bit for bit the reduction of the full output"""
+    (data, expected, response, sigma2, ips, center, stride, n_t, n_k, n_bins, n_j) = _profile_args(
+        "profiled_metric_matrix_best", kind, data, expected, response, sigma2, inv_prior_sigma, center, max_iter)
+    dev = data.device
+    if offset is not None:
+        if offset.shape != (n_k,) or offset.dtype != F8:
+            raise ValueError("profiled_metric_matrix_best: offset is float64 [n_templates]")
+        offset = offset.contiguous()
+    best = torch.empty(n_t, dtype=F8, device=dev)
+    arg = torch.empty(n_t, dtype=torch.int32, device=dev)
+    at = torch.empty(n_t, dtype=F8, device=dev)
+    eta_best = torch.empty((n_t, n_j), dtype=F8, device=dev)
+    eta_at = torch.empty((n_t, n_j), dtype=F8, device=dev)
+    trial_status = torch.empty(n_t, dtype=torch.int32, device=dev)
+    own_status = status is None
+    if own_status:
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+    _lib.check(_lib.lib().pisa_hip_profiled_metric_matrix_best(
+        METRIC_KIND[kind], _ptr(data), _ptr(expected), _ptr(sigma2), _ptr(response), stride, _ptr(ips), _ptr(center),
+        _ptr(offset), int(k0), n_j, int(max_iter), n_t, n_k, n_bins, _ptr(best), _ptr(arg), _ptr(at), _ptr(eta_best),
+        _ptr(eta_at), _ptr(trial_status), _ptr(status), _stream()))
+    if own_status:
+        _check_status(status)
+    return dict(best=best, arg=arg, at=at, eta_best=eta_best, eta_at=eta_at, status=trial_status)
+
+
 # --------------------------------------------------- generalized Poisson-gamma likelihood
 def _check_status(status):
     st = int(status.item())

@@ -103,6 +103,50 @@ def kernel_lines(reps, forms=("direct", "product")):
         del d, e
 
 
+def profiled_lines(n_params, reps):
+    """`profiled_metric_matrix_best` with J = n_params fitted nuisance displacements per pair, every kind, against the
+    unprofiled direct reduced form of the same run; iteration counts from the full output on the first trials.
+    Executed flops: per bin of a sweep 2 J (mu) + 2 J (its reach) + 2 J (gradient) + J + J (J + 1) (Hessian) + 20 (the
+    terms of phi, a transcendental counted as one), sweeps = Newton steps + 1 (halved steps not counted), + one sweep
+    of 2 J + 10 for the value."""
+    import torch
+
+    from pisa_amd import kernels as K
+
+    dev = K.device()
+    J = int(n_params)
+    for n_t, n_k, n_b in ((10 ** 4, 10 ** 2, 128), (10 ** 5, 10 ** 3, 128)):
+        e_host = _templates(n_k, n_b)
+        rs = np.random.RandomState(1)
+        x = (np.arange(n_b) + 0.5) / n_b
+        r_host = 0.05 * np.cos((np.arange(J)[:, None] + 1) * np.pi * x[None, :])[None] * e_host[:, None, :]
+        mu = e_host + np.einsum("kjb,kj->kb", r_host, 0.5 * rs.randn(n_k, J))
+        d = torch.from_numpy(rs.poisson(np.maximum(mu, 1.0)[rs.randint(0, n_k, n_t)]).astype(np.float64)).to(dev)
+        e, r = torch.from_numpy(e_host).to(dev), torch.from_numpy(r_host).to(dev)
+        s2 = 0.1 * e
+        ips = torch.ones(J, dtype=torch.float64, device=dev)
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+        n_head = min(n_t, 256 * 10 ** 2 // n_k * 8)
+        for kind in ("llh", "poisson_llh", "chi2", "mod_chi2"):
+            sig = s2 if kind == "mod_chi2" else None
+            head = K.profiled_metric_matrix(kind, d[:n_head], e, r, sig, ips, want_eta=False, status=status)
+            it = head["n_iter"].double()
+            flagged = int((head["status"] != 0).sum().item())
+            plain = _time(lambda: K.metric_matrix_best(kind, d, e, sig, k0=n_k // 2, form="direct", status=status), reps)
+            res = _time(lambda: K.profiled_metric_matrix_best(kind, d, e, r, sig, ips, k0=n_k // 2, status=status), reps)
+            per_bin = 2 * J + 2 * J + 2 * J + J + J * (J + 1) + 20
+            flop = float(n_t) * n_k * n_b * ((float(it.mean().item()) + 1.0) * per_bin + 2 * J + 10)
+            tflops = flop / (res["ms_median"] * 1e-3) / 1e12
+            print(json.dumps(dict(workload="profiled_kernel", T=n_t, K=n_k, B=n_b, J=J, kind=kind, output="reduced", **res,
+                                  ms_unprofiled_direct=plain["ms_median"],
+                                  ratio_to_unprofiled=round(res["ms_median"] / plain["ms_median"], 2),
+                                  iter_mean=round(float(it.mean().item()), 3), iter_max=int(it.max().item()),
+                                  flagged_of_head=flagged, head_pairs=int(it.numel()), tflops=round(tflops, 3),
+                                  frac_of_fp64_vector_peak=round(tflops / FP64_PEAK_TFLOPS, 4))), flush=True)
+        assert int(status.item()) == 0
+        del d, e, r
+
+
 HBM_PEAK_TBS = 8.0           # MI355X: 8 TB/s
 
 
@@ -220,12 +264,16 @@ def main():
     ap.add_argument("--generator", choices=("host", "device", "both"), default="host",
                     help="who draws the pseudo-data of the end-to-end run")
     ap.add_argument("--e2e-reps", type=int, default=3, help="timed end-to-end runs per generator (median)")
+    ap.add_argument("--profiled", type=int, default=0, metavar="J",
+                    help="also time the profiled reduced form with J fitted nuisance parameters (1 to 8)")
     args = ap.parse_args()
     import torch
 
     torch.cuda.set_device(0)
     if not args.skip_kernels:
         kernel_lines(args.reps, tuple(args.forms.split(",")))
+    if args.profiled:
+        profiled_lines(args.profiled, args.reps)
     if not args.skip_draw:
         draw_lines(args.reps)
     if not args.skip_e2e:
