@@ -830,6 +830,35 @@ int pisa_hip_metric_matrix_best(int32_t kind, int32_t form, const double *d_data
                                 int64_t n_templates, int64_t n_bins, double *d_best, int32_t *d_arg, double *d_at,
                                 int32_t *d_status, void *stream);
 
+/* The same matrix for the metrics that account for finite MC statistics (csrc/ensemble_mc.hip):
+ *     d_out[t][k] = nansum_b w(kind; d_data[t][b], d_expected[k][b], d_sigma2[k][b])
+ * for kind = PISA_HIP_METRIC_CORRECT_CHI2, _MCLLH_MEAN, _MCLLH_EFF and _CONV_LLH, w the per-bin value of
+ * pisa_hip_metric for that kind with every rule kept (the expectation clipped to SMALL_POS, the mixture's Poisson
+ * branch at sigma2 == 0, conv_llh's clips, its 101 shifted nodes, the sum opened at the first positive f_x and
+ * max(SMALL_POS, .) under both logarithms).  Whatever depends on a template row or a data row alone is computed once
+ * per row by a preparation launch, not once per pair; conv_llh's second term norm_conv_poisson(d, d, s) is taken as
+ * what it is on the real numbers, exp(log_poisson(d, d)).  Every sum over bins is one compensated chain in ascending
+ * order.  d_data [n_trials][n_bins], d_expected and d_sigma2 (required) [n_templates][n_bins], all finite.
+ * The bits of entry (t, k) depend on row t of d_data and row k of d_expected / d_sigma2 only: not on the number of
+ * rows, their position or how the caller splits trials or templates over calls.
+ * d_status[1] (int32, zeroed by the caller) is set to PISA_HIP_ERR_NEGATIVE for a negative d_sigma2 (every kind) and
+ * for a negative datum or expectation (the two mcllh kinds; correct_chi2 and conv_llh only clip).
+ * PISA_HIP_ERR_INVALID before any device access: any other kind, a size outside [1, 2^31 - 1], more than 65535 * 16
+ * templates for the full matrix, (n_trials + n_templates) * n_bins > 256 * (2^31 - 1), a NULL pointer (d_sigma2
+ * included; d_offset may be NULL), k0 outside [0, n_templates).
+ * The preparation buffers belong to the library, one set per process: calls on different streams must not overlap. */
+int pisa_hip_metric_matrix_mc(int32_t kind, const double *d_data, const double *d_expected, const double *d_sigma2,
+                              int64_t n_trials, int64_t n_templates, int64_t n_bins, double *d_out,
+                              int32_t *d_status, void *stream);
+
+/* Reduced per trial as pisa_hip_metric_matrix_best reduces: best = max over k of d_out[t][k] + d_offset[k] for the
+ * three llh kinds, min for correct_chi2; the smallest k that attains it; the value at column k0.  Bit for bit the
+ * reduction of pisa_hip_metric_matrix_mc. */
+int pisa_hip_metric_matrix_mc_best(int32_t kind, const double *d_data, const double *d_expected,
+                                   const double *d_sigma2, const double *d_offset, int32_t k0, int64_t n_trials,
+                                   int64_t n_templates, int64_t n_bins, double *d_best, int32_t *d_arg, double *d_at,
+                                   int32_t *d_status, void *stream);
+
 /* The pseudo-data of such an ensemble drawn on the device: d_out[t][b] ~ Poisson(d_mu[b]) for n_trials trials of
  * one template row, where the reference draws Map.fluctuate("poisson") per trial from a RandomState
  * (pisa/core/map.py:1098-1254).  A counter-based generator cannot reproduce that stream: this one has its own

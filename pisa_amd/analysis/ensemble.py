@@ -5,7 +5,9 @@ The reference has no such module: an analysis loops `Map.fluctuate` + `Map.metri
 1572-1604) over trials and hypotheses.  Here the templates of a grid are made once (`TemplateGrid.from_maker`: one
 sweep of the events per `MAX_POINTS` points where the pipeline allows it), the pseudo-data of a true point are drawn
 (`pseudo_data`), and the T x K metric values come from one launch (`kernels.metric_matrix`), or never exist at all
-(`kernels.metric_matrix_best`: best, arg and the value at the true point per trial).
+(`kernels.metric_matrix_best`: best, arg and the value at the true point per trial).  `METRICS` are llh, poisson_llh,
+chi2 and mod_chi2 and the four metrics that account for finite MC statistics, correct_chi2, mcllh_mean, mcllh_eff and
+conv_llh (csrc/ensemble_mc.hip: they read the templates' `sumw2`, and `response=` is refused with them).
 
 Two generators draw the pseudo-data.  `generator="host"` (the default) is the reference's `RandomState` stream: trial
 t is the t-th `Map.fluctuate("poisson")`, drawn by scipy on the host and uploaded.  `generator="device"` is the
@@ -48,8 +50,11 @@ import numpy as np
 __all__ = ["METRICS", "GENERATORS", "DeviceSolver", "TemplateGrid", "NuisanceResponse", "grid_points", "pseudo_data",
            "metric_matrix", "delta_metric", "critical_values", "feldman_cousins", "accepted"]
 
-METRICS = ("llh", "poisson_llh", "chi2", "mod_chi2")      # kernels.METRIC_KIND
-_MAXIMISED = ("llh", "poisson_llh")
+# kernels.METRIC_KIND, then kernels.ENSEMBLE_MC_KINDS: the metrics that account for finite MC statistics, which read
+# the templates' sumw2 and have no profiled form
+METRICS = ("llh", "poisson_llh", "chi2", "mod_chi2", "correct_chi2", "mcllh_mean", "mcllh_eff", "conv_llh")
+_MC_METRICS = METRICS[4:]
+_MAXIMISED = ("llh", "poisson_llh", "mcllh_mean", "mcllh_eff", "conv_llh")
 
 
 def _check_metric(metric):
@@ -193,7 +198,7 @@ class TemplateGrid:
         return self._host[which]
 
     def sigma2_for(self, metric):
-        return self.sumw2 if metric == "mod_chi2" else None
+        return self.sumw2 if metric == "mod_chi2" or metric in _MC_METRICS else None
 
     @classmethod
     def from_maker(cls, hypo_maker, rescaled_points, metric):
@@ -356,7 +361,10 @@ class NuisanceResponse:
         return cls(names, K.to_device(resp), ips, center, at_point, values, max_iter)
 
 
-def _check_response(response, grid, solver, what):
+def _check_response(response, grid, solver, what, metric=None):
+    if metric in _MC_METRICS:
+        raise ValueError("%s: response= is not available for '%s' (no profiled form of the MC-uncertainty metrics)"
+                         % (what, metric))
     if not hasattr(solver, "profiled_matrix") or not hasattr(solver, "profiled_best"):
         raise ValueError("ensemble: response= needs a solver with profiled_matrix and profiled_best; %s has none"
                          % type(solver).__name__)
@@ -427,7 +435,7 @@ def metric_matrix(data, grid, metric, with_penalty=True, solver=None, response=N
         m = solver.matrix(metric, _data_rows(data), grid.hist, grid.sigma2_for(metric))
         penalty = grid.penalty if np.any(grid.penalty != 0.0) else None
     else:
-        _check_response(response, grid, solver, "metric_matrix")
+        _check_response(response, grid, solver, "metric_matrix", metric)
         m = solver.profiled_matrix(metric, _data_rows(data), grid.hist, response.response, grid.sigma2_for(metric),
                                    response.inv_prior_sigma, response.center, response.max_iter)["value"]
         penalty = response.offset(grid)
@@ -459,7 +467,7 @@ def delta_metric(data, grid, metric, k0, solver=None, response=None, return_info
         best, _, at = solver.best(metric, _data_rows(data), grid.hist, grid.sigma2_for(metric), offset, int(k0))
         best, at = _host(best), _host(at)
         return best - at if metric in _MAXIMISED else at - best
-    _check_response(response, grid, solver, "delta_metric")
+    _check_response(response, grid, solver, "delta_metric", metric)
     out = solver.profiled_best(metric, _data_rows(data), grid.hist, response.response, grid.sigma2_for(metric),
                                response.inv_prior_sigma, response.center, response.offset(grid), int(k0),
                                response.max_iter)
@@ -517,7 +525,7 @@ def feldman_cousins(grid, metric, n_trials, cl=(0.6827, 0.90), random_state=None
     solver = DeviceSolver() if solver is None else solver
     _check_generator(generator, solver)
     if response is not None:
-        _check_response(response, grid, solver, "feldman_cousins")
+        _check_response(response, grid, solver, "feldman_cousins", metric)
     seed = _base_seed(random_state)
     flagged = []
 

@@ -601,11 +601,21 @@ def metric(kind, actual, expected, sigma2=None, per_bin=False, total_out=None, s
 
 
 # ------------------------------------------------------------------------- trial ensembles
+# the metrics that account for finite MC statistics: their own entry points (csrc/ensemble_mc.hip), one form
+ENSEMBLE_MC_KINDS = ("correct_chi2", "mcllh_mean", "mcllh_eff", "conv_llh")
+
+
 def _ensemble_args(kind, data, expected, sigma2, form):
-    if kind not in METRIC_KIND:
-        raise ValueError("metric_matrix: metric '%s' not among %s" % (kind, sorted(METRIC_KIND)))
+    if kind not in METRIC_KIND and kind not in ENSEMBLE_MC_KINDS:
+        raise ValueError("metric_matrix: metric '%s' not among %s" % (kind, sorted(METRIC_KIND) + list(
+            ENSEMBLE_MC_KINDS)))
     if form not in _lib.ENSEMBLE_FORMS:
         raise ValueError("metric_matrix: form '%s' not among %s" % (form, list(_lib.ENSEMBLE_FORMS)))
+    if kind in ENSEMBLE_MC_KINDS:
+        if form == "product":
+            raise ValueError("metric_matrix: '%s' has no product form" % kind)
+        if sigma2 is None:
+            raise ValueError("metric_matrix: '%s' needs sigma2" % kind)
     if data.dim() != 2 or expected.dim() != 2 or data.dtype != F8 or expected.dtype != F8:
         raise ValueError("metric_matrix: data is [n_trials, n_bins] and expected [n_templates, n_bins], both float64")
     if sigma2 is not None and (sigma2.shape != expected.shape or sigma2.dtype != F8):
@@ -621,16 +631,23 @@ def metric_matrix(kind, data, expected, sigma2=None, form="auto", status=None):
     """Map.metric_total of every data map against every template (`pisa_hip_metric_matrix`): data [T, B], expected
     and sigma2 [K, B] device tensors -> [T, K] device tensor.  form "direct" (every kind), "product" (llh,
     poisson_llh: the fp64 matrix cores) or "auto" (product where it exists).  A negative datum or expectation
-    raises ValueError, as `metric` does."""
+    raises ValueError, as `metric` does.  correct_chi2, mcllh_mean, mcllh_eff and conv_llh (`ENSEMBLE_MC_KINDS`) go to
+    `pisa_hip_metric_matrix_mc`: sigma2 is required, "product" is refused, a negative sigma2 raises ValueError and a
+    negative datum or expectation does for the two mcllh kinds (the other two clip)."""
     data, expected, sigma2, n_t, n_k, n_bins = _ensemble_args(kind, data, expected, sigma2, form)
     dev = data.device
     out = torch.empty((n_t, n_k), dtype=F8, device=dev)
     own_status = status is None
     if own_status:
         status = torch.zeros(1, dtype=torch.int32, device=dev)
-    _lib.check(_lib.lib().pisa_hip_metric_matrix(
-        METRIC_KIND[kind], _lib.ENSEMBLE_FORMS.index(form), _ptr(data), _ptr(expected), _ptr(sigma2), n_t, n_k,
-        n_bins, _ptr(out), _ptr(status), _stream()))
+    if kind in ENSEMBLE_MC_KINDS:
+        _lib.check(_lib.lib().pisa_hip_metric_matrix_mc(
+            MAP_METRIC_KIND[kind], _ptr(data), _ptr(expected), _ptr(sigma2), n_t, n_k, n_bins, _ptr(out),
+            _ptr(status), _stream()))
+    else:
+        _lib.check(_lib.lib().pisa_hip_metric_matrix(
+            METRIC_KIND[kind], _lib.ENSEMBLE_FORMS.index(form), _ptr(data), _ptr(expected), _ptr(sigma2), n_t, n_k,
+            n_bins, _ptr(out), _ptr(status), _stream()))
     if own_status:
         _check_status(status)
     return out
@@ -638,8 +655,9 @@ def metric_matrix(kind, data, expected, sigma2=None, form="auto", status=None):
 
 def metric_matrix_best(kind, data, expected, sigma2=None, offset=None, k0=0, form="auto", status=None):
     """the matrix of `metric_matrix` (+ offset [K] per column) reduced per trial without being written
-    (`pisa_hip_metric_matrix_best`) -> (best [T]: max over k for the llh kinds, min for the chi2 kinds; arg [T]
-    int32: the smallest k attaining it; at [T]: column k0), bit for bit the reduction of the full matrix"""
+    (`pisa_hip_metric_matrix_best`; `pisa_hip_metric_matrix_mc_best` for `ENSEMBLE_MC_KINDS`) -> (best [T]: max over
+    k for the llh kinds, min for the chi2 kinds; arg [T] int32: the smallest k attaining it; at [T]: column k0), bit
+    for bit the reduction of the full matrix"""
     data, expected, sigma2, n_t, n_k, n_bins = _ensemble_args(kind, data, expected, sigma2, form)
     dev = data.device
     if offset is not None:
@@ -652,9 +670,14 @@ def metric_matrix_best(kind, data, expected, sigma2=None, offset=None, k0=0, for
     own_status = status is None
     if own_status:
         status = torch.zeros(1, dtype=torch.int32, device=dev)
-    _lib.check(_lib.lib().pisa_hip_metric_matrix_best(
-        METRIC_KIND[kind], _lib.ENSEMBLE_FORMS.index(form), _ptr(data), _ptr(expected), _ptr(sigma2), _ptr(offset),
-        int(k0), n_t, n_k, n_bins, _ptr(best), _ptr(arg), _ptr(at), _ptr(status), _stream()))
+    if kind in ENSEMBLE_MC_KINDS:
+        _lib.check(_lib.lib().pisa_hip_metric_matrix_mc_best(
+            MAP_METRIC_KIND[kind], _ptr(data), _ptr(expected), _ptr(sigma2), _ptr(offset), int(k0), n_t, n_k, n_bins,
+            _ptr(best), _ptr(arg), _ptr(at), _ptr(status), _stream()))
+    else:
+        _lib.check(_lib.lib().pisa_hip_metric_matrix_best(
+            METRIC_KIND[kind], _lib.ENSEMBLE_FORMS.index(form), _ptr(data), _ptr(expected), _ptr(sigma2),
+            _ptr(offset), int(k0), n_t, n_k, n_bins, _ptr(best), _ptr(arg), _ptr(at), _ptr(status), _stream()))
     if own_status:
         _check_status(status)
     return best, arg, at
@@ -694,6 +717,9 @@ def poisson_fluctuate(mu, n_trials, seed, stream=0, first_trial=0, out=None, sta
 
 
 def _profile_args(what, kind, data, expected, response, sigma2, inv_prior_sigma, center, max_iter):
+    if kind in ENSEMBLE_MC_KINDS:
+        raise ValueError("%s: '%s' has no profiled form (its per-bin function is not convex in the response)"
+                         % (what, kind))
     if kind not in METRIC_KIND:
         raise ValueError("%s: metric '%s' not among %s" % (what, kind, sorted(METRIC_KIND)))
     if data.dim() != 2 or expected.dim() != 2 or data.dtype != F8 or expected.dtype != F8:

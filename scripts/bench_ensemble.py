@@ -13,10 +13,14 @@
     drawing, upload and kernels.  `--generator host` (the default) draws on the host, `device` on the device (no upload:
     the draws are made where the kernels read them), `both` runs the two alternately in this one process.  After a
     warm-up run the measurement is repeated `--e2e-reps` times: median wall time, every run's, and the split of the
-    median run.
+    median run;
+  * `--mc` (alone: nothing else runs): the MC-uncertainty metrics correct_chi2, mcllh_mean, mcllh_eff and conv_llh, the
+    reduced form at (T, K, B) = (1e4, 1e2, 128) with sigma2 = 0.3 mu, median of 5 launches (HIP events: the preparation
+    launch + the pair kernel), and in the same run the only way there was before: a loop of `kernels.metric` over the
+    pairs of a 64 x 16 sub-block (wall time, synchronised at its end), scaled to the full size by T K / 1024.
 
     python scripts/bench_ensemble.py [--reps 20] [--skip-e2e] [--skip-kernels] [--skip-draw] [--forms direct,product]
-                                     [--true-points N] [--generator host|device|both] [--e2e-reps 3]
+                                     [--true-points N] [--generator host|device|both] [--e2e-reps 3] [--mc]
 """
 import argparse
 import json
@@ -147,6 +151,40 @@ def profiled_lines(n_params, reps):
         del d, e, r
 
 
+def mc_lines(reps=5):
+    import torch
+
+    from pisa_amd import kernels as K
+
+    dev = K.device()
+    n_t, n_k, n_b = 10 ** 4, 10 ** 2, 128
+    sub_t, sub_k = 64, 16
+    e_host = _templates(n_k, n_b)
+    rs = np.random.RandomState(1)
+    d = torch.from_numpy(rs.poisson(e_host[rs.randint(0, n_k, n_t)]).astype(np.float64)).to(dev)
+    e = torch.from_numpy(e_host).to(dev)
+    s2 = 0.3 * e
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    total = torch.empty(1, dtype=torch.float64, device=dev)
+    for kind in K.ENSEMBLE_MC_KINDS:
+        res = _time(lambda: K.metric_matrix_best(kind, d, e, s2, k0=n_k // 2, status=status), reps)
+        full = _time(lambda: K.metric_matrix(kind, d, e, s2, status=status), reps)
+        K.metric(kind, d[0], e[0], s2[0], total_out=total, status=status)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for t in range(sub_t):
+            for k in range(sub_k):
+                K.metric(kind, d[t], e[k], s2[k], total_out=total, status=status)
+        torch.cuda.synchronize()
+        loop_ms = 1e3 * (time.perf_counter() - t0)
+        scaled = loop_ms * (n_t * n_k) / (sub_t * sub_k)
+        print(json.dumps(dict(workload="mc_kernel", T=n_t, K=n_k, B=n_b, kind=kind, output="reduced", **res,
+                              ms_matrix_median=full["ms_median"], loop_pairs=sub_t * sub_k, loop_ms=round(loop_ms, 3),
+                              loop_ms_scaled_to_full=round(scaled, 1),
+                              ratio_loop_to_reduced=round(scaled / res["ms_median"], 1))), flush=True)
+    assert int(status.item()) == 0
+
+
 HBM_PEAK_TBS = 8.0           # MI355X: 8 TB/s
 
 
@@ -266,10 +304,15 @@ def main():
     ap.add_argument("--e2e-reps", type=int, default=3, help="timed end-to-end runs per generator (median)")
     ap.add_argument("--profiled", type=int, default=0, metavar="J",
                     help="also time the profiled reduced form with J fitted nuisance parameters (1 to 8)")
+    ap.add_argument("--mc", action="store_true",
+                    help="time the MC-uncertainty metrics against the loop over kernels.metric, and nothing else")
     args = ap.parse_args()
     import torch
 
     torch.cuda.set_device(0)
+    if args.mc:
+        mc_lines()
+        return
     if not args.skip_kernels:
         kernel_lines(args.reps, tuple(args.forms.split(",")))
     if args.profiled:
