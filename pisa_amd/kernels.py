@@ -296,6 +296,10 @@ def apply_osc_weights(nu_flux, prob_e, prob_mu, weights):
     """prob3.apply_function (prob3.py:621-622), in place on `weights`.  `prob_e` / `prob_mu` may be 1-D views with
     the same element stride (columns of one table): read in place."""
     lib = _lib.lib()
+    if nu_flux.numel() != 2 * weights.numel():
+        # the kernel reads (nue, numu) of event i at nu_flux[2 i], nu_flux[2 i + 1]: anything shorter is read past its end
+        raise ValueError("apply_osc_weights: nu_flux needs two columns (nue, numu) per event: %s for %d events"
+                         % (tuple(nu_flux.shape), weights.numel()))
     if (prob_e.dim() == 1 and prob_mu.dim() == 1 and prob_e.stride(0) == prob_mu.stride(0) > 1
             and prob_e.is_cuda and prob_mu.is_cuda and prob_e.dtype == prob_mu.dtype == F8
             and prob_e.numel() == prob_mu.numel() == weights.numel()):

@@ -109,7 +109,14 @@ class decoherence(Stage):  # pylint: disable=invalid-name
     def apply_function(self):
         for container in self.data:
             weights = container.device("weights").clone()
-            K.apply_osc_weights(container.device("sys_flux"), container.device("prob_e"), container.device("prob_mu"), weights)
+            flux = container.device("sys_flux")
+            if flux.dim() == 1:
+                # decoherence.py:485-487: `apply_probs` is a gufunc '(d),(),()->()', so a 1-D array is ONE flux vector
+                # (nue, numu, ...) that every event shares, not a value per event
+                if flux.numel() < 2:
+                    raise ValueError("sys_flux needs the nue and the numu flux: %d value(s)" % flux.numel())
+                flux = flux[:2].expand(weights.numel(), 2).contiguous()
+            K.apply_osc_weights(flux, container.device("prob_e"), container.device("prob_mu"), weights)
             container["weights"] = weights
 
 

@@ -437,6 +437,17 @@ def test_unfused_stage_kernels(K, oracle):
     np.testing.assert_array_equal(K.fill_probs(K.to_device(P), 1, 2).cpu().numpy(), P[:, 1, 2])
 
 
+def test_apply_osc_weights_refuses_a_flux_without_two_columns(K):
+    """one flux value per event would be read past its end (events n / 2 .. n - 1); the weights stay untouched"""
+    n = 10
+    w = K.to_device(np.ones(n))
+    one = K.to_device(np.linspace(0.1, 1, n))
+    for flux in (one, K.to_device(np.ones((n - 1, 2))), K.to_device(np.ones((n, 3)))):
+        with pytest.raises(ValueError, match="two columns"):
+            K.apply_osc_weights(flux, one, one, w)
+    assert np.array_equal(w.cpu().numpy(), np.ones(n))
+
+
 def test_metric_golden_and_errors(K):
     # (values: rtol = 1e-12 here is superseded by the gate of tests/test_gpu_metric_exact.py, a few eps of the terms
     # against exact values, which runs these inputs too as its family `stats_ref`; what only this test holds: the

@@ -109,6 +109,37 @@ def test_service_sets_up_and_runs(stage_dot_service):
                 assert w.size and np.all(np.isfinite(w)), (stage_dot_service, c.name)
 
 
+def test_decoherence_reads_a_one_dimensional_flux_as_one_vector_for_every_event():
+    """the reference's `apply_probs` is a gufunc '(d),(),()->()' (osc/decoherence.py:485-487): the 10 values that
+    `_add_test_inputs` gives `sys_flux` are ONE flux vector, whose first two entries every event shares -- the same
+    weights as with that pair written out per event, and nothing read beyond the ten values"""
+    module = importlib.import_module("pisa_amd.stages.osc.decoherence")
+    runs = []
+    for per_event in (False, True):
+        service = module.init_test(prior=None, range=None, is_fixed=True)
+        _add_test_inputs(service, empty=False)
+        service.data.representation = "events"
+        w0 = {c.name: np.array(c["weights"]) for c in service.data.containers}
+        flux = {c.name: np.array(c["sys_flux"]) for c in service.data.containers}
+        if per_event:
+            for c in service.data.containers:
+                c["sys_flux"] = np.tile(flux[c.name][:2], (flux[c.name].size, 1))
+        service.calc_mode = service.apply_mode = "events"
+        service.setup()
+        service.run()
+        out = {}
+        for c in service.data.containers:
+            c.representation = "events"
+            w = np.asarray(c["weights"])
+            f, pe, pm = flux[c.name], np.asarray(c["prob_e"]), np.asarray(c["prob_mu"])
+            assert f.shape == (10,) and w.shape == (10,)
+            np.testing.assert_allclose(w, w0[c.name] * (f[0] * pe + f[1] * pm), rtol=4 * np.finfo(float).eps, atol=0)
+            out[c.name] = w
+        runs.append(out)
+    for name in runs[0]:
+        assert np.array_equal(runs[0][name], runs[1][name]), name
+
+
 def test_detectors_shared_and_per_detector_parameters():
     """`Detectors` (pisa/core/detectors.py:36-381; the flow of its own test, :384-433, on two copies of the event-mode
     example): pipelines grouped by detector name, shared parameters ONE parameter of the fit, the others per
