@@ -880,6 +880,31 @@ int pisa_hip_poisson_fluctuate(const double *d_mu, int64_t n_bins, int64_t n_tri
                                uint32_t stream_id, uint32_t first_trial, double *d_out /* [n_trials][n_bins] */,
                                int32_t *d_status, void *stream);
 
+/* The four methods of Map.fluctuate (pisa/core/map.py:1118-1254, FLUCTUATE_METHODS) on the same generator: n_trials
+ * trials of one template row d_mu with the standard deviations d_sigma (NULL is allowed for the poisson method alone).
+ * The normal deviate of entry (t, b) comes from the block with the counter (b, first_trial + t, stream_id, 0xFFFFFFFF)
+ * under the same key -- an attempt word the Poisson sampler cannot reach, so the deviate is independent of every
+ * Poisson block -- as z = PPND16(u) (Wichura, Algorithm AS 241) of the block's first double taken on the open interval,
+ * u = ((w0 >> 6) * 2^26 + (w1 >> 6) + 0.5) * 2^-52.
+ *     poisson         as pisa_hip_poisson_fluctuate, bit for bit
+ *     scaled_poisson  mu == 0 gives 0; s = (sigma sigma) / mu, k ~ Poisson(mu / s), value k s; a negative mean is an
+ *                     error here (the reference returns negative multiples); so is sigma == 0 with mu != 0
+ *     gauss           mu + sigma z, not clipped; sigma == 0 gives mu
+ *     gauss+poisson   g = max(mu + sigma z, 0), then Poisson(g) from the blocks j = 0, 1, ...; sigma == 0 is the
+ *                     poisson entry
+ * A NaN mean gives NaN and draws nothing.  d_status[1] is set to PISA_HIP_ERR_NEGATIVE, and the entry is NaN, for a
+ * NaN, negative or infinite sigma where it is read, and for a Poisson mean without a draw (negative, +inf, > 2^52).
+ * The value of entry (t, b) depends on (seed, stream_id, first_trial + t, b, d_mu[b], d_sigma[b], method) only.
+ * PISA_HIP_ERR_INVALID before any device access: as pisa_hip_poisson_fluctuate, an unknown method, a NULL d_sigma
+ * with a method that reads it. */
+#define PISA_HIP_FLUCT_POISSON 0
+#define PISA_HIP_FLUCT_SCALED_POISSON 1
+#define PISA_HIP_FLUCT_GAUSS 2
+#define PISA_HIP_FLUCT_GAUSS_POISSON 3
+int pisa_hip_fluctuate(const double *d_mu, const double *d_sigma /* NULL: poisson only */, int32_t method,
+                       int64_t n_bins, int64_t n_trials, uint64_t seed, uint32_t stream_id, uint32_t first_trial,
+                       double *d_out /* [n_trials][n_bins] */, int32_t *d_status, void *stream);
+
 /* ----------------------------------------------- binned post-histogram stages */
 
 /* d_out[i] = d_x[i] * d_scale[i] * scalar  (d_scale may be NULL = 1), then, if

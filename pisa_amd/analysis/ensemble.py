@@ -18,6 +18,16 @@ in tests/fluctuate_cases.py and validated statistically there.  Its entry (trial
 of the true point, trial number, bin, mean) alone, so the result of `feldman_cousins` does not depend on how the
 trials are chunked.
 
+Both generators draw by any of `FLUCTUATE_METHODS` (`method=`, default "poisson"), the methods of `Map.fluctuate`
+(pisa/core/map.py:1118-1254): "gauss" and "gauss+poisson" also carry the template's MC-statistical error sqrt(sumw2)
+-- the pseudo-data a calibration of the MC-uncertainty metrics needs --, "scaled_poisson" is Bohm & Zech's scaled
+Poisson process with the template's mean and variance.  The host generator is the loop over `Map.fluctuate(method)`
+on one `RandomState`, trial by trial (the Gaussian and the Poisson draws alternate in the stream).  The device
+generator draws through `solver.fluctuate` (`kernels.fluctuate`, `pisa_hip_fluctuate`): a normal deviate per entry
+from a Philox block of its own through AS 241, defined in csrc/fluctuate_device.hpp and DESIGN.md §4 and restated in
+tests/fluctuate_method_cases.py.  The row rules of "scaled_poisson" (errors missing: their Poisson expectation;
+variance equal to the mean: the plain Poisson call) are applied per template row on the host before the launch.
+
 Nuisance parameters are profiled in two ways.  A dimension of the grid is profiled by `delta_metric` taking the best
 value over the grid's points.  A free parameter that is NOT a dimension of the grid is fitted per (trial, point) pair
 where a `NuisanceResponse` is passed (`response=`): the template of point k is linearised in those parameters around
@@ -35,19 +45,24 @@ The batch evaluator is an argument (`solver=`, default `DeviceSolver`): an objec
     best(kind, data, expected, sigma2, offset, k0) -> (best [T], arg [T], at [T])
 and, for `generator="device"`,
     draw(mu [B], n_trials, seed, stream, first_trial=0) -> [n_trials, B]
+and, for `generator="device"` with another method than "poisson",
+    fluctuate(mu [B], sigma [B], method, n_trials, seed, stream, first_trial=0) -> [n_trials, B]
 and, for `response=`,
     profiled_matrix(kind, data, expected, response, sigma2, inv_prior_sigma, center, max_iter)
         -> dict(value [T, K], eta [T, K, J], n_iter [T, K], status [T, K])
     profiled_best(kind, data, expected, response, sigma2, inv_prior_sigma, center, offset, k0, max_iter)
         -> dict(best [T], arg [T], at [T], eta_best [T, J], eta_at [T, J], status [T])
 so that everything around the kernels can run with a numpy restatement (tests/ensemble_cases.py,
-tests/fluctuate_cases.py, tests/profile_cases.py).
+tests/fluctuate_cases.py, tests/fluctuate_method_cases.py, tests/profile_cases.py).
 """
 import math
 
 import numpy as np
 
-__all__ = ["METRICS", "GENERATORS", "DeviceSolver", "TemplateGrid", "NuisanceResponse", "grid_points", "pseudo_data",
+from pisa_amd.core.map import FLUCTUATE_METHODS
+from pisa_amd.utils.comparisons import ALLCLOSE_KW
+
+__all__ = ["METRICS", "GENERATORS", "FLUCTUATE_METHODS", "DeviceSolver", "TemplateGrid", "NuisanceResponse", "grid_points", "pseudo_data",
            "metric_matrix", "delta_metric", "critical_values", "feldman_cousins", "accepted"]
 
 # kernels.METRIC_KIND, then kernels.ENSEMBLE_MC_KINDS: the metrics that account for finite MC statistics, which read
@@ -117,6 +132,14 @@ class DeviceSolver:
         from pisa_amd import kernels as K
 
         return K.poisson_fluctuate(self._up(mu).reshape(-1), n_trials, seed, stream=stream, first_trial=first_trial)
+
+    def fluctuate(self, mu, sigma, method, n_trials, seed, stream, first_trial=0):
+        """[n_trials, B] draws of the row `mu` with the standard deviations `sigma` by `method` on the device
+        (`kernels.fluctuate`)"""
+        from pisa_amd import kernels as K
+
+        return K.fluctuate(self._up(mu).reshape(-1), n_trials, seed, method=method, sigma=self._up(sigma).reshape(-1),
+                           stream=stream, first_trial=first_trial)
 
 
 def _rescaled(param, value):
@@ -378,16 +401,86 @@ GENERATORS = ("host", "device")
 CHUNK_BYTES = 1 << 30          # pseudo-data of the device generator alive at a time
 
 
-def _check_generator(generator, solver):
+def _check_generator(generator, solver, method="poisson"):
     if generator not in GENERATORS:
         raise ValueError("ensemble: generator '%s' not among %s" % (generator, list(GENERATORS)))
     if generator == "device" and not hasattr(solver, "draw"):
         raise ValueError("ensemble: generator='device' needs a solver with draw(mu, n_trials, seed, stream, "
                          "first_trial); %s has none" % type(solver).__name__)
+    if generator == "device" and method != "poisson" and not hasattr(solver, "fluctuate"):
+        raise ValueError("ensemble: generator='device' with method='%s' needs a solver with fluctuate(mu, sigma, "
+                         "method, n_trials, seed, stream, first_trial); %s has none" % (method, type(solver).__name__))
 
 
-def pseudo_data(grid, k, n_trials, random_state=None, generator="host", solver=None):
-    """[n_trials, B] pseudo-data of template k.
+def _check_method(method, grid):
+    """the method's name as `Map.fluctuate` normalises it (its ValueError for an unknown one)"""
+    name = str(method).strip().lower().replace(" ", "")
+    if name not in FLUCTUATE_METHODS:
+        raise ValueError('Map fluctuation method "%s" not recognized! Valid choices are: %s.'
+                         % (name, FLUCTUATE_METHODS))
+    if name in ("gauss", "gauss+poisson") and grid.sumw2 is None:
+        raise ValueError("ensemble: method='%s' needs the templates' sumw2; this grid has none" % name)
+    return name
+
+
+def _sigma_row(grid, k, method):
+    """The standard deviations of template k as `method` reads them: sqrt(sumw2[k]) on the host, after the row rules
+    of "scaled_poisson" (map.py:1180-1193): a non-NaN, non-zero bin without an error sets every valid bin's error to
+    its Poisson expectation (one warning); a row whose variances equal its means to `ALLCLOSE_KW` has the scale 1
+    exactly.  None where the draw is the plain Poisson draw (method "poisson", or that scale of 1)."""
+    if method == "poisson":
+        return None
+    mu = np.asarray(grid.host("hist")[k], dtype=np.float64).ravel()
+    with np.errstate(invalid="ignore"):
+        sigma = np.zeros(mu.size) if grid.sumw2 is None else np.sqrt(
+            np.asarray(grid.host("sumw2")[k], dtype=np.float64).ravel())
+        if method == "scaled_poisson":
+            ok = ~np.isnan(mu)
+            if np.any(sigma[ok & (mu != 0.0)] == 0.0):
+                from pisa_amd.utils.log import logging
+
+                logging.warning("Some bins have non-zero counts but no associated error! All errors will be set to "
+                                "their Poisson expectation now.")
+                sigma = np.where(ok, np.sqrt(mu), sigma)
+            if np.allclose(sigma[ok] ** 2, mu[ok], **ALLCLOSE_KW):
+                return None
+    return sigma
+
+
+def _host_fluctuate(mu, sigma, method, rs):
+    """one `Map.fluctuate(method, random_state=rs)` of the row `mu` with the standard deviations `sigma` (the
+    post-rule row of `_sigma_row`; None: the scale 1 of "scaled_poisson"): the same scipy calls on the non-NaN bins
+    in the same order (map.py:1171-1251)"""
+    from scipy.stats import norm, poisson
+
+    ok = ~np.isnan(mu)
+    out = np.full(mu.size, np.nan)
+    with np.errstate(invalid="ignore"):
+        if method == "scaled_poisson":
+            scale = 1.0 if sigma is None else sigma[ok] ** 2 / mu[ok]
+            out[ok] = poisson.rvs(mu[ok] / scale, random_state=rs)
+            out[ok] *= scale
+            out[mu == 0.0] = 0.0
+        elif method == "gauss+poisson":
+            g = np.clip(norm.rvs(loc=mu[ok], scale=sigma[ok], random_state=rs), 0, None)
+            out[ok] = poisson.rvs(g, random_state=rs)
+        else:
+            out[ok] = norm.rvs(loc=mu[ok], scale=sigma[ok], random_state=rs)
+    return out
+
+
+def _device_draw(solver, grid, k, sigma, method, n_trials, seed, first_trial=0):
+    if sigma is None:
+        return solver.draw(grid.hist[k], n_trials, seed, stream=k, first_trial=first_trial)
+    return solver.fluctuate(grid.hist[k], sigma, method, n_trials, seed, stream=k, first_trial=first_trial)
+
+
+def pseudo_data(grid, k, n_trials, random_state=None, generator="host", solver=None, method="poisson"):
+    """[n_trials, B] pseudo-data of template k by `method` (one of `FLUCTUATE_METHODS`; every method but "poisson"
+    reads sigma = sqrt(grid.sumw2[k]), and "scaled_poisson" applies the reference's row rules to it first: module
+    docstring).  With another method than "poisson" the host generator is the loop of `Map.fluctuate(method,
+    random_state=rs)` over the trials on ONE `RandomState`, and the device generator is `solver.fluctuate(grid.hist[k],
+    sigma, method, n_trials, seed, stream=k)`.  For "poisson":
     generator="host": trial t is exactly the t-th `Map.fluctuate("poisson", random_state=rs)` of that template from
     ONE `RandomState` rs (one `scipy.stats.poisson.rvs` call on the tiled expectation consumes the stream in the same
     order; NaN bins stay NaN and draw nothing).  Drawn on the host, a host array: the reference's stream.
@@ -395,14 +488,22 @@ def pseudo_data(grid, k, n_trials, random_state=None, generator="host", solver=N
     default, a device tensor: `kernels.poisson_fluctuate`), seed = `random_state` or one draw from it if it is a
     RandomState, as in `feldman_cousins`.  A counter-based generator of its own definition, NOT the reference's
     stream; NaN bins stay NaN and a zero bin stays 0 here as well."""
+    method = _check_method(method, grid)
     if generator != "host":
         solver = DeviceSolver() if solver is None else solver
-        _check_generator(generator, solver)
-        return solver.draw(grid.hist[k], int(n_trials), _base_seed(random_state), stream=int(k))
+        _check_generator(generator, solver, method)
+        return _device_draw(solver, grid, int(k), _sigma_row(grid, k, method), method, int(n_trials),
+                            _base_seed(random_state))
     from scipy.stats import poisson
 
     rs = random_state if isinstance(random_state, np.random.RandomState) else np.random.RandomState(random_state)
     mu = np.asarray(grid.host("hist")[k], dtype=np.float64).ravel()
+    if method != "poisson":
+        sigma = _sigma_row(grid, k, method)
+        out = np.empty((max(int(n_trials), 0), mu.size))
+        for t in range(out.shape[0]):
+            out[t] = _host_fluctuate(mu, sigma, method, rs)
+        return out
     ok = ~np.isnan(mu)
     out = np.full((int(n_trials), mu.size), np.nan)
     if n_trials > 0 and ok.any():
@@ -506,7 +607,7 @@ def _base_seed(random_state):
 
 
 def feldman_cousins(grid, metric, n_trials, cl=(0.6827, 0.90), random_state=None, true_points=None, solver=None,
-                    generator="host", chunk_bytes=CHUNK_BYTES, response=None):
+                    generator="host", chunk_bytes=CHUNK_BYTES, response=None, method="poisson"):
     """Critical values of the Feldman-Cousins ordering on the grid: for every true point k0 (default: all), n_trials
     pseudo-data maps of template k0, their `delta_metric` at k0 and `critical_values` -> crit [len(true_points),
     len(cl)].  seed: `random_state`, or one draw from it if it is a RandomState.
@@ -514,7 +615,8 @@ def feldman_cousins(grid, metric, n_trials, cl=(0.6827, 0.90), random_state=None
     uploaded; generator="device": every true point is the stream k0 of the solver's `draw` under the one seed, the
     draws go from `draw` into `delta_metric` where they are, in chunks of whole trials of at most `chunk_bytes` of
     pseudo-data (trial numbers carried through `first_trial`: the result does not depend on the chunks).  Either way
-    a subset of true points reproduces the full run's rows.  Without `response` nuisance parameters are profiled only
+    a subset of true points reproduces the full run's rows.  `method`: how the pseudo-data fluctuate, as in
+    `pseudo_data` (the device generator then draws through the solver's `fluctuate`).  Without `response` nuisance parameters are profiled only
     as far as they are dimensions of the grid (module docstring).  With `response` (a `NuisanceResponse`) every
     distance is profiled over the response's parameters and the return value is (crit, info), info = dict(flagged
     [len(true_points)]: per true point the number of trials whose pair at the best point or at the true point carries
@@ -523,7 +625,8 @@ def feldman_cousins(grid, metric, n_trials, cl=(0.6827, 0.90), random_state=None
     if n_trials < 1:
         raise ValueError("feldman_cousins: n_trials >= 1")
     solver = DeviceSolver() if solver is None else solver
-    _check_generator(generator, solver)
+    method = _check_method(method, grid)
+    _check_generator(generator, solver, method)
     if response is not None:
         _check_response(response, grid, solver, "feldman_cousins", metric)
     seed = _base_seed(random_state)
@@ -546,12 +649,13 @@ def feldman_cousins(grid, metric, n_trials, cl=(0.6827, 0.90), random_state=None
     for i, k0 in enumerate(points):
         flagged.append(0)
         if generator == "host":
-            data = pseudo_data(grid, k0, n_trials, np.random.RandomState([seed, k0]))
+            data = pseudo_data(grid, k0, n_trials, np.random.RandomState([seed, k0]), method=method)
             delta = distances(data, k0)
         else:
+            sigma = _sigma_row(grid, k0, method)
             parts = []
             for first in range(0, n_trials, rows):
-                data = solver.draw(grid.hist[k0], min(rows, n_trials - first), seed, stream=k0, first_trial=first)
+                data = _device_draw(solver, grid, k0, sigma, method, min(rows, n_trials - first), seed, first)
                 parts.append(distances(data, k0))
             delta = np.concatenate(parts)
         crit[i] = critical_values(delta, cl)

@@ -1,5 +1,8 @@
-// fluctuate.hip -- Poisson pseudo-data of a trial ensemble drawn on the device: out[t][b] ~ Poisson(mu[b]) for
-// n_trials trials of one template row, from a counter-based generator (Philox4x32-10, Salmon et al., SC'11).
+// fluctuate.hip -- pseudo-data of a trial ensemble drawn on the device: out[t][b] ~ Poisson(mu[b]) for n_trials
+// trials of one template row, from a counter-based generator (Philox4x32-10, Salmon et al., SC'11), and the other
+// methods of `Map.fluctuate` (pisa/core/map.py:1118-1254): gauss, gauss+poisson and scaled_poisson, which also read
+// the row's standard deviations (their definition: the head of fluctuate_device.hpp; a normal deviate per entry from
+// the block (b, trial, stream, 0xFFFFFFFF) through AS 241, independent of the Poisson blocks).
 // The reference draws `Map.fluctuate("poisson")` from a `RandomState` stream (pisa/core/map.py:1098-1254), which no
 // counter-based generator reproduces; this is a generator of its own, defined here and in DESIGN.md §4, restated draw
 // for draw in tests/fluctuate_cases.py and validated statistically (tests/test_host_fluctuate.py).
@@ -32,18 +35,21 @@ constexpr int FL_THREADS = 256;
 constexpr int FL_MAX_BLOCKS = 2048;      // 2 workgroups per CU are resident (fluct_kernel: 2 wavefronts per SIMD)
 
 // entry i = t n_bins + b; lane i0 of the grid takes the entries i0, i0 + step, ... with step = step_t n_bins + step_b
-// (the number of lanes of the grid, split on the host), carried as (t, b) so that no 64-bit division runs here
+// (the number of lanes of the grid, split on the host), carried as (t, b) so that no 64-bit division runs here.
+// One instantiation per method: `fl_fluctuate` folds to the method's own branch, and the Poisson one reads no sigma.
+template <int METHOD>
 __global__ void __launch_bounds__(FL_THREADS)
-fluct_kernel(const double *__restrict__ mu, uint32_t B, int64_t T, uint32_t k0, uint32_t k1, uint32_t stream,
-             uint32_t first_trial, int64_t step_t, uint32_t step_b, double *__restrict__ out,
-             int32_t *__restrict__ status) {
+fluct_kernel(const double *__restrict__ mu, const double *__restrict__ sigma, uint32_t B, int64_t T, uint32_t k0,
+             uint32_t k1, uint32_t stream, uint32_t first_trial, int64_t step_t, uint32_t step_b,
+             double *__restrict__ out, int32_t *__restrict__ status) {
     const uint32_t i0 = blockIdx.x * (uint32_t)FL_THREADS + threadIdx.x;   // < FL_MAX_BLOCKS * FL_THREADS
     uint32_t b = i0 % B;
     int64_t t = (int64_t)(i0 / B);
     bool bad = false;
     while (t < T) {
         // first_trial + n_trials <= 2^32: the trial number fits the counter word
-        out[t * (int64_t)B + b] = fl_draw(mu[b], b, first_trial + (uint32_t)t, stream, k0, k1, bad);
+        const double sg = METHOD == FL_POISSON ? 0.0 : sigma[b];
+        out[t * (int64_t)B + b] = fl_fluctuate(METHOD, mu[b], sg, b, first_trial + (uint32_t)t, stream, k0, k1, bad);
         b += step_b;   // (< 2 B <= 2^32 - 2)
         t += step_t;
         if (b >= B) {
@@ -54,6 +60,32 @@ fluct_kernel(const double *__restrict__ mu, uint32_t B, int64_t T, uint32_t k0, 
     if (bad) status[0] = PISA_HIP_ERR_NEGATIVE;   // (every writer stores the same word)
 }
 
+static_assert(FL_POISSON == PISA_HIP_FLUCT_POISSON && FL_SCALED_POISSON == PISA_HIP_FLUCT_SCALED_POISSON &&
+                  FL_GAUSS == PISA_HIP_FLUCT_GAUSS && FL_GAUSS_POISSON == PISA_HIP_FLUCT_GAUSS_POISSON,
+              "fluctuate_device.hpp and pisa_hip.h number the methods alike");
+
+template <int METHOD>
+static int fluct_launch(const double *d_mu, const double *d_sigma, int64_t n_bins, int64_t n_trials, uint64_t seed,
+                        uint32_t stream_id, uint32_t first_trial, double *d_out, int32_t *d_status, void *stream) {
+    // (with the limits of fluct_check n_trials * n_bins does not overflow int64)
+    const int64_t entries = n_trials * n_bins;
+    const int64_t want = (entries + FL_THREADS - 1) / FL_THREADS;
+    const int64_t blocks = want < FL_MAX_BLOCKS ? want : FL_MAX_BLOCKS;
+    const int64_t step = blocks * FL_THREADS;
+    hipLaunchKernelGGL(fluct_kernel<METHOD>, dim3((unsigned)blocks), dim3(FL_THREADS), 0, as_stream(stream), d_mu,
+                       d_sigma, (uint32_t)n_bins, n_trials, (uint32_t)(seed & 0xffffffffu), (uint32_t)(seed >> 32),
+                       stream_id, first_trial, step / n_bins, (uint32_t)(step % n_bins), d_out, d_status);
+    PISA_CHECK_LAUNCH("fluct_kernel");
+    return PISA_HIP_OK;
+}
+
+static bool fluct_check(const double *d_mu, int64_t n_bins, int64_t n_trials, uint32_t first_trial,
+                        const double *d_out, const int32_t *d_status) {
+    if (!d_mu || !d_out || !d_status) return false;
+    if (n_bins < 1 || n_trials < 1 || n_bins > 0x7FFFFFFF || n_trials > 0x7FFFFFFF) return false;
+    return (int64_t)first_trial + n_trials <= ((int64_t)1 << 32);
+}
+
 }  // namespace pisa
 
 using namespace pisa;
@@ -61,17 +93,29 @@ using namespace pisa;
 PISA_API int pisa_hip_poisson_fluctuate(const double *d_mu, int64_t n_bins, int64_t n_trials, uint64_t seed,
                                         uint32_t stream_id, uint32_t first_trial, double *d_out, int32_t *d_status,
                                         void *stream) {
-    if (!d_mu || !d_out || !d_status) return PISA_HIP_ERR_INVALID;
-    if (n_bins < 1 || n_trials < 1 || n_bins > 0x7FFFFFFF || n_trials > 0x7FFFFFFF) return PISA_HIP_ERR_INVALID;
-    if ((int64_t)first_trial + n_trials > ((int64_t)1 << 32)) return PISA_HIP_ERR_INVALID;
-    // (with the limits above n_trials * n_bins does not overflow int64)
-    const int64_t entries = n_trials * n_bins;
-    const int64_t want = (entries + FL_THREADS - 1) / FL_THREADS;
-    const int64_t blocks = want < FL_MAX_BLOCKS ? want : FL_MAX_BLOCKS;
-    const int64_t step = blocks * FL_THREADS;
-    hipLaunchKernelGGL(fluct_kernel, dim3((unsigned)blocks), dim3(FL_THREADS), 0, as_stream(stream), d_mu,
-                       (uint32_t)n_bins, n_trials, (uint32_t)(seed & 0xffffffffu), (uint32_t)(seed >> 32), stream_id,
-                       first_trial, step / n_bins, (uint32_t)(step % n_bins), d_out, d_status);
-    PISA_CHECK_LAUNCH("fluct_kernel");
-    return PISA_HIP_OK;
+    if (!fluct_check(d_mu, n_bins, n_trials, first_trial, d_out, d_status)) return PISA_HIP_ERR_INVALID;
+    return fluct_launch<FL_POISSON>(d_mu, nullptr, n_bins, n_trials, seed, stream_id, first_trial, d_out, d_status,
+                                    stream);
+}
+
+PISA_API int pisa_hip_fluctuate(const double *d_mu, const double *d_sigma, int32_t method, int64_t n_bins,
+                                int64_t n_trials, uint64_t seed, uint32_t stream_id, uint32_t first_trial,
+                                double *d_out, int32_t *d_status, void *stream) {
+    if (!fluct_check(d_mu, n_bins, n_trials, first_trial, d_out, d_status)) return PISA_HIP_ERR_INVALID;
+    if (method < FL_POISSON || method > FL_GAUSS_POISSON) return PISA_HIP_ERR_INVALID;
+    if (method != FL_POISSON && !d_sigma) return PISA_HIP_ERR_INVALID;
+    switch (method) {
+    case FL_POISSON:
+        return fluct_launch<FL_POISSON>(d_mu, d_sigma, n_bins, n_trials, seed, stream_id, first_trial, d_out, d_status,
+                                        stream);
+    case FL_SCALED_POISSON:
+        return fluct_launch<FL_SCALED_POISSON>(d_mu, d_sigma, n_bins, n_trials, seed, stream_id, first_trial, d_out,
+                                               d_status, stream);
+    case FL_GAUSS:
+        return fluct_launch<FL_GAUSS>(d_mu, d_sigma, n_bins, n_trials, seed, stream_id, first_trial, d_out, d_status,
+                                      stream);
+    default:
+        return fluct_launch<FL_GAUSS_POISSON>(d_mu, d_sigma, n_bins, n_trials, seed, stream_id, first_trial, d_out,
+                                              d_status, stream);
+    }
 }

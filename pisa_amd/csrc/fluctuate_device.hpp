@@ -1,7 +1,22 @@
-// fluctuate_device.hpp -- the counter-based Poisson generator of fluctuate.hip, per entry: Philox4x32-10, the two doubles
-// of a block and the sampler (definition: the head of fluctuate.hip).  No HIP type or call, so that the same
-// source also compiles for the host with a plain C++ compiler: tests/test_host_fluctuate.py runs it there, under the
-// sanitizers, against the numpy restatement of tests/fluctuate_cases.py.
+// fluctuate_device.hpp -- the counter-based generator of fluctuate.hip, per entry: Philox4x32-10, the doubles of a block,
+// the Poisson sampler, the normal deviate and the four fluctuation methods (definition: the head of fluctuate.hip,
+// DESIGN.md §4).  No HIP type or call, so that the same source also compiles for the host with a plain C++ compiler:
+// tests/test_host_fluctuate.py and tests/test_host_fluctuate_methods.py run it there, under the sanitizers, against the
+// numpy restatements of tests/fluctuate_cases.py and tests/fluctuate_method_cases.py.
+//
+// The Gaussian block of an entry is the Philox block with the counter (bin, trial number, stream, 0xFFFFFFFF) under
+// the same key.  The Poisson sampler's blocks carry the attempt j = 0, 1, ... in that word; PTRS accepts every attempt
+// with a probability above 0.8, so the chance of reaching j = 2^32 - 1 is below 0.2^(2^32 - 1): the word is one the
+// sampler cannot reach and the normal deviate is independent of every Poisson block.  Only the block's first double is
+// used, as the open-interval uniform
+//     u = ((double)(w0 >> 6) * 2^26 + (double)(w1 >> 6) + 0.5) * 2^-52
+// of 52 random bits: it lies in [2^-53, 1 - 2^-53], its lattice is symmetric about 1/2, and u - 0.5 and 1 - u are exact.
+// ((k + 0.5) * 2^-53 on the 53-bit integer of fl_unit would not do: k + 0.5 is no double from 2^52 on and the top of
+// that lattice rounds to 1.0.)  The deviate is z = PPND16(u), Wichura's Algorithm AS 241 (Applied Statistics 37 (1988)
+// 477-484), with the coefficients of the publication; |z| < 8.2096.  Its central branch (|u - 0.5| <= 0.425, 85 % of
+// the draws) is additions, multiplications and one division: built without contraction it has the same bits in the
+// kernel, in g++ and in numpy.  The tail branches take r = sqrt(-log(min(u, 1 - u))): log is the one library call that
+// may differ between the sides.  The Horner chains run from the highest coefficient down, the numerator first.
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -17,6 +32,9 @@ namespace pisa {
 constexpr int FL_INVERSION_CAP = 255;
 constexpr double FL_PTRS_FROM = 10.0;
 constexpr double FL_MU_MAX = 4503599627370496.0;   // 2^52: beyond it a count is not every integer
+constexpr uint32_t FL_GAUSS_WORD = 0xFFFFFFFFu;    // the attempt word of the Gaussian block
+// the methods (PISA_HIP_FLUCT_* of pisa_hip.h; Map.fluctuate of pisa/core/map.py:1118-1254)
+constexpr int FL_POISSON = 0, FL_SCALED_POISSON = 1, FL_GAUSS = 2, FL_GAUSS_POISSON = 3;
 
 struct FlWords {
     uint32_t w[4];
@@ -80,6 +98,101 @@ PISA_FL_HD double fl_draw(double mu, uint32_t b, uint32_t trial, uint32_t stream
         j++;
         w = fl_philox(b, trial, stream, j, k0, k1);
     }
+}
+
+// 52 bits of two words -> (0, 1), symmetric about 1/2; every operation is exact
+PISA_FL_HD double fl_unit_open(uint32_t w0, uint32_t w1) {
+    return ((double)(w0 >> 6) * 67108864.0 + (double)(w1 >> 6) + 0.5) * (1.0 / 4503599627370496.0);
+}
+
+// PPND16 of AS 241: the standard normal quantile of u in (0, 1)
+PISA_FL_HD double fl_normal_quantile(double u) {
+    const double q = u - 0.5;
+    if (fabs(q) <= 0.425) {
+        const double r = 0.180625 - q * q;
+        const double num = (((((((2.5090809287301226727e+3 * r + 3.3430575583588128105e+4) * r +
+                                 6.7265770927008700853e+4) * r + 4.5921953931549871457e+4) * r +
+                               1.3731693765509461125e+4) * r + 1.9715909503065514427e+3) * r +
+                             1.3314166789178437745e+2) * r + 3.3871328727963666080e+0) * q;
+        const double den = ((((((5.2264952788528545610e+3 * r + 2.8729085735721942674e+4) * r +
+                                3.9307895800092710610e+4) * r + 2.1213794301586595867e+4) * r +
+                              5.3941960214247511077e+3) * r + 6.8718700749205790830e+2) * r +
+                            4.2313330701600911252e+1) * r + 1.0;
+        return num / den;
+    }
+    double r = sqrt(-log(q <= 0.0 ? u : 1.0 - u));
+    double num, den;
+    if (r <= 5.0) {
+        r = r - 1.6;
+        num = ((((((7.74545014278341407640e-4 * r + 2.27238449892691845833e-2) * r + 2.41780725177450611770e-1) * r +
+                  1.27045825245236838258e+0) * r + 3.64784832476320460504e+0) * r + 5.76949722146069140550e+0) * r +
+               4.63033784615654529590e+0) * r + 1.42343711074968357734e+0;
+        den = ((((((1.05075007164441684324e-9 * r + 5.47593808499534494600e-4) * r + 1.51986665636164571966e-2) * r +
+                  1.48103976427480074590e-1) * r + 6.89767334985100004550e-1) * r + 1.67638483018380384940e+0) * r +
+               2.05319162663775882187e+0) * r + 1.0;
+    } else {
+        r = r - 5.0;
+        num = ((((((2.01033439929228813265e-7 * r + 2.71155556874348757815e-5) * r + 1.24266094738807843860e-3) * r +
+                  2.65321895265761230930e-2) * r + 2.96560571828504891230e-1) * r + 1.78482653991729133580e+0) * r +
+               5.46378491116411436990e+0) * r + 6.65790464350110377720e+0;
+        den = ((((((2.04426310338993978564e-15 * r + 1.42151175831644588870e-7) * r + 1.84631831751005468180e-5) * r +
+                  7.86869131145613259100e-4) * r + 1.48753612908506148525e-2) * r + 1.36929880922735805310e-1) * r +
+               5.99832206555887937690e-1) * r + 1.0;
+    }
+    const double x = num / den;
+    return q < 0.0 ? -x : x;
+}
+
+// the normal deviate of entry (b, trial, stream): the first double of the Gaussian block
+PISA_FL_HD double fl_normal(uint32_t b, uint32_t trial, uint32_t stream, uint32_t k0, uint32_t k1) {
+    const FlWords w = fl_philox(b, trial, stream, FL_GAUSS_WORD, k0, k1);
+    return fl_normal_quantile(fl_unit_open(w.w[0], w.w[1]));
+}
+
+// One entry of `method`.  A NaN mean gives NaN for every method: nothing is drawn and `bad` is not set.  Where sigma
+// is read, a NaN, negative or infinite sigma gives NaN and `bad`.  Every product and sum is rounded (no contraction).
+//   poisson         fl_draw(mu); sigma is not read.
+//   gauss           mu + sigma z, not clipped; sigma == 0 gives mu itself and reads no block; mu == 0 with sigma > 0
+//                   does fluctuate, as in the reference.
+//   gauss+poisson   g = mu + sigma z; g < 0 becomes 0; then fl_draw(g) with its own blocks j = 0, 1, ...; g > 2^52
+//                   gives NaN and `bad`; sigma == 0 is exactly the poisson entry.
+//   scaled_poisson  mu == 0 gives 0 (sigma is not read); mu < 0 gives NaN and `bad` (the reference silently returns
+//                   negative multiples of a negative scale there: this departs from it); otherwise
+//                   s = (sigma sigma) / mu, lam = mu / s, k = fl_draw(lam), result k s.  sigma == 0 with mu != 0 gives
+//                   lam = inf, so NaN and `bad` (analysis/ensemble.py applies the reference's row rule before it calls);
+//                   so does an s that is not finite (sigma sigma overflowed, or mu = +inf gave s = 0 and lam = inf).
+// `method` is a constant where the kernel calls this, so an instantiation holds its own branch only.
+PISA_FL_HD double fl_fluctuate(int method, double mu, double sigma, uint32_t b, uint32_t trial, uint32_t stream,
+                               uint32_t k0, uint32_t k1, bool &bad) {
+    if (method == FL_POISSON) return fl_draw(mu, b, trial, stream, k0, k1, bad);
+    if (mu != mu) return mu;
+    if (method == FL_SCALED_POISSON && mu == 0.0) return 0.0;
+    if (!(sigma >= 0.0 && sigma <= 1.7976931348623157e308)) {
+        bad = true;
+        return NAN;
+    }
+    if (method == FL_SCALED_POISSON) {
+        if (mu < 0.0) {
+            bad = true;
+            return NAN;
+        }
+        const double s = (sigma * sigma) / mu;
+        if (!(s <= 1.7976931348623157e308)) {   // (sigma sigma overflowed: lam = 0 would give 0 * inf)
+            bad = true;
+            return NAN;
+        }
+        const double lam = mu / s;
+        const double k = fl_draw(lam, b, trial, stream, k0, k1, bad);
+        return k * s;
+    }
+    double g = mu;
+    if (sigma != 0.0) {
+        const double sz = sigma * fl_normal(b, trial, stream, k0, k1);
+        g = mu + sz;
+        if (method == FL_GAUSS_POISSON && g < 0.0) g = 0.0;
+    }
+    // (one call site of the sampler for both cases of sigma: one copy of it in the kernel)
+    return method == FL_GAUSS ? g : fl_draw(g, b, trial, stream, k0, k1, bad);
 }
 
 }  // namespace pisa

@@ -720,6 +720,57 @@ def poisson_fluctuate(mu, n_trials, seed, stream=0, first_trial=0, out=None, sta
     return out
 
 
+FLUCTUATE_METHOD = {"poisson": 0, "scaled_poisson": 1, "gauss": 2, "gauss+poisson": 3}     # PISA_HIP_FLUCT_*
+
+
+def fluctuate_method(method):
+    """a method name normalised as `Map.fluctuate` does (strip, lower, spaces removed); its ValueError otherwise"""
+    name = str(method).strip().lower().replace(" ", "")
+    if name not in FLUCTUATE_METHOD:
+        raise ValueError('Map fluctuation method "%s" not recognized! Valid choices are: %s.'
+                         % (name, tuple(FLUCTUATE_METHOD)))
+    return name
+
+
+def fluctuate(mu, n_trials, seed, method="poisson", sigma=None, stream=0, first_trial=0, out=None, status=None):
+    """Pseudo-data of one template row drawn on the device by one of the methods of `Map.fluctuate`
+    (`pisa_hip_fluctuate`; map.py:1118-1254): mu [B] and, for every method but "poisson", sigma [B] float64 device
+    vectors -> [n_trials, B] float64 device tensor from the counter-based generator of csrc/fluctuate.hip.
+    "poisson" is `poisson_fluctuate`, bit for bit; "gauss" mu + sigma z; "gauss+poisson" Poisson(max(mu + sigma z, 0));
+    "scaled_poisson" k s with s = sigma^2 / mu and k ~ Poisson(mu / s), 0 where mu is 0.  The entry depends on (seed,
+    stream, first_trial + t, b, mu[b], sigma[b], method) alone.  A NaN mean gives NaN; a NaN, negative or infinite
+    sigma, or a Poisson mean without a draw (negative, infinite, > 2^52), raises ValueError."""
+    name = fluctuate_method(method)
+    if mu.dim() != 1 or mu.dtype != F8:
+        raise ValueError("fluctuate: mu is a float64 vector [n_bins]")
+    if sigma is None:
+        if name != "poisson":
+            raise ValueError("fluctuate: method '%s' needs sigma" % name)
+    elif sigma.dim() != 1 or sigma.dtype != F8 or sigma.shape != mu.shape or sigma.device != mu.device:
+        raise ValueError("fluctuate: sigma is a float64 vector of mu's shape on mu's device")
+    seed, stream, first_trial, n_trials = int(seed), int(stream), int(first_trial), int(n_trials)
+    if not 0 <= seed < 2 ** 64:
+        raise ValueError("fluctuate: the seed %d is outside [0, 2^64)" % seed)
+    if not (0 <= stream < 2 ** 32 and 0 <= first_trial < 2 ** 32):
+        raise ValueError("fluctuate: stream and first_trial are in [0, 2^32)")
+    mu = mu.contiguous()
+    sigma = None if sigma is None else sigma.contiguous()
+    n_bins = mu.shape[0]
+    dev = mu.device
+    if out is None:
+        out = torch.empty((max(n_trials, 0), n_bins), dtype=F8, device=dev)
+    elif tuple(out.shape) != (n_trials, n_bins) or out.dtype != F8 or not out.is_contiguous():
+        raise ValueError("fluctuate: out is a contiguous float64 [n_trials, n_bins]")
+    own_status = status is None
+    if own_status:
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+    _lib.check(_lib.lib().pisa_hip_fluctuate(_ptr(mu), _ptr(sigma), FLUCTUATE_METHOD[name], n_bins, n_trials, seed,
+                                             stream, first_trial, _ptr(out), _ptr(status), _stream()))
+    if own_status:
+        _check_status(status)
+    return out
+
+
 def _profile_args(what, kind, data, expected, response, sigma2, inv_prior_sigma, center, max_iter):
     if kind in ENSEMBLE_MC_KINDS:
         raise ValueError("%s: '%s' has no profiled form (its per-bin function is not convex in the response)"

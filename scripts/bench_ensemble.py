@@ -8,12 +8,14 @@
     The product form's fraction of the fp64 peak counts 2 T K B flop (llh: 4 T K B, its two products);
   * the same work as a loop over `kernels.metric` on a 100 x 100 corner (all there was before these kernels);
   * the draw kernel alone (`kernels.poisson_fluctuate`), output resident, at (T, B) = (1e4, 128) and (1e4, 4800), with the
-    draws per second and the share of the HBM bandwidth its 8 T B bytes of stores come to;
+    draws per second and the share of the HBM bandwidth its 8 T B bytes of stores come to; then, in the same run, the four
+    fluctuation methods through `kernels.fluctuate` (sigma = sqrt(0.3 mu)) with their ratio to that Poisson baseline;
   * end to end: `feldman_cousins` with T = 1e4 on a 30 x 30 grid of 128-bin templates, its wall time split into
     drawing, upload and kernels.  `--generator host` (the default) draws on the host, `device` on the device (no upload:
     the draws are made where the kernels read them), `both` runs the two alternately in this one process.  After a
     warm-up run the measurement is repeated `--e2e-reps` times: median wall time, every run's, and the split of the
-    median run;
+    median run.  `--metric` and `--method` choose the metric and the fluctuation method of that run (defaults llh and
+    poisson; any other choice gives the templates sumw2 = 0.3 mu);
   * `--mc` (alone: nothing else runs): the MC-uncertainty metrics correct_chi2, mcllh_mean, mcllh_eff and conv_llh, the
     reduced form at (T, K, B) = (1e4, 1e2, 128) with sigma2 = 0.3 mu, median of 5 launches (HIP events: the preparation
     launch + the pair kernel), and in the same run the only way there was before: a loop of `kernels.metric` over the
@@ -21,6 +23,7 @@
 
     python scripts/bench_ensemble.py [--reps 20] [--skip-e2e] [--skip-kernels] [--skip-draw] [--forms direct,product]
                                      [--true-points N] [--generator host|device|both] [--e2e-reps 3] [--mc]
+                                     [--metric llh] [--method poisson]
 """
 import argparse
 import json
@@ -205,6 +208,13 @@ def draw_lines(reps):
         print(json.dumps(dict(workload="draw_kernel", T=n_t, B=n_b, mean_of_mu=round(float(mu.mean().item()), 2), **res,
                               gdraws_per_s=round(n_t * n_b / sec / 1e9, 3),
                               frac_of_hbm_peak=round(8.0 * n_t * n_b / sec / 1e12 / HBM_PEAK_TBS, 4))), flush=True)
+        sigma = torch.sqrt(0.3 * mu)
+        for method in K.FLUCTUATE_METHOD:
+            m = _time(lambda: K.fluctuate(mu, n_t, 1, method=method, sigma=sigma, stream=7, out=out, status=status), reps)
+            assert int(status.item()) == 0
+            print(json.dumps(dict(workload="fluctuate_kernel", method=method, T=n_t, B=n_b, **m,
+                                  ratio_to_poisson_entry_point=round(m["ms_median"] / res["ms_median"], 3),
+                                  gdraws_per_s=round(n_t * n_b / (m["ms_median"] * 1e-3) / 1e9, 3))), flush=True)
 
 
 class _TimedSolver:
@@ -223,6 +233,15 @@ class _TimedSolver:
         self.timings["draw"] = self.timings.get("draw", 0.0) + (time.perf_counter() - t0)
         return out
 
+    def fluctuate(self, mu, sigma, method, n_trials, seed, stream, first_trial=0):
+        import torch
+
+        t0 = time.perf_counter()
+        out = self.solver.fluctuate(mu, sigma, method, n_trials, seed, stream, first_trial)
+        torch.cuda.synchronize()
+        self.timings["draw"] = self.timings.get("draw", 0.0) + (time.perf_counter() - t0)
+        return out
+
     def best(self, kind, data, expected, sigma2=None, offset=None, k0=0):
         import torch
 
@@ -237,7 +256,7 @@ class _TimedSolver:
         return out
 
 
-def _e2e_once(en, grid, n_trials, points, generator):
+def _e2e_once(en, grid, n_trials, points, generator, metric="llh", method="poisson"):
     """one timed `feldman_cousins` -> (wall, timings, crit)"""
     import torch
 
@@ -254,40 +273,42 @@ def _e2e_once(en, grid, n_trials, points, generator):
     t0 = time.perf_counter()
     en.pseudo_data = timed_draw
     try:
-        crit = en.feldman_cousins(grid, "llh", n_trials, random_state=1, true_points=points,
-                                  solver=_TimedSolver(en.DeviceSolver(), timings), generator=generator)
+        crit = en.feldman_cousins(grid, metric, n_trials, random_state=1, true_points=points,
+                                  solver=_TimedSolver(en.DeviceSolver(), timings), generator=generator, method=method)
     finally:
         en.pseudo_data = draw
     torch.cuda.synchronize()
     return time.perf_counter() - t0, timings, crit
 
 
-def e2e_lines(n_trials, true_points, generator, reps):
+def e2e_lines(n_trials, true_points, generator, reps, metric="llh", method="poisson"):
     from pisa_amd import kernels as K
     from pisa_amd.analysis import ensemble as en
 
     side, n_b = 30, 128
     hist = _templates(side * side, n_b, seed=3)
-    grid = en.TemplateGrid(K.to_device(hist), K.to_device(0.0 * hist), np.zeros((side * side, 2)), None, None, "llh")
-    grid._host["hist"] = hist
+    sumw2 = (0.0 if (metric, method) == ("llh", "poisson") else 0.3) * hist
+    grid = en.TemplateGrid(K.to_device(hist), K.to_device(sumw2), np.zeros((side * side, 2)), None, None, metric)
+    grid._host["hist"], grid._host["sumw2"] = hist, sumw2
     points = None if true_points is None else list(range(0, side * side, max(1, side * side // true_points)))[:true_points]
     generators = ("host", "device") if generator == "both" else (generator,)
     warm = points[:2] if points is not None else [0, 1]
     for g in generators:                   # (first launches, allocator, scipy's first call: the timed shape, two points)
-        en.feldman_cousins(grid, "llh", n_trials, random_state=1, true_points=warm, generator=g)
+        en.feldman_cousins(grid, metric, n_trials, random_state=1, true_points=warm, generator=g, method=method)
     runs = {g: [] for g in generators}
     for _ in range(reps):                  # the generators alternate: what else the machine does meets both alike
         for g in generators:
-            runs[g].append(_e2e_once(en, grid, n_trials, points, g))
+            runs[g].append(_e2e_once(en, grid, n_trials, points, g, metric, method))
     for g in generators:
         walls = [r[0] for r in runs[g]]
         wall, timings, crit = sorted(runs[g], key=lambda r: r[0])[len(walls) // 2]
         print(json.dumps(dict(workload="feldman_cousins", generator=g, grid="%dx%d" % (side, side), B=n_b, T=n_trials,
-                              metric="llh", true_points=crit.shape[0], runs=len(walls), wall_s=round(wall, 3),
+                              metric=metric, method=method, true_points=crit.shape[0], runs=len(walls), wall_s=round(wall, 3),
                               wall_s_all=[round(w, 3) for w in walls], draw_s=round(timings["draw"], 3),
                               upload_s=round(timings["upload"], 3), kernels_s=round(timings["kernels"], 3),
                               other_s=round(wall - timings["draw"] - timings["upload"] - timings["kernels"], 3),
-                              crit90_mean=round(float(crit[:, 1].mean()), 6))), flush=True)
+                              crit90_mean=round(float(crit[:, 1].mean()), 6),
+                              crit90_first=[round(float(c), 6) for c in crit[:4, 1]])), flush=True)
 
 
 def main():
@@ -302,6 +323,8 @@ def main():
     ap.add_argument("--generator", choices=("host", "device", "both"), default="host",
                     help="who draws the pseudo-data of the end-to-end run")
     ap.add_argument("--e2e-reps", type=int, default=3, help="timed end-to-end runs per generator (median)")
+    ap.add_argument("--metric", default="llh", help="the metric of the end-to-end run")
+    ap.add_argument("--method", default="poisson", help="the fluctuation method of the end-to-end run")
     ap.add_argument("--profiled", type=int, default=0, metavar="J",
                     help="also time the profiled reduced form with J fitted nuisance parameters (1 to 8)")
     ap.add_argument("--mc", action="store_true",
@@ -320,7 +343,7 @@ def main():
     if not args.skip_draw:
         draw_lines(args.reps)
     if not args.skip_e2e:
-        e2e_lines(int(args.trials), args.true_points, args.generator, args.e2e_reps)
+        e2e_lines(int(args.trials), args.true_points, args.generator, args.e2e_reps, args.metric, args.method)
 
 
 if __name__ == "__main__":
