@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/pisa_hip.h"
 
 #define PISA_API extern "C" __attribute__((visibility("default")))
@@ -53,6 +55,35 @@ inline const char *dev_env_str(const char *name) { return getenv(name); }
 #endif
 
 inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
+
+// A device buffer of doubles that grows on demand and never shrinks: the scratch of an entry point between its
+// launches.  An instance is a file's static, one per process: calls that use it on different streams must not
+// overlap.  Instances stay apart, so calls into different entry points share no memory.
+struct DeviceScratch {
+    double *ptr = nullptr;
+    int64_t doubles = 0;
+    int reserve(int64_t n, double **w) {
+        if (n > doubles) {
+            if (ptr) (void)hipFree(ptr);   // (waits for the launches that still read it)
+            ptr = nullptr;
+            doubles = 0;
+            PISA_TRY_HIP(hipMalloc(&ptr, (size_t)n * sizeof(double)));
+            doubles = n;
+        }
+        *w = ptr;
+        return PISA_HIP_OK;
+    }
+};
+
+// a run-time value as a template argument: f(std::integral_constant<int, V>) for the V that equals `value`, the
+// last V where none does (callers check the range first)
+template <int V0, int... Vs, class F>
+inline int dispatch_int(int value, F &&f) {
+    if constexpr (sizeof...(Vs) == 0)
+        return f(std::integral_constant<int, V0>{});
+    else
+        return value == V0 ? f(std::integral_constant<int, V0>{}) : dispatch_int<Vs...>(value, f);
+}
 
 // Regular (linear, equal-width) binning as the kernels see it
 // (fast_histogram rule / translation.py:417-456): bin = (int)((x - min) * norm)

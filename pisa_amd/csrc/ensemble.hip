@@ -75,8 +75,7 @@ ens_direct_kernel(const double *__restrict__ D, const double *__restrict__ E, co
     const int n_kt = ens_tiles(K, ED_TILE);
     const int kt_begin = REDUCE ? 0 : (int)blockIdx.y, kt_end = REDUCE ? n_kt : (int)blockIdx.y + 1;
     const bool use_s2 = WITH_S2 && S2 != nullptr;
-    double best_v = 0.0, at_v = 0.0;
-    int best_k = -1;
+    EnsOut<MAXIMISE, REDUCE> res;
     bool negative = false;
     for (int kt = kt_begin; kt < kt_end; kt++) {
         const int64_t k = (int64_t)kt * ED_TILE + ki;
@@ -112,29 +111,9 @@ ens_direct_kernel(const double *__restrict__ D, const double *__restrict__ E, co
         }
         double acc = sum + comp;
         if (KIND == PISA_HIP_METRIC_CHI2 && !differs) acc = 0.0;   // stats.py:160-161
-        if (t < T && k < K) {
-            if (REDUCE) {
-                const double v = offset ? acc + offset[k] : acc;
-                if (ens_better<MAXIMISE>(v, (int)k, best_v, best_k)) {
-                    best_v = v;
-                    best_k = (int)k;
-                }
-                if ((int)k == k0) at_v = v;
-            } else {
-                out[t * K + k] = acc;
-            }
-        }
+        if (t < T && k < K) res.entry(acc, t, k, K, offset, k0, out);
     }
-    if (REDUCE) {
-        ens_join16<MAXIMISE>(best_v, best_k);
-        if (t < T) {
-            if (ki == 0) {
-                best[t] = best_v;
-                arg[t] = best_k;
-            }
-            if (ki == (k0 & 15)) at[t] = at_v;
-        }
-    }
+    res.finish(t, T, ki, k0, best, arg, at);
     if (negative) status[0] = PISA_HIP_ERR_NEGATIVE;   // (every writer stores the same word)
 }
 
@@ -226,6 +205,7 @@ ens_product_kernel(const double *__restrict__ D, const double *__restrict__ Lp, 
     const int64_t t0 = (int64_t)blockIdx.x * EP_TILE;
     const int n_kt = ens_tiles(K, EP_TILE);
     const int kt_begin = REDUCE ? 0 : (int)blockIdx.y, kt_end = REDUCE ? n_kt : (int)blockIdx.y + 1;
+    // (`EnsOut` in its four-row form, spelled out: four instances of the struct change the kernel's code, EXPERIMENTS.md)
     double best_v[4] = {0.0, 0.0, 0.0, 0.0}, at_v[4] = {0.0, 0.0, 0.0, 0.0};
     int best_k[4] = {-1, -1, -1, -1};
     double2 c_t[4];
@@ -327,93 +307,56 @@ ens_product_kernel(const double *__restrict__ D, const double *__restrict__ Lp, 
     }
 }
 
-// preparation buffers of the product form (grown on demand; one per process, like the scratch of pisa_hip_metric)
-static double *g_ens_work = nullptr;
-static int64_t g_ens_doubles = 0;
 
-static int ens_workspace(int64_t doubles, double **w) {
-    if (doubles > g_ens_doubles) {
-        if (g_ens_work) (void)hipFree(g_ens_work);   // (waits for the launches that still read it)
-        g_ens_work = nullptr;
-        g_ens_doubles = 0;
-        PISA_TRY_HIP(hipMalloc(&g_ens_work, (size_t)doubles * sizeof(double)));
-        g_ens_doubles = doubles;
-    }
-    *w = g_ens_work;
-    return PISA_HIP_OK;
-}
+
+// preparation buffers of the product form
+static DeviceScratch g_ens_work;
 
 template <int KIND, bool REDUCE>
-static int ens_launch_direct(const double *D, const double *E, const double *S2, const double *offset, int k0, int T,
-                             int K, int64_t B, double *out, double *best, int32_t *arg, double *at, int32_t *status,
-                             hipStream_t stream) {
+static int ens_launch_direct(const EnsArgs &a) {
+    const int T = (int)a.T, K = (int)a.K;
     const dim3 grid((unsigned)ens_tiles(T, ED_TILE), REDUCE ? 1u : (unsigned)ens_tiles(K, ED_TILE));
-    hipLaunchKernelGGL((ens_direct_kernel<KIND, REDUCE>), grid, dim3(ENS_THREADS), 0, stream, D, E, S2, offset, k0, T,
-                       K, B, out, best, arg, at, status);
+    hipLaunchKernelGGL((ens_direct_kernel<KIND, REDUCE>), grid, dim3(ENS_THREADS), 0, as_stream(a.stream), a.D, a.E,
+                       a.S2, a.offset, a.k0, T, K, a.B, a.out, a.best, a.arg, a.at, a.status);
     PISA_CHECK_LAUNCH("ens_direct_kernel");
     return PISA_HIP_OK;
 }
 
 template <int KIND, bool REDUCE>
-static int ens_launch_product(const double *D, const double *E, const double *offset, int k0, int T, int K, int64_t B,
-                              double *out, double *best, int32_t *arg, double *at, int32_t *status,
-                              hipStream_t stream) {
+static int ens_launch_product(const EnsArgs &a) {
     constexpr bool LLH = KIND == PISA_HIP_METRIC_LLH;
-    const int64_t Bp = (B + 3) / 4 * 4;
+    const int T = (int)a.T, K = (int)a.K;
+    const int64_t B = a.B, Bp = (B + 3) / 4 * 4;
+    hipStream_t stream = as_stream(a.stream);
     double *w;
-    const int rc = ens_workspace((int64_t)K * Bp * (LLH ? 2 : 1) + 2 * ((int64_t)K + T), &w);
+    const int rc = g_ens_work.reserve((int64_t)K * Bp * (LLH ? 2 : 1) + 2 * ((int64_t)K + T), &w);
     if (rc != PISA_HIP_OK) return rc;
     double *Lp = w, *NLp = LLH ? Lp + (int64_t)K * Bp : nullptr;
     double2 *s = reinterpret_cast<double2 *>(w + (int64_t)K * Bp * (LLH ? 2 : 1)), *c = s + K;   // (16-byte aligned: Bp is a multiple of 4)
     const unsigned n_prep = (unsigned)(ens_tiles(K, EPREP_ROWS) + ens_tiles(T, EPREP_ROWS));
-    hipLaunchKernelGGL((ens_prep_kernel<KIND>), dim3(n_prep), dim3(ENS_THREADS), 0, stream, D, E, T, K, B, Bp, Lp, NLp,
-                       s, c, status);
+    hipLaunchKernelGGL((ens_prep_kernel<KIND>), dim3(n_prep), dim3(ENS_THREADS), 0, stream, a.D, a.E, T, K, B, Bp, Lp,
+                       NLp, s, c, a.status);
     PISA_CHECK_LAUNCH("ens_prep_kernel");
     const dim3 grid((unsigned)ens_tiles(T, EP_TILE), REDUCE ? 1u : (unsigned)ens_tiles(K, EP_TILE));
-    hipLaunchKernelGGL((ens_product_kernel<KIND, REDUCE>), grid, dim3(ENS_THREADS), 0, stream, D, Lp, NLp, s, c,
-                       offset, k0, T, K, B, Bp, out, best, arg, at);
+    hipLaunchKernelGGL((ens_product_kernel<KIND, REDUCE>), grid, dim3(ENS_THREADS), 0, stream, a.D, Lp, NLp, s, c,
+                       a.offset, a.k0, T, K, B, Bp, a.out, a.best, a.arg, a.at);
     PISA_CHECK_LAUNCH("ens_product_kernel");
     return PISA_HIP_OK;
 }
 
 template <bool REDUCE>
-static int ens_run(int32_t kind, int32_t form, const double *D, const double *E, const double *S2,
-                   const double *offset, int32_t k0, int64_t T, int64_t K, int64_t B, double *out, double *best,
-                   int32_t *arg, double *at, int32_t *status, void *stream) {
+static int ens_run(int32_t kind, int32_t form, const EnsArgs &a) {
     if (kind < PISA_HIP_METRIC_LLH || kind > PISA_HIP_METRIC_MOD_CHI2) return PISA_HIP_ERR_INVALID;
     if (form < PISA_HIP_ENSEMBLE_AUTO || form > PISA_HIP_ENSEMBLE_PRODUCT) return PISA_HIP_ERR_INVALID;
     const bool llh_kind = kind <= PISA_HIP_METRIC_POISSON_LLH;
     if (form == PISA_HIP_ENSEMBLE_PRODUCT && !llh_kind) return PISA_HIP_ERR_INVALID;
-    if (T < 1 || K < 1 || B < 1 || T > 0x7FFFFFFF || K > 0x7FFFFFFF || B > 0x7FFFFFFF) return PISA_HIP_ERR_INVALID;
-    // (with the limits above no product of two sizes overflows int64)
-    if (!D || !E || !status) return PISA_HIP_ERR_INVALID;
-    if (REDUCE ? (!best || !arg || !at || k0 < 0 || k0 >= K) : !out) return PISA_HIP_ERR_INVALID;
-    // the full matrix has one workgroup row per template tile
-    if (!REDUCE && ens_tiles(K, ED_TILE) > 65535) return PISA_HIP_ERR_INVALID;
-    const bool product = llh_kind && form != PISA_HIP_ENSEMBLE_DIRECT;
-    hipStream_t st = as_stream(stream);
-    const int t = (int)T, k = (int)K;
-    if (product) {
-        if (kind == PISA_HIP_METRIC_LLH)
-            return ens_launch_product<PISA_HIP_METRIC_LLH, REDUCE>(D, E, offset, k0, t, k, B, out, best, arg, at,
-                                                                  status, st);
-        return ens_launch_product<PISA_HIP_METRIC_POISSON_LLH, REDUCE>(D, E, offset, k0, t, k, B, out, best, arg, at,
-                                                                      status, st);
-    }
-    switch (kind) {
-    case PISA_HIP_METRIC_LLH:
-        return ens_launch_direct<PISA_HIP_METRIC_LLH, REDUCE>(D, E, S2, offset, k0, t, k, B, out, best, arg, at,
-                                                             status, st);
-    case PISA_HIP_METRIC_POISSON_LLH:
-        return ens_launch_direct<PISA_HIP_METRIC_POISSON_LLH, REDUCE>(D, E, S2, offset, k0, t, k, B, out, best, arg,
-                                                                     at, status, st);
-    case PISA_HIP_METRIC_CHI2:
-        return ens_launch_direct<PISA_HIP_METRIC_CHI2, REDUCE>(D, E, S2, offset, k0, t, k, B, out, best, arg, at,
-                                                              status, st);
-    default:
-        return ens_launch_direct<PISA_HIP_METRIC_MOD_CHI2, REDUCE>(D, E, S2, offset, k0, t, k, B, out, best, arg, at,
-                                                                  status, st);
-    }
+    if (!ens_check_matrix<REDUCE>(a, ED_TILE)) return PISA_HIP_ERR_INVALID;
+    if (llh_kind && form != PISA_HIP_ENSEMBLE_DIRECT)
+        return dispatch_int<PISA_HIP_METRIC_LLH, PISA_HIP_METRIC_POISSON_LLH>(
+            kind, [&](auto c) { return ens_launch_product<decltype(c)::value, REDUCE>(a); });
+    return dispatch_int<PISA_HIP_METRIC_LLH, PISA_HIP_METRIC_POISSON_LLH, PISA_HIP_METRIC_CHI2,
+                        PISA_HIP_METRIC_MOD_CHI2>(
+        kind, [&](auto c) { return ens_launch_direct<decltype(c)::value, REDUCE>(a); });
 }
 
 }  // namespace pisa
@@ -423,14 +366,14 @@ using namespace pisa;
 PISA_API int pisa_hip_metric_matrix(int32_t kind, int32_t form, const double *d_data, const double *d_expected,
                                     const double *d_sigma2, int64_t n_trials, int64_t n_templates, int64_t n_bins,
                                     double *d_out, int32_t *d_status, void *stream) {
-    return ens_run<false>(kind, form, d_data, d_expected, d_sigma2, nullptr, 0, n_trials, n_templates, n_bins, d_out,
-                          nullptr, nullptr, nullptr, d_status, stream);
+    return ens_run<false>(kind, form, {d_data, d_expected, d_sigma2, nullptr, 0, n_trials, n_templates, n_bins, d_out,
+                                       nullptr, nullptr, nullptr, d_status, stream});
 }
 
 PISA_API int pisa_hip_metric_matrix_best(int32_t kind, int32_t form, const double *d_data, const double *d_expected,
                                          const double *d_sigma2, const double *d_offset, int32_t k0,
                                          int64_t n_trials, int64_t n_templates, int64_t n_bins, double *d_best,
                                          int32_t *d_arg, double *d_at, int32_t *d_status, void *stream) {
-    return ens_run<true>(kind, form, d_data, d_expected, d_sigma2, d_offset, k0, n_trials, n_templates, n_bins, nullptr,
-                         d_best, d_arg, d_at, d_status, stream);
+    return ens_run<true>(kind, form, {d_data, d_expected, d_sigma2, d_offset, k0, n_trials, n_templates, n_bins,
+                                      nullptr, d_best, d_arg, d_at, d_status, stream});
 }

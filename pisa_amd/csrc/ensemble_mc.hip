@@ -28,9 +28,8 @@
 // What is guaranteed, as in ensemble.hip: the bits of entry (t, k) depend on row t of D and row k of E / S2 only.
 // A prepared value is a function of its own bin, a node table of its own (mu, s); every sum over bins is ONE chain
 // per lane in ascending bin order with the rounding errors kept (`ens_two_sum`, ensemble_device.hpp)
-// and added last; no atomic touches the result and no pair's bins are split over lanes.  The reduced form keeps per
-// lane the best value of its column class over the template tiles in ascending order (strict comparison: the
-// smallest k wins a tie) and joins the 16 columns at the end.
+// and added last; no atomic touches the result and no pair's bins are split over lanes.  The full and the reduced
+// output are those of every kernel in which a lane owns a pair (`EnsOut`, ensemble_device.hpp).
 #include "common.hpp"
 #include "ensemble_device.hpp"
 #include "metric_device.hpp"
@@ -154,37 +153,6 @@ emc_prep_kernel(const double *__restrict__ D, const double *__restrict__ E, cons
     if (negative) status[0] = PISA_HIP_ERR_NEGATIVE;   // (every writer stores the same word)
 }
 
-// what every kernel below does with its lane's entry
-template <bool MAXIMISE, bool REDUCE>
-struct EmcOut {
-    double best_v = 0.0, at_v = 0.0;
-    int best_k = -1;
-    __device__ __forceinline__ void entry(double acc, int64_t t, int64_t k, int K, const double *offset, int k0,
-                                          double *out) {
-        if (REDUCE) {
-            const double v = offset ? acc + offset[k] : acc;
-            if (ens_better<MAXIMISE>(v, (int)k, best_v, best_k)) {
-                best_v = v;
-                best_k = (int)k;
-            }
-            if ((int)k == k0) at_v = v;
-        } else {
-            out[t * K + k] = acc;
-        }
-    }
-    __device__ __forceinline__ void finish(int64_t t, int T, int ki, int k0, double *best, int32_t *arg, double *at) {
-        if (!REDUCE) return;
-        ens_join16<MAXIMISE>(best_v, best_k);
-        if (t < T) {
-            if (ki == 0) {
-                best[t] = best_v;
-                arg[t] = best_k;
-            }
-            if (ki == (k0 & 15)) at[t] = at_v;
-        }
-    }
-};
-
 // ------------------------------------------------------------------ correct_chi2, mcllh_mean, mcllh_eff
 // grid.x: strips of 16 trials; FULL: grid.y = tiles of 16 templates, REDUCE: the workgroup walks all of them
 template <int KIND, bool REDUCE>
@@ -202,7 +170,7 @@ emc_pair_kernel(const double *__restrict__ D, const double *__restrict__ P, cons
     const int64_t n_kb = (int64_t)K * B;
     const int n_kt = ens_tiles(K, EMC_TILE);
     const int kt_begin = REDUCE ? 0 : (int)blockIdx.y, kt_end = REDUCE ? n_kt : (int)blockIdx.y + 1;
-    EmcOut<MIX, REDUCE> res;
+    EnsOut<MIX, REDUCE> res;
     for (int kt = kt_begin; kt < kt_end; kt++) {
         const int64_t k = (int64_t)kt * EMC_TILE + ki;
         double sum = 0.0, comp = 0.0;
@@ -267,7 +235,7 @@ emc_conv_kernel(const double *__restrict__ D, const double *__restrict__ E, cons
     const int64_t n_kb = (int64_t)K * B;
     const int n_kt = ens_tiles(K, EMC_TILE);
     const int kt_begin = REDUCE ? 0 : (int)blockIdx.y, kt_end = REDUCE ? n_kt : (int)blockIdx.y + 1;
-    EmcOut<true, REDUCE> res;
+    EnsOut<true, REDUCE> res;
     for (int kt = kt_begin; kt < kt_end; kt++) {
         const int64_t k = (int64_t)kt * EMC_TILE + ki;
         const bool live = t < T && k < K;
@@ -314,81 +282,49 @@ emc_conv_kernel(const double *__restrict__ D, const double *__restrict__ E, cons
     res.finish(t, T, ki, k0, best, arg, at);
 }
 
-// preparation buffers (grown on demand; one per process, like those of the product form of ensemble.hip)
-static double *g_emc_work = nullptr;
-static int64_t g_emc_doubles = 0;
-
-static int emc_workspace(int64_t doubles, double **w) {
-    if (doubles > g_emc_doubles) {
-        if (g_emc_work) (void)hipFree(g_emc_work);   // (waits for the launches that still read it)
-        g_emc_work = nullptr;
-        g_emc_doubles = 0;
-        PISA_TRY_HIP(hipMalloc(&g_emc_work, (size_t)doubles * sizeof(double)));
-        g_emc_doubles = doubles;
-    }
-    *w = g_emc_work;
-    return PISA_HIP_OK;
-}
+// preparation buffers
+static DeviceScratch g_emc_work;
 
 template <int KIND, bool REDUCE>
-static int emc_launch(const double *D, const double *E, const double *S2, const double *offset, int k0, int T, int K,
-                      int64_t B, double *out, double *best, int32_t *arg, double *at, int32_t *status,
-                      hipStream_t stream) {
+static int emc_launch(const EnsArgs &a) {
     constexpr bool CONV = KIND == PISA_HIP_METRIC_CONV_LLH;
     constexpr int n_p = CONV ? EMC_PLANES_CONV : EMC_PLANES_CHEAP;
     constexpr int n_g = CONV ? 2 : (KIND == PISA_HIP_METRIC_CORRECT_CHI2 ? 0 : 1);
-    const int64_t n_kb = (int64_t)K * B, n_tb = (int64_t)T * B;
+    const int T = (int)a.T, K = (int)a.K;
+    const int64_t B = a.B, n_kb = (int64_t)K * B, n_tb = (int64_t)T * B;
+    hipStream_t stream = as_stream(a.stream);
     double *w;
-    const int rc = emc_workspace(n_p * n_kb + n_g * n_tb + 1, &w);
+    const int rc = g_emc_work.reserve(n_p * n_kb + n_g * n_tb + 1, &w);
     if (rc != PISA_HIP_OK) return rc;
     double *P = w, *G = w + n_p * n_kb;
     const int64_t n_el = n_kb + (n_g ? n_tb : 0);
     hipLaunchKernelGGL((emc_prep_kernel<KIND>), dim3((unsigned)((n_el + EMC_THREADS - 1) / EMC_THREADS)),
-                       dim3(EMC_THREADS), 0, stream, D, E, S2, n_g ? n_tb : (int64_t)0, n_kb, P, G, status);
+                       dim3(EMC_THREADS), 0, stream, a.D, a.E, a.S2, n_g ? n_tb : (int64_t)0, n_kb, P, G, a.status);
     PISA_CHECK_LAUNCH("emc_prep_kernel");
     const dim3 grid((unsigned)ens_tiles(T, EMC_TILE), REDUCE ? 1u : (unsigned)ens_tiles(K, EMC_TILE));
     if constexpr (CONV) {
-        hipLaunchKernelGGL((emc_conv_kernel<REDUCE>), grid, dim3(EMC_THREADS), 0, stream, D, E, P, G, offset, k0, T, K,
-                           B, n_tb, out, best, arg, at);
+        hipLaunchKernelGGL((emc_conv_kernel<REDUCE>), grid, dim3(EMC_THREADS), 0, stream, a.D, a.E, P, G, a.offset,
+                           a.k0, T, K, B, n_tb, a.out, a.best, a.arg, a.at);
         PISA_CHECK_LAUNCH("emc_conv_kernel");
     } else {
-        hipLaunchKernelGGL((emc_pair_kernel<KIND, REDUCE>), grid, dim3(EMC_THREADS), 0, stream, D, P, G, offset, k0, T,
-                           K, B, out, best, arg, at);
+        hipLaunchKernelGGL((emc_pair_kernel<KIND, REDUCE>), grid, dim3(EMC_THREADS), 0, stream, a.D, P, G, a.offset,
+                           a.k0, T, K, B, a.out, a.best, a.arg, a.at);
         PISA_CHECK_LAUNCH("emc_pair_kernel");
     }
     return PISA_HIP_OK;
 }
 
 template <bool REDUCE>
-static int emc_run(int32_t kind, const double *D, const double *E, const double *S2, const double *offset, int32_t k0,
-                   int64_t T, int64_t K, int64_t B, double *out, double *best, int32_t *arg, double *at,
-                   int32_t *status, void *stream) {
+static int emc_run(int32_t kind, const EnsArgs &a) {
     if (kind != PISA_HIP_METRIC_CORRECT_CHI2 && kind != PISA_HIP_METRIC_MCLLH_MEAN &&
         kind != PISA_HIP_METRIC_MCLLH_EFF && kind != PISA_HIP_METRIC_CONV_LLH)
         return PISA_HIP_ERR_INVALID;
-    if (T < 1 || K < 1 || B < 1 || T > 0x7FFFFFFF || K > 0x7FFFFFFF || B > 0x7FFFFFFF) return PISA_HIP_ERR_INVALID;
-    // (with the limits above no product of two sizes overflows int64)
-    if (!D || !E || !S2 || !status) return PISA_HIP_ERR_INVALID;
-    if (REDUCE ? (!best || !arg || !at || k0 < 0 || k0 >= K) : !out) return PISA_HIP_ERR_INVALID;
-    // the full matrix has one workgroup row per template tile; the preparation one thread per bin of every row
-    if (!REDUCE && ens_tiles(K, EMC_TILE) > 65535) return PISA_HIP_ERR_INVALID;
-    if ((T + K) * B > (int64_t)0x7FFFFFFF * EMC_THREADS) return PISA_HIP_ERR_INVALID;
-    hipStream_t st = as_stream(stream);
-    const int t = (int)T, k = (int)K;
-    switch (kind) {
-    case PISA_HIP_METRIC_CORRECT_CHI2:
-        return emc_launch<PISA_HIP_METRIC_CORRECT_CHI2, REDUCE>(D, E, S2, offset, k0, t, k, B, out, best, arg, at,
-                                                               status, st);
-    case PISA_HIP_METRIC_MCLLH_MEAN:
-        return emc_launch<PISA_HIP_METRIC_MCLLH_MEAN, REDUCE>(D, E, S2, offset, k0, t, k, B, out, best, arg, at,
-                                                             status, st);
-    case PISA_HIP_METRIC_MCLLH_EFF:
-        return emc_launch<PISA_HIP_METRIC_MCLLH_EFF, REDUCE>(D, E, S2, offset, k0, t, k, B, out, best, arg, at, status,
-                                                            st);
-    default:
-        return emc_launch<PISA_HIP_METRIC_CONV_LLH, REDUCE>(D, E, S2, offset, k0, t, k, B, out, best, arg, at, status,
-                                                           st);
-    }
+    if (!ens_check_matrix<REDUCE>(a, EMC_TILE) || !a.S2) return PISA_HIP_ERR_INVALID;
+    // the preparation has one thread per bin of every row
+    if ((a.T + a.K) * a.B > (int64_t)0x7FFFFFFF * EMC_THREADS) return PISA_HIP_ERR_INVALID;
+    return dispatch_int<PISA_HIP_METRIC_CORRECT_CHI2, PISA_HIP_METRIC_MCLLH_MEAN, PISA_HIP_METRIC_MCLLH_EFF,
+                        PISA_HIP_METRIC_CONV_LLH>(
+        kind, [&](auto c) { return emc_launch<decltype(c)::value, REDUCE>(a); });
 }
 
 }  // namespace pisa
@@ -398,14 +334,14 @@ using namespace pisa;
 PISA_API int pisa_hip_metric_matrix_mc(int32_t kind, const double *d_data, const double *d_expected,
                                        const double *d_sigma2, int64_t n_trials, int64_t n_templates, int64_t n_bins,
                                        double *d_out, int32_t *d_status, void *stream) {
-    return emc_run<false>(kind, d_data, d_expected, d_sigma2, nullptr, 0, n_trials, n_templates, n_bins, d_out, nullptr,
-                          nullptr, nullptr, d_status, stream);
+    return emc_run<false>(kind, {d_data, d_expected, d_sigma2, nullptr, 0, n_trials, n_templates, n_bins, d_out,
+                                 nullptr, nullptr, nullptr, d_status, stream});
 }
 
 PISA_API int pisa_hip_metric_matrix_mc_best(int32_t kind, const double *d_data, const double *d_expected,
                                             const double *d_sigma2, const double *d_offset, int32_t k0,
                                             int64_t n_trials, int64_t n_templates, int64_t n_bins, double *d_best,
                                             int32_t *d_arg, double *d_at, int32_t *d_status, void *stream) {
-    return emc_run<true>(kind, d_data, d_expected, d_sigma2, d_offset, k0, n_trials, n_templates, n_bins, nullptr,
-                         d_best, d_arg, d_at, d_status, stream);
+    return emc_run<true>(kind, {d_data, d_expected, d_sigma2, d_offset, k0, n_trials, n_templates, n_bins, nullptr,
+                                d_best, d_arg, d_at, d_status, stream});
 }

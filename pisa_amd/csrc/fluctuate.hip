@@ -79,43 +79,33 @@ static int fluct_launch(const double *d_mu, const double *d_sigma, int64_t n_bin
     return PISA_HIP_OK;
 }
 
-static bool fluct_check(const double *d_mu, int64_t n_bins, int64_t n_trials, uint32_t first_trial,
-                        const double *d_out, const int32_t *d_status) {
+static bool fluct_check(const double *d_mu, const double *d_sigma, int32_t method, int64_t n_bins, int64_t n_trials,
+                        uint32_t first_trial, const double *d_out, const int32_t *d_status) {
     if (!d_mu || !d_out || !d_status) return false;
     if (n_bins < 1 || n_trials < 1 || n_bins > 0x7FFFFFFF || n_trials > 0x7FFFFFFF) return false;
-    return (int64_t)first_trial + n_trials <= ((int64_t)1 << 32);
+    if ((int64_t)first_trial + n_trials > ((int64_t)1 << 32)) return false;
+    if (method < FL_POISSON || method > FL_GAUSS_POISSON) return false;
+    return method == FL_POISSON || d_sigma;
 }
 
 }  // namespace pisa
 
 using namespace pisa;
 
-PISA_API int pisa_hip_poisson_fluctuate(const double *d_mu, int64_t n_bins, int64_t n_trials, uint64_t seed,
-                                        uint32_t stream_id, uint32_t first_trial, double *d_out, int32_t *d_status,
-                                        void *stream) {
-    if (!fluct_check(d_mu, n_bins, n_trials, first_trial, d_out, d_status)) return PISA_HIP_ERR_INVALID;
-    return fluct_launch<FL_POISSON>(d_mu, nullptr, n_bins, n_trials, seed, stream_id, first_trial, d_out, d_status,
-                                    stream);
-}
-
 PISA_API int pisa_hip_fluctuate(const double *d_mu, const double *d_sigma, int32_t method, int64_t n_bins,
                                 int64_t n_trials, uint64_t seed, uint32_t stream_id, uint32_t first_trial,
                                 double *d_out, int32_t *d_status, void *stream) {
-    if (!fluct_check(d_mu, n_bins, n_trials, first_trial, d_out, d_status)) return PISA_HIP_ERR_INVALID;
-    if (method < FL_POISSON || method > FL_GAUSS_POISSON) return PISA_HIP_ERR_INVALID;
-    if (method != FL_POISSON && !d_sigma) return PISA_HIP_ERR_INVALID;
-    switch (method) {
-    case FL_POISSON:
-        return fluct_launch<FL_POISSON>(d_mu, d_sigma, n_bins, n_trials, seed, stream_id, first_trial, d_out, d_status,
-                                        stream);
-    case FL_SCALED_POISSON:
-        return fluct_launch<FL_SCALED_POISSON>(d_mu, d_sigma, n_bins, n_trials, seed, stream_id, first_trial, d_out,
-                                               d_status, stream);
-    case FL_GAUSS:
-        return fluct_launch<FL_GAUSS>(d_mu, d_sigma, n_bins, n_trials, seed, stream_id, first_trial, d_out, d_status,
-                                      stream);
-    default:
-        return fluct_launch<FL_GAUSS_POISSON>(d_mu, d_sigma, n_bins, n_trials, seed, stream_id, first_trial, d_out,
-                                              d_status, stream);
-    }
+    if (!fluct_check(d_mu, d_sigma, method, n_bins, n_trials, first_trial, d_out, d_status))
+        return PISA_HIP_ERR_INVALID;
+    return dispatch_int<FL_POISSON, FL_SCALED_POISSON, FL_GAUSS, FL_GAUSS_POISSON>(method, [&](auto m) {
+        return fluct_launch<decltype(m)::value>(d_mu, d_sigma, n_bins, n_trials, seed, stream_id, first_trial, d_out,
+                                                d_status, stream);
+    });
+}
+
+PISA_API int pisa_hip_poisson_fluctuate(const double *d_mu, int64_t n_bins, int64_t n_trials, uint64_t seed,
+                                        uint32_t stream_id, uint32_t first_trial, double *d_out, int32_t *d_status,
+                                        void *stream) {
+    return pisa_hip_fluctuate(d_mu, nullptr, FL_POISSON, n_bins, n_trials, seed, stream_id, first_trial, d_out,
+                              d_status, stream);
 }

@@ -21,9 +21,10 @@
 // reduced form compares the same doubles in ascending k with a strict comparison (the smallest k wins a tie).  Where
 // a call has too few strips to fill the device the templates of a strip are split over workgroups in contiguous ranges
 // and a second launch joins the ranges in ascending order with the same comparison: whatever the split, the output
-// is that of one walk over all templates.  The join buffer belongs to the library, one per process: reduced-form
-// calls on different streams must not overlap (as the product form of ensemble.hip).
+// is that of one walk over all templates.  The join buffer is a `DeviceScratch` (common.hpp): reduced-form calls on
+// different streams must not overlap.
 #include "common.hpp"
+#include "ensemble_device.hpp"
 #include "profile_device.hpp"
 
 namespace pisa {
@@ -235,21 +236,8 @@ profile_join_kernel(const PfArgs a, int J) {
     for (int j = 0; j < J; j++) a.eta_best[t * J + j] = a.ws_eta[o * J + j];
 }
 
-// join buffer of the split reduced form (grown on demand; one per process, like the buffers of ensemble.hip)
-static double *g_pf_work = nullptr;
-static int64_t g_pf_doubles = 0;
-
-static int pf_workspace(int64_t doubles, double **w) {
-    if (doubles > g_pf_doubles) {
-        if (g_pf_work) (void)hipFree(g_pf_work);   // (waits for the launches that still read it)
-        g_pf_work = nullptr;
-        g_pf_doubles = 0;
-        PISA_TRY_HIP(hipMalloc(&g_pf_work, (size_t)doubles * sizeof(double)));
-        g_pf_doubles = doubles;
-    }
-    *w = g_pf_work;
-    return PISA_HIP_OK;
-}
+// join buffer of the split reduced form
+static DeviceScratch g_pf_work;
 
 template <int KIND, int J, bool REDUCE>
 static int pf_launch(const PfArgs &a, unsigned blocks, hipStream_t stream) {
@@ -264,35 +252,19 @@ static int pf_launch(const PfArgs &a, unsigned blocks, hipStream_t stream) {
     return PISA_HIP_OK;
 }
 
-template <int KIND, bool REDUCE>
-static int pf_launch_j(int J, const PfArgs &a, unsigned blocks, hipStream_t stream) {
-    switch (J) {
-    case 1: return pf_launch<KIND, 1, REDUCE>(a, blocks, stream);
-    case 2: return pf_launch<KIND, 2, REDUCE>(a, blocks, stream);
-    case 3: return pf_launch<KIND, 3, REDUCE>(a, blocks, stream);
-    case 4: return pf_launch<KIND, 4, REDUCE>(a, blocks, stream);
-    case 5: return pf_launch<KIND, 5, REDUCE>(a, blocks, stream);
-    case 6: return pf_launch<KIND, 6, REDUCE>(a, blocks, stream);
-    case 7: return pf_launch<KIND, 7, REDUCE>(a, blocks, stream);
-    default: return pf_launch<KIND, 8, REDUCE>(a, blocks, stream);
-    }
-}
-
 template <bool REDUCE>
 static int pf_run(int32_t kind, int64_t response_stride_k, int32_t n_params, int32_t max_iter, int64_t T, int64_t K,
                   int64_t B, PfArgs a, void *stream) {
     if (kind < PISA_HIP_METRIC_LLH || kind > PISA_HIP_METRIC_MOD_CHI2) return PISA_HIP_ERR_INVALID;
     if (n_params < 1 || n_params > PISA_HIP_PROFILE_MAX_PARAMS) return PISA_HIP_ERR_INVALID;
     if (max_iter < 0 || max_iter > PF_MAX_ITER) return PISA_HIP_ERR_INVALID;
-    if (T < 1 || K < 1 || B < 1 || T > 0x7FFFFFFF || K > 0x7FFFFFFF || B > 0x7FFFFFFF) return PISA_HIP_ERR_INVALID;
-    // (with the limits above no product of two sizes overflows int64)
+    if (!ens_check_sizes(T, K, B)) return PISA_HIP_ERR_INVALID;
     if (!a.D || !a.E || !a.R || !a.status) return PISA_HIP_ERR_INVALID;
     if (kind == PISA_HIP_METRIC_MOD_CHI2 && !a.S2) return PISA_HIP_ERR_INVALID;
     // the response of template k begins k * stride doubles in: 0 (shared by all templates) or whole [J][B] blocks
     if (response_stride_k != 0 && response_stride_k < (int64_t)n_params * B) return PISA_HIP_ERR_INVALID;
-    if (REDUCE ? (!a.best || !a.arg || !a.at || !a.eta_best || !a.eta_at || !a.trial_status || a.k0 < 0 || a.k0 >= K)
-               : (!a.value || !a.pair_status))
-        return PISA_HIP_ERR_INVALID;
+    if (!ens_check_outputs<REDUCE>(a.value, a.best, a.arg, a.at, a.k0, K)) return PISA_HIP_ERR_INVALID;
+    if (REDUCE ? (!a.eta_best || !a.eta_at || !a.trial_status) : !a.pair_status) return PISA_HIP_ERR_INVALID;
     const int64_t strips = (T + PF_LANES - 1) / PF_LANES;
     const int64_t blocks = REDUCE ? strips : strips * K;   // full: one workgroup per (strip, template)
     // (a grid holds at most 2^32 threads: 2^26 workgroups of 64 lanes)
@@ -314,7 +286,7 @@ static int pf_run(int32_t kind, int64_t response_stride_k, int32_t n_params, int
         if (n_split > 1) {
             const int64_t per = n_split * T;               // doubles: best, eta [J], and arg + flags as one more; + T
             double *w;
-            const int rc = pf_workspace(per * (2 + n_params) + T, &w);
+            const int rc = g_pf_work.reserve(per * (2 + n_params) + T, &w);
             if (rc != PISA_HIP_OK) return rc;
             a.n_split = (int)n_split;
             a.k_chunk = (int)chunk;
@@ -326,12 +298,11 @@ static int pf_run(int32_t kind, int64_t response_stride_k, int32_t n_params, int
         }
     }
     hipStream_t st = as_stream(stream);
-    switch (kind) {
-    case PISA_HIP_METRIC_LLH: return pf_launch_j<PF_LLH, REDUCE>(n_params, a, (unsigned)blocks, st);
-    case PISA_HIP_METRIC_POISSON_LLH: return pf_launch_j<PF_POISSON_LLH, REDUCE>(n_params, a, (unsigned)blocks, st);
-    case PISA_HIP_METRIC_CHI2: return pf_launch_j<PF_CHI2, REDUCE>(n_params, a, (unsigned)blocks, st);
-    default: return pf_launch_j<PF_MOD_CHI2, REDUCE>(n_params, a, (unsigned)blocks, st);
-    }
+    return dispatch_int<PF_LLH, PF_POISSON_LLH, PF_CHI2, PF_MOD_CHI2>(kind, [&](auto c) {
+        return dispatch_int<1, 2, 3, 4, 5, 6, 7, 8>(n_params, [&](auto j) {
+            return pf_launch<decltype(c)::value, decltype(j)::value, REDUCE>(a, (unsigned)blocks, st);
+        });
+    });
 }
 
 }  // namespace pisa

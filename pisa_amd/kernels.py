@@ -578,6 +578,23 @@ def kde_lattice_batch(jobs, origin, step, count, bw_method="silverman", adaptive
     return b.wait()
 
 
+def _check_status(status):
+    st = int(status.item())
+    if st != 0:
+        _lib.check(st)
+
+
+def _with_status(status, dev, launch):
+    """`launch(status word)` with the caller's word, which the caller reads; or with one allocated here and checked when
+    the launch has returned"""
+    if status is not None:
+        launch(status)
+        return
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    launch(status)
+    _check_status(status)
+
+
 def metric(kind, actual, expected, sigma2=None, per_bin=False, total_out=None, status=None):
     """Map.metric + nansum (map.py:1572-1604) on device.  `expected` (and
     `sigma2`) may be [n_maps, n_bins]; maps are summed in index order first.
@@ -590,6 +607,7 @@ def metric(kind, actual, expected, sigma2=None, per_bin=False, total_out=None, s
     if total_out is None:
         total_out = torch.empty(1, dtype=F8, device=dev)
     pb = torch.empty(n_bins, dtype=F8, device=dev) if per_bin else None
+    # (`_with_status` spelled out: this call is on the evaluation path of engine.py, where a closure costs 0.3 us of 7)
     own_status = status is None
     if own_status:
         status = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -598,15 +616,30 @@ def metric(kind, actual, expected, sigma2=None, per_bin=False, total_out=None, s
         total_out.data_ptr() if not total_out.is_cuda and total_out.is_pinned() else _ptr(total_out),
         _ptr(status), _stream()))
     if own_status:
-        st = int(status.item())
-        if st != 0:
-            _lib.check(st)
+        _check_status(status)
     return (total_out, pb) if per_bin else total_out
 
 
 # ------------------------------------------------------------------------- trial ensembles
 # the metrics that account for finite MC statistics: their own entry points (csrc/ensemble_mc.hip), one form
 ENSEMBLE_MC_KINDS = ("correct_chi2", "mcllh_mean", "mcllh_eff", "conv_llh")
+
+
+def _maps_args(what, data, expected, sigma2):
+    """data [T, B], expected [K, B] and sigma2 (None or [K, B]) checked and made contiguous"""
+    if data.dim() != 2 or expected.dim() != 2 or data.dtype != F8 or expected.dtype != F8:
+        raise ValueError("%s: data is [n_trials, n_bins] and expected [n_templates, n_bins], both float64" % what)
+    if sigma2 is not None and (sigma2.shape != expected.shape or sigma2.dtype != F8):
+        raise ValueError("%s: sigma2 has the shape and dtype of expected" % what)
+    return data.contiguous(), expected.contiguous(), None if sigma2 is None else sigma2.contiguous()
+
+
+def _offset_arg(what, offset, n_k):
+    if offset is None:
+        return None
+    if offset.shape != (n_k,) or offset.dtype != F8:
+        raise ValueError("%s: offset is float64 [n_templates]" % what)
+    return offset.contiguous()
 
 
 def _ensemble_args(kind, data, expected, sigma2, form):
@@ -620,12 +653,7 @@ def _ensemble_args(kind, data, expected, sigma2, form):
             raise ValueError("metric_matrix: '%s' has no product form" % kind)
         if sigma2 is None:
             raise ValueError("metric_matrix: '%s' needs sigma2" % kind)
-    if data.dim() != 2 or expected.dim() != 2 or data.dtype != F8 or expected.dtype != F8:
-        raise ValueError("metric_matrix: data is [n_trials, n_bins] and expected [n_templates, n_bins], both float64")
-    if sigma2 is not None and (sigma2.shape != expected.shape or sigma2.dtype != F8):
-        raise ValueError("metric_matrix: sigma2 has the shape and dtype of expected")
-    data, expected = data.contiguous(), expected.contiguous()
-    sigma2 = None if sigma2 is None else sigma2.contiguous()
+    data, expected, sigma2 = _maps_args("metric_matrix", data, expected, sigma2)
     # (a mismatch of the bin counts reaches the library as n_bins = 0: PISA_HIP_ERR_INVALID, nothing is launched)
     n_bins = data.shape[1] if data.shape[1] == expected.shape[1] else 0
     return data, expected, sigma2, data.shape[0], expected.shape[0], n_bins
@@ -641,19 +669,18 @@ def metric_matrix(kind, data, expected, sigma2=None, form="auto", status=None):
     data, expected, sigma2, n_t, n_k, n_bins = _ensemble_args(kind, data, expected, sigma2, form)
     dev = data.device
     out = torch.empty((n_t, n_k), dtype=F8, device=dev)
-    own_status = status is None
-    if own_status:
-        status = torch.zeros(1, dtype=torch.int32, device=dev)
-    if kind in ENSEMBLE_MC_KINDS:
-        _lib.check(_lib.lib().pisa_hip_metric_matrix_mc(
-            MAP_METRIC_KIND[kind], _ptr(data), _ptr(expected), _ptr(sigma2), n_t, n_k, n_bins, _ptr(out),
-            _ptr(status), _stream()))
-    else:
-        _lib.check(_lib.lib().pisa_hip_metric_matrix(
-            METRIC_KIND[kind], _lib.ENSEMBLE_FORMS.index(form), _ptr(data), _ptr(expected), _ptr(sigma2), n_t, n_k,
-            n_bins, _ptr(out), _ptr(status), _stream()))
-    if own_status:
-        _check_status(status)
+
+    def launch(status):
+        if kind in ENSEMBLE_MC_KINDS:
+            _lib.check(_lib.lib().pisa_hip_metric_matrix_mc(
+                MAP_METRIC_KIND[kind], _ptr(data), _ptr(expected), _ptr(sigma2), n_t, n_k, n_bins, _ptr(out),
+                _ptr(status), _stream()))
+        else:
+            _lib.check(_lib.lib().pisa_hip_metric_matrix(
+                METRIC_KIND[kind], _lib.ENSEMBLE_FORMS.index(form), _ptr(data), _ptr(expected), _ptr(sigma2), n_t,
+                n_k, n_bins, _ptr(out), _ptr(status), _stream()))
+
+    _with_status(status, dev, launch)
     return out
 
 
@@ -664,27 +691,50 @@ def metric_matrix_best(kind, data, expected, sigma2=None, offset=None, k0=0, for
     for bit the reduction of the full matrix"""
     data, expected, sigma2, n_t, n_k, n_bins = _ensemble_args(kind, data, expected, sigma2, form)
     dev = data.device
-    if offset is not None:
-        if offset.shape != (n_k,) or offset.dtype != F8:
-            raise ValueError("metric_matrix_best: offset is float64 [n_templates]")
-        offset = offset.contiguous()
+    offset = _offset_arg("metric_matrix_best", offset, n_k)
     best = torch.empty(n_t, dtype=F8, device=dev)
     arg = torch.empty(n_t, dtype=torch.int32, device=dev)
     at = torch.empty(n_t, dtype=F8, device=dev)
-    own_status = status is None
-    if own_status:
-        status = torch.zeros(1, dtype=torch.int32, device=dev)
-    if kind in ENSEMBLE_MC_KINDS:
-        _lib.check(_lib.lib().pisa_hip_metric_matrix_mc_best(
-            MAP_METRIC_KIND[kind], _ptr(data), _ptr(expected), _ptr(sigma2), _ptr(offset), int(k0), n_t, n_k, n_bins,
-            _ptr(best), _ptr(arg), _ptr(at), _ptr(status), _stream()))
-    else:
-        _lib.check(_lib.lib().pisa_hip_metric_matrix_best(
-            METRIC_KIND[kind], _lib.ENSEMBLE_FORMS.index(form), _ptr(data), _ptr(expected), _ptr(sigma2),
-            _ptr(offset), int(k0), n_t, n_k, n_bins, _ptr(best), _ptr(arg), _ptr(at), _ptr(status), _stream()))
-    if own_status:
-        _check_status(status)
+
+    def launch(status):
+        if kind in ENSEMBLE_MC_KINDS:
+            _lib.check(_lib.lib().pisa_hip_metric_matrix_mc_best(
+                MAP_METRIC_KIND[kind], _ptr(data), _ptr(expected), _ptr(sigma2), _ptr(offset), int(k0), n_t, n_k,
+                n_bins, _ptr(best), _ptr(arg), _ptr(at), _ptr(status), _stream()))
+        else:
+            _lib.check(_lib.lib().pisa_hip_metric_matrix_best(
+                METRIC_KIND[kind], _lib.ENSEMBLE_FORMS.index(form), _ptr(data), _ptr(expected), _ptr(sigma2),
+                _ptr(offset), int(k0), n_t, n_k, n_bins, _ptr(best), _ptr(arg), _ptr(at), _ptr(status), _stream()))
+
+    _with_status(status, dev, launch)
     return best, arg, at
+
+
+def _draw_args(what, mu, sigma, method, n_trials, seed, stream, first_trial, out):
+    """the arguments of a draw checked: mu [B], sigma (None where `method` is "poisson", else [B]), the ranges of seed,
+    stream and first_trial, and out [n_trials, B] (allocated when None)"""
+    if mu.dim() != 1 or mu.dtype != F8:
+        raise ValueError("%s: mu is a float64 vector [n_bins]" % what)
+    if sigma is None:
+        if method != "poisson":
+            raise ValueError("%s: method '%s' needs sigma" % (what, method))
+    elif sigma.dim() != 1 or sigma.dtype != F8 or sigma.shape != mu.shape or sigma.device != mu.device:
+        raise ValueError("%s: sigma is a float64 vector of mu's shape on mu's device" % what)
+    seed, stream, first_trial, n_trials = int(seed), int(stream), int(first_trial), int(n_trials)
+    if not 0 <= seed < 2 ** 64:
+        raise ValueError("%s: the seed %d is outside [0, 2^64)" % (what, seed))
+    if not (0 <= stream < 2 ** 32 and 0 <= first_trial < 2 ** 32):
+        raise ValueError("%s: stream and first_trial are in [0, 2^32)" % what)
+    mu = mu.contiguous()
+    sigma = None if sigma is None else sigma.contiguous()
+    n_bins = mu.shape[0]
+    # (a size outside [1, 2^31 - 1] or trial numbers beyond 2^32 reach the library: PISA_HIP_ERR_INVALID, nothing
+    # is launched)
+    if out is None:
+        out = torch.empty((max(n_trials, 0), n_bins), dtype=F8, device=mu.device)
+    elif tuple(out.shape) != (n_trials, n_bins) or out.dtype != F8 or not out.is_contiguous():
+        raise ValueError("%s: out is a contiguous float64 [n_trials, n_bins]" % what)
+    return mu, sigma, n_bins, n_trials, seed, stream, first_trial, out
 
 
 def poisson_fluctuate(mu, n_trials, seed, stream=0, first_trial=0, out=None, status=None):
@@ -694,29 +744,14 @@ def poisson_fluctuate(mu, n_trials, seed, stream=0, first_trial=0, out=None, sta
     that split the trials through `first_trial` give the rows of one call.  seed in [0, 2^64), stream and
     first_trial in [0, 2^32).  A NaN mean gives NaN, a zero mean 0; a negative, infinite or > 2^52 mean raises
     ValueError."""
-    if mu.dim() != 1 or mu.dtype != F8:
-        raise ValueError("poisson_fluctuate: mu is a float64 vector [n_bins]")
-    seed, stream, first_trial, n_trials = int(seed), int(stream), int(first_trial), int(n_trials)
-    if not 0 <= seed < 2 ** 64:
-        raise ValueError("poisson_fluctuate: the seed %d is outside [0, 2^64)" % seed)
-    if not (0 <= stream < 2 ** 32 and 0 <= first_trial < 2 ** 32):
-        raise ValueError("poisson_fluctuate: stream and first_trial are in [0, 2^32)")
-    mu = mu.contiguous()
-    n_bins = mu.shape[0]
-    dev = mu.device
-    if out is None:
-        out = torch.empty((max(n_trials, 0), n_bins), dtype=F8, device=dev)
-    elif tuple(out.shape) != (n_trials, n_bins) or out.dtype != F8 or not out.is_contiguous():
-        raise ValueError("poisson_fluctuate: out is a contiguous float64 [n_trials, n_bins]")
-    own_status = status is None
-    if own_status:
-        status = torch.zeros(1, dtype=torch.int32, device=dev)
-    # (a size outside [1, 2^31 - 1] or trial numbers beyond 2^32 reach the library: PISA_HIP_ERR_INVALID, nothing
-    # is launched)
-    _lib.check(_lib.lib().pisa_hip_poisson_fluctuate(_ptr(mu), n_bins, n_trials, seed, stream, first_trial, _ptr(out),
-                                                     _ptr(status), _stream()))
-    if own_status:
-        _check_status(status)
+    mu, _, n_bins, n_trials, seed, stream, first_trial, out = _draw_args(
+        "poisson_fluctuate", mu, None, "poisson", n_trials, seed, stream, first_trial, out)
+
+    def launch(status):
+        _lib.check(_lib.lib().pisa_hip_poisson_fluctuate(_ptr(mu), n_bins, n_trials, seed, stream, first_trial,
+                                                         _ptr(out), _ptr(status), _stream()))
+
+    _with_status(status, mu.device, launch)
     return out
 
 
@@ -741,33 +776,14 @@ def fluctuate(mu, n_trials, seed, method="poisson", sigma=None, stream=0, first_
     stream, first_trial + t, b, mu[b], sigma[b], method) alone.  A NaN mean gives NaN; a NaN, negative or infinite
     sigma, or a Poisson mean without a draw (negative, infinite, > 2^52), raises ValueError."""
     name = fluctuate_method(method)
-    if mu.dim() != 1 or mu.dtype != F8:
-        raise ValueError("fluctuate: mu is a float64 vector [n_bins]")
-    if sigma is None:
-        if name != "poisson":
-            raise ValueError("fluctuate: method '%s' needs sigma" % name)
-    elif sigma.dim() != 1 or sigma.dtype != F8 or sigma.shape != mu.shape or sigma.device != mu.device:
-        raise ValueError("fluctuate: sigma is a float64 vector of mu's shape on mu's device")
-    seed, stream, first_trial, n_trials = int(seed), int(stream), int(first_trial), int(n_trials)
-    if not 0 <= seed < 2 ** 64:
-        raise ValueError("fluctuate: the seed %d is outside [0, 2^64)" % seed)
-    if not (0 <= stream < 2 ** 32 and 0 <= first_trial < 2 ** 32):
-        raise ValueError("fluctuate: stream and first_trial are in [0, 2^32)")
-    mu = mu.contiguous()
-    sigma = None if sigma is None else sigma.contiguous()
-    n_bins = mu.shape[0]
-    dev = mu.device
-    if out is None:
-        out = torch.empty((max(n_trials, 0), n_bins), dtype=F8, device=dev)
-    elif tuple(out.shape) != (n_trials, n_bins) or out.dtype != F8 or not out.is_contiguous():
-        raise ValueError("fluctuate: out is a contiguous float64 [n_trials, n_bins]")
-    own_status = status is None
-    if own_status:
-        status = torch.zeros(1, dtype=torch.int32, device=dev)
-    _lib.check(_lib.lib().pisa_hip_fluctuate(_ptr(mu), _ptr(sigma), FLUCTUATE_METHOD[name], n_bins, n_trials, seed,
-                                             stream, first_trial, _ptr(out), _ptr(status), _stream()))
-    if own_status:
-        _check_status(status)
+    mu, sigma, n_bins, n_trials, seed, stream, first_trial, out = _draw_args(
+        "fluctuate", mu, sigma, name, n_trials, seed, stream, first_trial, out)
+
+    def launch(status):
+        _lib.check(_lib.lib().pisa_hip_fluctuate(_ptr(mu), _ptr(sigma), FLUCTUATE_METHOD[name], n_bins, n_trials,
+                                                 seed, stream, first_trial, _ptr(out), _ptr(status), _stream()))
+
+    _with_status(status, mu.device, launch)
     return out
 
 
@@ -777,10 +793,7 @@ def _profile_args(what, kind, data, expected, response, sigma2, inv_prior_sigma,
                          % (what, kind))
     if kind not in METRIC_KIND:
         raise ValueError("%s: metric '%s' not among %s" % (what, kind, sorted(METRIC_KIND)))
-    if data.dim() != 2 or expected.dim() != 2 or data.dtype != F8 or expected.dtype != F8:
-        raise ValueError("%s: data is [n_trials, n_bins] and expected [n_templates, n_bins], both float64" % what)
-    if sigma2 is not None and (sigma2.shape != expected.shape or sigma2.dtype != F8):
-        raise ValueError("%s: sigma2 has the shape and dtype of expected" % what)
+    data, expected, sigma2 = _maps_args(what, data, expected, sigma2)
     if kind == "mod_chi2" and sigma2 is None:
         raise ValueError("%s: mod_chi2 needs sigma2" % what)
     n_k, n_b = expected.shape
@@ -797,8 +810,7 @@ def _profile_args(what, kind, data, expected, response, sigma2, inv_prior_sigma,
         raise ValueError("%s: center is float64 [n_templates, n_params]" % what)
     if int(max_iter) < 0:
         raise ValueError("%s: max_iter >= 0" % what)
-    data, expected, response = data.contiguous(), expected.contiguous(), response.contiguous()
-    sigma2 = None if sigma2 is None else sigma2.contiguous()
+    response = response.contiguous()
     inv_prior_sigma = None if inv_prior_sigma is None else inv_prior_sigma.contiguous()
     center = None if center is None else center.contiguous()
     stride = n_j * n_b if response.dim() == 3 else 0
@@ -823,15 +835,14 @@ def profiled_metric_matrix(kind, data, expected, response, sigma2=None, inv_prio
     eta = torch.empty((n_t, n_k, n_j), dtype=F8, device=dev) if want_eta else None
     n_iter = torch.empty((n_t, n_k), dtype=torch.int32, device=dev)
     pair_status = torch.empty((n_t, n_k), dtype=torch.int32, device=dev)
-    own_status = status is None
-    if own_status:
-        status = torch.zeros(1, dtype=torch.int32, device=dev)
-    _lib.check(_lib.lib().pisa_hip_profiled_metric_matrix(
-        METRIC_KIND[kind], _ptr(data), _ptr(expected), _ptr(sigma2), _ptr(response), stride, _ptr(ips), _ptr(center),
-        n_j, int(max_iter), n_t, n_k, n_bins, _ptr(value), _ptr(eta), _ptr(n_iter), _ptr(pair_status), _ptr(status),
-        _stream()))
-    if own_status:
-        _check_status(status)
+
+    def launch(status):
+        _lib.check(_lib.lib().pisa_hip_profiled_metric_matrix(
+            METRIC_KIND[kind], _ptr(data), _ptr(expected), _ptr(sigma2), _ptr(response), stride, _ptr(ips),
+            _ptr(center), n_j, int(max_iter), n_t, n_k, n_bins, _ptr(value), _ptr(eta), _ptr(n_iter),
+            _ptr(pair_status), _ptr(status), _stream()))
+
+    _with_status(status, dev, launch)
     return dict(value=value, eta=eta, n_iter=n_iter, status=pair_status)
 
 
@@ -844,35 +855,25 @@ def profiled_metric_matrix_best(kind, data, expected, response, sigma2=None, inv
     (data, expected, response, sigma2, ips, center, stride, n_t, n_k, n_bins, n_j) = _profile_args(
         "profiled_metric_matrix_best", kind, data, expected, response, sigma2, inv_prior_sigma, center, max_iter)
     dev = data.device
-    if offset is not None:
-        if offset.shape != (n_k,) or offset.dtype != F8:
-            raise ValueError("profiled_metric_matrix_best: offset is float64 [n_templates]")
-        offset = offset.contiguous()
+    offset = _offset_arg("profiled_metric_matrix_best", offset, n_k)
     best = torch.empty(n_t, dtype=F8, device=dev)
     arg = torch.empty(n_t, dtype=torch.int32, device=dev)
     at = torch.empty(n_t, dtype=F8, device=dev)
     eta_best = torch.empty((n_t, n_j), dtype=F8, device=dev)
     eta_at = torch.empty((n_t, n_j), dtype=F8, device=dev)
     trial_status = torch.empty(n_t, dtype=torch.int32, device=dev)
-    own_status = status is None
-    if own_status:
-        status = torch.zeros(1, dtype=torch.int32, device=dev)
-    _lib.check(_lib.lib().pisa_hip_profiled_metric_matrix_best(
-        METRIC_KIND[kind], _ptr(data), _ptr(expected), _ptr(sigma2), _ptr(response), stride, _ptr(ips), _ptr(center),
-        _ptr(offset), int(k0), n_j, int(max_iter), n_t, n_k, n_bins, _ptr(best), _ptr(arg), _ptr(at), _ptr(eta_best),
-        _ptr(eta_at), _ptr(trial_status), _ptr(status), _stream()))
-    if own_status:
-        _check_status(status)
+
+    def launch(status):
+        _lib.check(_lib.lib().pisa_hip_profiled_metric_matrix_best(
+            METRIC_KIND[kind], _ptr(data), _ptr(expected), _ptr(sigma2), _ptr(response), stride, _ptr(ips),
+            _ptr(center), _ptr(offset), int(k0), n_j, int(max_iter), n_t, n_k, n_bins, _ptr(best), _ptr(arg),
+            _ptr(at), _ptr(eta_best), _ptr(eta_at), _ptr(trial_status), _ptr(status), _stream()))
+
+    _with_status(status, dev, launch)
     return dict(best=best, arg=arg, at=at, eta_best=eta_best, eta_at=eta_at, status=trial_status)
 
 
 # --------------------------------------------------- generalized Poisson-gamma likelihood
-def _check_status(status):
-    st = int(status.item())
-    if st != 0:
-        _lib.check(st)
-
-
 def gpllh_bin_sums(weights, index, offsets):
     """(Sigma w, Sigma w^2) per bin, bin b's events being weights[index[offsets[b]:offsets[b + 1]]]
     (`pisa_hip_gpllh_bin_sums`); a negative weight among them raises"""
