@@ -30,6 +30,7 @@
 #include <algorithm>
 #include <atomic>
 #include <string.h>
+#include <type_traits>
 #include <vector>
 
 #include "common.hpp"
@@ -43,7 +44,7 @@ struct pisa_hip_hist_plan {
     int64_t n_nodes = 0, n_bins = 0;
     std::vector<int64_t> n_events;           // per container: the snapshot a planned call is checked against
     std::vector<int32_t> n_blocks, n_dep;    // per container: blocks of 256 events / those that deposit
-    std::vector<const int32_t *> list;       // per container: DEVICE block numbers, ascending; nullptr = every block
+    std::vector<const int32_t *> list;       // per container: DEVICE block numbers, ascending, bit 31 = needs guards
     std::vector<int64_t> offset;             // per container: its list starts at d_lists + offset
     std::vector<int32_t> blk_start;          // per launch (MAX_CONT containers): MAX_CONT + 1 entries
     std::vector<int64_t> chunk;              // per launch
@@ -78,6 +79,11 @@ constexpr int64_t LDS_ACC_BYTES_MAX = 64 * 1024;
 // atomic on a generic pointer (which this compiler then fails to select).
 __device__ __forceinline__ void lds_add(unsigned long long *p, unsigned long long v) {
     (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+// (the LDS accumulator at a 32-bit LDS byte address: the planned sweep forms its addresses as integers)
+typedef __attribute__((address_space(3))) unsigned long long *lds_u64;
+__device__ __forceinline__ void lds_add_at(unsigned at, unsigned long long v) {
+    (void)__hip_atomic_fetch_add((lds_u64)(uintptr_t)at, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 __device__ __forceinline__ void glb_add(unsigned long long *p, unsigned long long v) {
     (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -208,8 +214,8 @@ struct ContDev {
     // bins [p W, (p+1) W), W = the LDS window (HistArgs::window)
     const int32_t *part_start;
     int32_t n_part, part_width;
-    // optional (pisa_hip_hist_plan; MODE 7 sweeping together): the n_dep blocks of 256 events that hold an event which
-    // can deposit, ascending -- the sweep visits these and no other block
+    // pisa_hip_hist_plan (the LEAN sweep): the n_dep blocks of 256 events that hold an event which can deposit, ascending
+    // -- the sweep visits these and no other block; bit 31 of an entry: the block also holds an event that deposits nothing
     const int32_t *dep_blocks;
     int32_t n_dep, reserved;
 };
@@ -321,7 +327,7 @@ __device__ unsigned long long g_hist_stamps[8 * 1024];
 #else
 #define STAMP(k) do {} while (0)
 #endif
-template <int MODE, bool LDS_ACC, int DIMS = 0>
+template <int MODE, bool LDS_ACC, int DIMS = 0, bool LEAN = false>
 __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8)))
 hist_accumulate_kernel(const HistArgs a, unsigned long long *__restrict__ g_limbs,
                        int32_t *__restrict__ status) {
@@ -344,7 +350,7 @@ hist_accumulate_kernel(const HistArgs a, unsigned long long *__restrict__ g_limb
     // chunk -- a binning too large for LDS still gets LDS accumulation when the
     // events are stored in an order that keeps a chunk inside a few hundred
     // neighbouring bins; deposits outside the window go to the global limbs directly
-    const int n_bins = a.window > 0 ? a.window : (int)a.n_bins;
+    const int n_bins = !LEAN && a.window > 0 ? a.window : (int)a.n_bins;
     const int n_acc = NL * 2 * n_bins;
     // replica used by this lane: neighbouring lanes (neighbouring, i.e. correlated,
     // events) add into different copies, which cuts same-address serialisation
@@ -359,7 +365,7 @@ hist_accumulate_kernel(const HistArgs a, unsigned long long *__restrict__ g_limb
     // binning needs bin-contiguous chunks and keeps them.  The loads of the first sweep
     // are issued here, before the LDS accumulators are cleared, so that the clearing
     // overlaps the first HBM round trip.
-    const bool together = a.window == 0;
+    const bool together = LEAN || a.window == 0;
     const int64_t n_wg = a.blk_start[c + 1] - a.blk_start[c];
     const int64_t step = together ? n_wg * nthreads : nthreads;
     const int64_t p_end = together ? (C.n >> 1) : (end >> 1);
@@ -374,27 +380,39 @@ hist_accumulate_kernel(const HistArgs a, unsigned long long *__restrict__ g_limb
     const int64_t q_end = ((together ? C.n : end) + 3) >> 2;
     int64_t q = (together ? lb * nthreads : (start >> 2)) + threadIdx.x;
     bool qhave = QUAD && q < q_end;
-    // Planned sweep (ContDev::dep_blocks): the wavefronts of the container's workgroups take the listed blocks round
-    // robin -- wavefront wv of workgroup lb the ordinals lb W + wv + i W n_wg (W wavefronts per workgroup), ordinal o
-    // standing for block dep[o] -- so every workgroup's share is equal to within one block.  The block number is one
-    // scalar load per sweep (the list is written once, by the plan: constant address space), fetched a sweep ahead of
-    // the column loads that need it.  No list: the direct index above, a wave-uniform choice.
-    typedef const int32_t __attribute__((address_space(4))) *dep_list;
-    const dep_list dep = QUAD && together ? (dep_list)C.dep_blocks : nullptr;
+    // Planned sweep (LEAN; ContDev::dep_blocks): the wavefronts of the container's workgroups take the listed blocks
+    // round robin -- wavefront wv of workgroup lb the ordinals wv n_wg + lb + i W n_wg (W wavefronts per workgroup),
+    // ordinal o standing for block dep[o] & 0x7fffffff.  The list's last, partial round (n_dep mod W n_wg blocks) is
+    // thereby dealt ACROSS the workgroups, wavefront 0 of every workgroup first: a workgroup has one or two wavefronts
+    // with a sweep more than the others, which they run on an otherwise idle CU.  (Dealt lb W + wv, the first few
+    // workgroups of a container took that round with all sixteen wavefronts and finished 3-6 us after every other
+    // workgroup of the launch: in-kernel stamps, EXPERIMENTS R14-1.)  The
+    // list entry (block number, and in bit 31 the plan's mark "holds an event that deposits nothing") is one scalar
+    // load per sweep (the list is written once, by the plan: constant address space), fetched a sweep ahead of the
+    // column loads that need it.  Ordinal and entries are wave-uniform values in scalar registers: a wavefront sweeps
+    // whole blocks (both columns are padded to whole blocks), so the sweep loop has no per-lane exit.
+    typedef const uint32_t __attribute__((address_space(4))) *dep_list;
+    const dep_list dep = LEAN ? (dep_list)C.dep_blocks : nullptr;
     const int o_step = (int)n_wg * (nthreads >> 6);
     const int n_dep = C.n_dep;
-    int o = 0, blk_next = 0;
-    if (QUAD && dep) {
-        o = __builtin_amdgcn_readfirstlane((int)lb * (nthreads >> 6) + (int)(threadIdx.x >> 6));
-        const int last = n_dep - 1;
-        const int blk = dep[o < last ? o : last];
-        blk_next = dep[o + o_step < last ? o + o_step : last];
-        q = (int64_t)blk * 64 + (threadIdx.x & 63);
-        qhave = o < n_dep && q < q_end;
-    }
+    int o = 0;
+    uint32_t ent = 0, ent_next = 0;
     uint4 qx = make_uint4(~0u, ~0u, ~0u, ~0u);
     double2 g0 = awa, g1 = awa;
-    if (QUAD && qhave) {
+    if (LEAN) {
+        o = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6) * (int)n_wg + (int)lb);
+        qhave = o < n_dep;
+        if (qhave) {
+            const int last = n_dep - 1;
+            ent = dep[o];
+            ent_next = dep[o + o_step < last ? o + o_step : last];
+            const int64_t blk = ent & 0x7fffffffu;
+            qx = reinterpret_cast<const uint4 *>(C.idx16)[blk * 64 + (threadIdx.x & 63)];
+            const double2 *gq = C.wflux_q + (blk * 256 + (threadIdx.x & 63));
+            g0 = gq[0]; g1 = gq[64];
+        }
+    }
+    if (QUAD && !LEAN && qhave) {
         qx = reinterpret_cast<const uint4 *>(C.idx16)[q];
         const double2 *gq = C.wflux_q + ((q >> 6) * 256 + (q & 63));
         g0 = gq[0]; g1 = gq[64];
@@ -413,11 +431,11 @@ hist_accumulate_kernel(const HistArgs a, unsigned long long *__restrict__ g_limb
     if (LDS_ACC) {
         // (partitioned order: two windows -- a chunk may reach into a second partition -- and the partition
         // table in LDS: looking a partition up in global memory is a chain of dependent scalar loads, ~1 us each)
-        const bool parts = QUAD && a.window > 0 && C.part_start;
+        const bool parts = QUAD && !LEAN && a.window > 0 && C.part_start;
         if (parts)   // behind the two windows (a strided fill: the table has up to PART_MAX + 1 entries whatever the block size)
             for (int k = threadIdx.x; k <= C.n_part; k += nthreads) s_part[k] = C.part_start[k];
         for (int k = threadIdx.x; k < n_acc * (parts ? 2 : a.copies); k += nthreads) s_acc[k] = 0ull;
-        if ((PACKED || QUAD) && a.window > 0 && !(QUAD && C.part_start)) {
+        if ((PACKED || QUAD) && !LEAN && a.window > 0 && !(QUAD && C.part_start)) {
             bin_lo = window_lowest_bin<QUAD>(C, start, end, q_end, nthreads);
         }
         __syncthreads();
@@ -427,7 +445,7 @@ hist_accumulate_kernel(const HistArgs a, unsigned long long *__restrict__ g_limb
 
     auto accumulate = [&](int bin, double w, double w2) {
         const int rel = bin - bin_lo;
-        const bool in_lds = LDS_ACC && (unsigned)rel < (unsigned)n_bins;
+        const bool in_lds = LEAN || (LDS_ACC && (unsigned)rel < (unsigned)n_bins);   // (LEAN: every bin, no window)
         // digits of slabs j, j-1, j-2 of one weight (deposit_units): LDS accumulators of this workgroup,
         // or -- bins outside the LDS window, binnings without LDS accumulators -- the global limbs
         auto put = [&](int qn, int j, unsigned long long d) {
@@ -465,7 +483,103 @@ hist_accumulate_kernel(const HistArgs a, unsigned long long *__restrict__ g_limb
     // partitioned order: the other LDS window (see the QUAD sweep) and the first bin of what it holds
     int other_lo = -1;
 
-    if (QUAD) {
+    if constexpr (LEAN) {
+        // THE PLANNED SWEEP (MODE 7, every bin in LDS, the blocks of the plan's list): the QUAD sweep below with what a
+        // planned launch knows taken out of the instruction stream.
+        //  * A block the plan did not mark holds 256 events that all deposit (node and bin valid, none beyond the
+        //    container's end): no 0xffff selects.  A marked block (the topped-up last one, a block with an event outside
+        //    the calc grid or the binning) runs the guarded body with the shared `accumulate`.  The mark is bit 31 of the
+        //    list entry: a scalar, wave-uniform choice.
+        //  * The wavefront classifies the two weights of a half-sweep ONCE: 2^-26 <= w < 2^38 makes w and w*w both `fast`
+        //    in the sense of deposit_units (w*w is then in [2^-52, 2^76): its rounding cannot reach 2^76), and if that
+        //    holds in every lane the four deposits run without a branch.  Otherwise this half-sweep takes `accumulate`,
+        //    which deposits the same digits.  (Per half-sweep, not per quad: the flux pairs of events 2, 3 are still in
+        //    flight while events 0, 1 deposit -- the load pipeline of the QUAD sweep is kept.)
+        //  * One LDS byte address per deposit, slab j: slabs j-1, j-2 lie one and two scalar strides below it.
+        const double2 *tab = C.pepmu_own ? C.pepmu_own
+                                         : a.pepmu + ((int64_t)C.side * 3 + C.flav) * a.n_nodes;
+        const double scale = C.scale;
+        const uint4 *idxq = reinterpret_cast<const uint4 *>(C.idx16);
+        const double2 *aw = C.wflux_q;
+        const double2 zero2 = make_double2(0.0, 0.0);
+        const unsigned lane = threadIdx.x & 63;
+        const unsigned q_bytes = 8u * (unsigned)n_bins, slab_bytes = 2u * q_bytes;   // [slab][quantity][bin] of 8-byte words
+        // byte address of (slab -29, quantity 0, bin 0) of this lane's replica: put_fast counts slabs from there
+        const unsigned acc0 = (unsigned)(uintptr_t)(lds_u64)my_acc - 29u * slab_bytes;
+        auto both_fast = [](double w) { return ((unsigned)__double2hiint(w) >> 20) - (1023u - 26u) < 64u; };
+        // deposit_units' fast case at byte address `at` = (slab -29, quantity, bin): biased exponent + 21 = 32 (j + 29) + sh
+        auto put_fast = [&](unsigned at, double x) {
+            const unsigned hi = (unsigned)__double2hiint(x) + (21u << 20);
+            const unsigned sh = (hi >> 20) & 31u;
+            const unsigned long long m =
+                ((unsigned long long)((hi & 0xfffffu) | 0x100000u) << 32) | (unsigned)__double2loint(x);
+            const unsigned long long low = m << (sh + 12u);
+            const unsigned at0 = __umul24(hi >> 25, slab_bytes) + at;
+            lds_add_at(at0, m >> (52u - sh));
+            lds_add_at(at0 - slab_bytes, low >> 32);
+            lds_add_at(at0 - 2u * slab_bytes, low & 0xffffffffull);
+        };
+        int64_t blk = ent & 0x7fffffffu;
+        // one block of 256 events: blk_n = the block whose first loads are issued half-way (the last sweep re-reads its own)
+        auto sweep = [&](auto guard, int64_t blk_n) {
+            constexpr bool GUARD = decltype(guard)::value;
+            uint4 x = qx;
+            if (GUARD && blk * 64 + lane >= q_end) x = make_uint4(~0u, ~0u, ~0u, ~0u);   // (beyond the container's last quad)
+            auto half = [&](unsigned xa, unsigned xb, double2 ga, double2 gb, double2 pa, double2 pb) {
+                unsigned ba = xa >> 16, bb = xb >> 16;
+                if (GUARD) {
+                    if ((xa & 0xffffu) == 0xffffu) pa = zero2;
+                    if ((xb & 0xffffu) == 0xffffu) pb = zero2;
+                }
+                double wa = weight_compact(ga.x, ga.y, pa.x, pa.y, scale);
+                double wb = weight_compact(gb.x, gb.y, pb.x, pb.y, scale);
+                if (GUARD) {
+                    if (ba == 0xffffu) { wa = 0.0; ba = 0; }
+                    if (bb == 0xffffu) { wb = 0.0; bb = 0; }
+                    accumulate((int)ba, wa, wa * wa);
+                    accumulate((int)bb, wb, wb * wb);
+                    return;
+                }
+                bool fast = both_fast(wa) && both_fast(wb);
+#ifdef PISA_DEV_PROBES
+                fast = fast && !(a.opts & 2);
+#endif
+                if (__all(fast)) {
+                    const unsigned ata = acc0 + 8u * ba, atb = acc0 + 8u * bb;
+                    put_fast(ata, wa); put_fast(ata + q_bytes, wa * wa);
+                    put_fast(atb, wb); put_fast(atb + q_bytes, wb * wb);
+                } else {
+                    accumulate((int)ba, wa, wa * wa);
+                    accumulate((int)bb, wb, wb * wb);
+                }
+            };
+            auto gather = [&](unsigned w) {
+                const unsigned n = w & 0xffffu;
+                return tab[GUARD && n == 0xffffu ? 0u : n];
+            };
+            const double2 *gq = aw + (blk * 256 + lane);   // lane-contiguous 16-B loads
+            const double2 p0 = gather(x.x), p1 = gather(x.y);
+            const double2 g2 = gq[128], g3 = gq[192];
+            half(x.x, x.y, g0, g1, p0, p1);
+            const double2 p2 = gather(x.z), p3 = gather(x.w);
+            const uint4 qxn = idxq[blk_n * 64 + lane];
+            const double2 *gn = aw + (blk_n * 256 + lane);
+            const double2 g0n = gn[0], g1n = gn[64];
+            half(x.z, x.w, g2, g3, p2, p3);
+            qx = qxn; g0 = g0n; g1 = g1n;
+        };
+        while (qhave) {   // (wave-uniform)
+            const int o_next = o + o_step, last = n_dep - 1;
+            const bool have_n = o_next < n_dep;
+            const int64_t blk_n = have_n ? (int64_t)(ent_next & 0x7fffffffu) : blk;
+            const uint32_t ent_nn = dep[o_next + o_step < last ? o_next + o_step : last];
+            if (ent >> 31) sweep(std::true_type{}, blk_n);
+            else sweep(std::false_type{}, blk_n);
+            blk = blk_n; ent = ent_next; ent_next = ent_nn;
+            o = o_next;
+            qhave = have_n;
+        }
+    } else if (QUAD) {
         const double2 *tab = C.pepmu_own ? C.pepmu_own
                                          : a.pepmu + ((int64_t)C.side * 3 + C.flav) * a.n_nodes;
         const double scale = C.scale;
@@ -551,17 +665,8 @@ hist_accumulate_kernel(const HistArgs a, unsigned long long *__restrict__ g_limb
             const unsigned b2 = qx.z >> 16, b3 = qx.w >> 16;
             double2 p2 = tab[n2 == 0xffffu ? 0 : n2];
             double2 p3 = tab[n3 == 0xffffu ? 0 : n3];
-            int64_t qn = q + qstep;
-            bool have_n = qn < q_lim;
-            if (dep) {   // (wave-uniform) the next listed block, and the number of the one after it
-                // (the lanes of a wavefront leave the sweep one by one in its last block only: `o` is the same in
-                // all that are here, which the compiler cannot see across the loops)
-                const int o_next = __builtin_amdgcn_readfirstlane(o + o_step), last = n_dep - 1;
-                qn = (int64_t)blk_next * 64 + (threadIdx.x & 63);
-                have_n = o_next < n_dep && qn < q_lim;
-                blk_next = dep[o_next + o_step < last ? o_next + o_step : last];
-                o = o_next;
-            }
+            const int64_t qn = q + qstep;
+            const bool have_n = qn < q_lim;
             const int64_t ql = have_n ? qn : q;  // unconditional loads (the last sweep re-reads its own quad)
             const uint4 qxn = idxq[ql];
             const double2 *gn = aw + ((ql >> 6) * 256 + (ql & 63));
@@ -578,9 +683,6 @@ hist_accumulate_kernel(const HistArgs a, unsigned long long *__restrict__ g_limb
             q = qn;
             qhave = have_n;
         }
-        // (nothing after the sweep reads the ordinal: said here, it and the block number stay wave-uniform values in
-        // scalar registers inside the sweep although the lanes leave it one by one)
-        o = 0; blk_next = 0;
         if (part < 0) break;
         // next partition of this chunk, if any
         const int64_t pe = (int64_t)s_part[part + 1] * 256;
@@ -1376,6 +1478,8 @@ static const struct HistForm { int mode, gd, od; hist_kernel_t lds, no_lds; } hi
     {0, 0, 2, hist_accumulate_kernel<0, true, 2>, hist_accumulate_kernel<0, false, 2>},
     {0, 0, 3, hist_accumulate_kernel<0, true, 3>, hist_accumulate_kernel<0, false, 3>},
 };
+// the form a planned launch takes (pisa_hip_hist_plan: MODE 7, no window, the plan's lists): the LEAN sweep
+static const hist_kernel_t hist_planned_form = hist_accumulate_kernel<7, true, 0, true>;
 
 static int run_hist(const ContDev *conts, int n_cont, int mode, const DevBinning *grid,
                     int64_t n_nodes, const double *prob_nu, const double *prob_nubar,
@@ -1482,9 +1586,14 @@ static int run_hist(const ContDev *conts, int n_cont, int mode, const DevBinning
         const int gd = form == 1 ? a.grid.ndim : 0, od = form <= 1 ? a.outb.ndim : 0;
         if (form == 1 && (gd < 1 || gd > 2 || od < 1 || od > 3 || n_nodes >= (1LL << 31) / 9)) return PISA_HIP_ERR_INVALID;
         if (form == 0 && (od < 1 || od > 3)) return PISA_HIP_ERR_INVALID;
-        for (const HistForm &f : hist_forms)
-            if (f.mode == form && f.gd == gd && f.od == od)
-                hipLaunchKernelGGL(lds || !f.no_lds ? f.lds : f.no_lds, grid_dim, block, shmem, s, a, out, d_status);
+        if (plan) {   // the planned sweep: MODE 7, every bin in LDS, both quantities (what a plan is made for)
+            if (!(form == 7 && lds && window == 0 && second_quantity)) return PISA_HIP_ERR_INVALID;
+            hipLaunchKernelGGL(hist_planned_form, grid_dim, block, shmem, s, a, out, d_status);
+        } else {
+            for (const HistForm &f : hist_forms)
+                if (f.mode == form && f.gd == gd && f.od == od)
+                    hipLaunchKernelGGL(lds || !f.no_lds ? f.lds : f.no_lds, grid_dim, block, shmem, s, a, out, d_status);
+        }
         PISA_CHECK_LAUNCH("hist_accumulate_kernel");
         if (g_prof_stop) PISA_TRY_HIP(hipEventRecord(g_prof_stop, s));
     }
@@ -1634,19 +1743,24 @@ PISA_API int pisa_hip_reweight_hist_acc(const pisa_hip_container *h_containers,
 // ---------------------------------------------------------------------------
 // THE ACCUMULATE PLAN (pisa_hip_hist_plan_*): which events lie outside the output binning is fixed by the binning and
 // the events' static coordinates; the resident order (order.hip, `deposit_block_order`) gathers the others into whole
-// blocks of 256.  The plan lists those blocks once, and hist_accumulate_kernel<7, true> then streams them alone.
+// blocks of 256.  The plan lists those blocks once -- and marks the listed blocks that also hold an event which deposits
+// nothing --, and hist_accumulate_kernel<7, true, 0, true> (the LEAN sweep) then streams them alone.
 namespace pisa {
 
-// marks[b] = block b of 256 events holds an event whose bin half is not 0xffff (the multi-point kernel's `any_in`:
-// the bin alone -- an event inside the binning but outside the calc grid still forms its product)
+// marks[b] bit 0 = block b of 256 events holds an event whose bin half is not 0xffff (the multi-point kernel's `any_in`:
+// the bin alone -- an event inside the binning but outside the calc grid still forms its product); bit 1 = it holds an
+// event that needs a guard in the sweep: a half that is 0xffff, or a position beyond the container's n events
 __global__ void __launch_bounds__(256)
-hist_plan_mark_kernel(const uint32_t *__restrict__ idx16, uint8_t *__restrict__ marks) {
-    const uint32_t v = idx16[(int64_t)blockIdx.x * 256 + threadIdx.x];   // (the column is padded to whole blocks)
+hist_plan_mark_kernel(const uint32_t *__restrict__ idx16, int64_t n, uint8_t *__restrict__ marks) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const uint32_t v = idx16[e];   // (the column is padded to whole blocks)
     const int any = __syncthreads_or((v >> 16) != 0xffffu);
-    if (threadIdx.x == 0) marks[blockIdx.x] = (uint8_t)(any != 0);
+    const int idle = __syncthreads_or((v >> 16) == 0xffffu || (v & 0xffffu) == 0xffffu || e >= n);
+    if (threadIdx.x == 0) marks[blockIdx.x] = (uint8_t)((any != 0) | ((idle != 0) << 1));
 }
 
-// the marked block numbers, ascending, and their count: one workgroup, every thread a contiguous run of blocks
+// the numbers of the blocks with bit 0 set, ascending (bit 1 of the mark in bit 31 of the entry), and their count: one
+// workgroup, every thread a contiguous run of blocks
 __global__ void __launch_bounds__(1024)
 hist_plan_compact_kernel(const uint8_t *__restrict__ marks, int32_t n_blocks, int32_t *__restrict__ list,
                          int32_t *__restrict__ count) {
@@ -1656,7 +1770,7 @@ hist_plan_compact_kernel(const uint8_t *__restrict__ marks, int32_t n_blocks, in
     const int lo = t * per < n_blocks ? t * per : n_blocks;
     const int hi = lo + per < n_blocks ? lo + per : n_blocks;
     int cnt = 0;
-    for (int b = lo; b < hi; b++) cnt += marks[b];
+    for (int b = lo; b < hi; b++) cnt += marks[b] & 1;
     s_cnt[t] = cnt;
     __syncthreads();
     for (int d = 1; d < 1024; d <<= 1) {   // inclusive scan
@@ -1667,7 +1781,7 @@ hist_plan_compact_kernel(const uint8_t *__restrict__ marks, int32_t n_blocks, in
     }
     int pos = s_cnt[t] - cnt;
     for (int b = lo; b < hi; b++)
-        if (marks[b]) list[pos++] = b;
+        if (marks[b] & 1) list[pos++] = (int32_t)((uint32_t)b | ((uint32_t)(marks[b] & 2) << 30));
     if (t == 1023) *count = s_cnt[1023];
 }
 
@@ -1729,7 +1843,7 @@ PISA_API int pisa_hip_hist_plan_create(const pisa_hip_container *h_containers, i
         p->n_blocks[c] = nb;
         p->offset[c] = at;
         if (nb > 0) {
-            hipLaunchKernelGGL(hist_plan_mark_kernel, dim3((unsigned)nb), dim3(256), 0, s, h.d_node_bin16, d_marks + at);
+            hipLaunchKernelGGL(hist_plan_mark_kernel, dim3((unsigned)nb), dim3(256), 0, s, h.d_node_bin16, h.n_events, d_marks + at);
             hipLaunchKernelGGL(hist_plan_compact_kernel, dim3(1), dim3(1024), 0, s, d_marks + at, nb, p->d_lists + at,
                                d_counts + c);
         }
@@ -1748,8 +1862,7 @@ PISA_API int pisa_hip_hist_plan_create(const pisa_hip_container *h_containers, i
         for (int c = 0; c < nc; c++) {
             if (p->n_dep[base + c] < 0 || p->n_dep[base + c] > p->n_blocks[base + c]) return fail(PISA_HIP_ERR_HIP);
             nev[c] = 256 * (int64_t)p->n_dep[base + c];
-            // every block deposits: no list, the direct index
-            p->list[base + c] = p->n_dep[base + c] < p->n_blocks[base + c] ? p->d_lists + p->offset[base + c] : nullptr;
+            p->list[base + c] = p->n_dep[base + c] > 0 ? p->d_lists + p->offset[base + c] : nullptr;   // (none: no workgroup)
         }
         plan_blocks(nev, nc, p->threads, chunk, blk_start);
         for (int c = nc; c < MAX_CONT; c++) blk_start[c + 1] = blk_start[nc];
@@ -1768,10 +1881,8 @@ PISA_API int pisa_hip_hist_plan_info(const pisa_hip_hist_plan *plan, int32_t con
     if (n_dep_blocks) *n_dep_blocks = plan->n_dep[container];
     if (workgroups) *workgroups = bs[1] - bs[0];
     if (h_dep_blocks && plan->n_dep[container] > 0) {
-        if (plan->list[container])
-            PISA_TRY_HIP(hipMemcpy(h_dep_blocks, plan->list[container], (size_t)plan->n_dep[container] * 4, hipMemcpyDeviceToHost));
-        else
-            for (int32_t b = 0; b < plan->n_dep[container]; b++) h_dep_blocks[b] = b;
+        PISA_TRY_HIP(hipMemcpy(h_dep_blocks, plan->list[container], (size_t)plan->n_dep[container] * 4, hipMemcpyDeviceToHost));
+        for (int32_t b = 0; b < plan->n_dep[container]; b++) h_dep_blocks[b] &= 0x7fffffff;   // (bit 31: the sweep's mark)
     }
     return PISA_HIP_OK;
 }
