@@ -1258,6 +1258,42 @@ int pisa_hip_profiled_metric_matrix_best(int32_t kind, const double *d_data, con
                                          int32_t *d_arg, double *d_at, double *d_eta_best, double *d_eta_at,
                                          int32_t *d_trial_status, int32_t *d_status, void *stream);
 
+/* The two entry points above with every displacement fitted inside its range (csrc/profile_bounded.hip; DESIGN.md
+ * section 4, "Profiled trial ensembles: bounds"):
+ *     eta_hat = argmin Phi(eta)  over  d_lower[k][j] <= eta_j <= d_upper[k][j]  on the same domain.
+ * Bounds are displacements in the parameter's units; -inf / +inf: no bound on that side; lower == upper pins the
+ * parameter.  The iteration is the same damped Newton iteration with a projected step: it starts at 0 held inside the
+ * box (_START_OUTSIDE is judged there), every trial point is held inside the box by comparisons, and after each
+ * accepted step the coordinates that sit on a bound with the gradient pointing out of the box leave the Newton system;
+ * _NOT_POSDEF and the decrement are those of the remaining block.  A fitted coordinate on a bound holds the bound's
+ * own double (eta == bound); no flag marks it, status 0 keeps meaning a clean fit.
+ *   d_lower, d_upper [n_templates][J] with bound_stride_k >= J doubles between templates, or ONE [J] block shared by
+ *       all templates with bound_stride_k = 0; either may be NULL: no bound on that side.
+ *   _BAD_BOUNDS: some j of template k does not satisfy lower <= upper (a NaN bound included).  The pair takes no
+ *       step: eta = 0, n_iter = 0, and the entry is the metric at eta = 0.
+ * With every bound infinite the outputs are bit for bit those of the entry points above.  Everything said there
+ * about placement, d_status, the join buffer (these two entry points have one of their own) and PISA_HIP_ERR_INVALID
+ * holds; in addition PISA_HIP_ERR_INVALID for a bound stride that is neither 0 nor >= J. */
+#define PISA_HIP_PROFILE_BAD_BOUNDS 16
+int pisa_hip_profiled_metric_matrix_bounded(int32_t kind, const double *d_data, const double *d_expected,
+                                            const double *d_sigma2, const double *d_response,
+                                            int64_t response_stride_k, const double *d_inv_prior_sigma,
+                                            const double *d_center, const double *d_lower, const double *d_upper,
+                                            int64_t bound_stride_k, int32_t n_params, int32_t max_iter,
+                                            int64_t n_trials, int64_t n_templates, int64_t n_bins, double *d_value,
+                                            double *d_eta, int32_t *d_n_iter, int32_t *d_pair_status,
+                                            int32_t *d_status, void *stream);
+int pisa_hip_profiled_metric_matrix_best_bounded(int32_t kind, const double *d_data, const double *d_expected,
+                                                 const double *d_sigma2, const double *d_response,
+                                                 int64_t response_stride_k, const double *d_inv_prior_sigma,
+                                                 const double *d_center, const double *d_lower,
+                                                 const double *d_upper, int64_t bound_stride_k,
+                                                 const double *d_offset, int32_t k0, int32_t n_params,
+                                                 int32_t max_iter, int64_t n_trials, int64_t n_templates,
+                                                 int64_t n_bins, double *d_best, int32_t *d_arg, double *d_at,
+                                                 double *d_eta_best, double *d_eta_at, int32_t *d_trial_status,
+                                                 int32_t *d_status, void *stream);
+
 /* ------------------------------------------------------- raw device memory */
 /* Thin wrappers so hosts without torch (a cgo/ctypes binding of the
  * reference) can own device buffers. */

@@ -35,10 +35,13 @@ the point, mu = hist[k] + sum_j response[k, j] eta_j with the binwise gradients 
 (`NuisanceResponse.from_maker`), and the displacements eta are fitted by the damped Newton iteration of
 csrc/profile.hip (`kernels.profiled_metric_matrix`, at most 8 parameters, Gaussian priors included; DESIGN.md §4,
 "Profiled trial ensembles") -- T x K small convex fits in one launch, no minimiser on the host.  The fit is exact for
-a parameter the template is linear in (aeff_scale) and a first-order profile otherwise; the fitted eta come back so
-that a caller can hold them against the parameters' ranges (no bounds are applied).  Without `response` a parameter
-that is not a dimension of the grid stays at the value it had when the grid was made, and every call gives what it
-gave before the argument existed.
+a parameter the template is linear in (aeff_scale) and a first-order profile otherwise.  A response with bounds
+(`NuisanceResponse(..., lower=, upper=)`, `from_maker(..., bounded=True)`: the parameters' ranges as displacements
+from the point's values) fits every eta inside them, as a host minimiser working in the rescaled box [0, 1] would
+(csrc/profile_bounded.hip; DESIGN.md §4, "Profiled trial ensembles: bounds"): a fitted coordinate on a bound equals
+the bound, and a response without bounds is fitted as before.  Without `response` a parameter that is not a dimension
+of the grid stays at the value it had when the grid was made, and every call gives what it gave before the argument
+existed.
 
 The batch evaluator is an argument (`solver=`, default `DeviceSolver`): an object with
     matrix(kind, data, expected, sigma2) -> [T, K]
@@ -52,6 +55,10 @@ and, for `response=`,
         -> dict(value [T, K], eta [T, K, J], n_iter [T, K], status [T, K])
     profiled_best(kind, data, expected, response, sigma2, inv_prior_sigma, center, offset, k0, max_iter)
         -> dict(best [T], arg [T], at [T], eta_best [T, J], eta_at [T, J], status [T])
+and, for a `response` that has bounds, the same two methods with the keywords
+    lower=, upper=  ([J] or [K, J] host arrays of displacements, -inf / +inf for no bound)
+which the drivers pass ONLY for such a response: a solver that knows nothing of bounds keeps working with responses
+that have none, and a bounded response on it is refused,
 so that everything around the kernels can run with a numpy restatement (tests/ensemble_cases.py,
 tests/fluctuate_cases.py, tests/fluctuate_method_cases.py, tests/profile_cases.py).
 """
@@ -111,21 +118,22 @@ class DeviceSolver:
         return self._run(K.metric_matrix_best, kind, (data, expected, sigma2, offset), k0=int(k0))
 
     def profiled_matrix(self, kind, data, expected, response, sigma2=None, inv_prior_sigma=None, center=None,
-                        max_iter=32):
+                        max_iter=32, lower=None, upper=None):
         from pisa_amd import kernels as K
 
-        data, expected, response, sigma2, ips, center = [self._up(a) for a in (data, expected, response, sigma2,
-                                                                               inv_prior_sigma, center)]
-        return K.profiled_metric_matrix(kind, data, expected, response, sigma2, ips, center, max_iter=max_iter)
+        data, expected, response, sigma2, ips, center, lower, upper = [self._up(a) for a in (
+            data, expected, response, sigma2, inv_prior_sigma, center, lower, upper)]
+        return K.profiled_metric_matrix(kind, data, expected, response, sigma2, ips, center, max_iter=max_iter,
+                                        lower=lower, upper=upper)
 
     def profiled_best(self, kind, data, expected, response, sigma2=None, inv_prior_sigma=None, center=None,
-                      offset=None, k0=0, max_iter=32):
+                      offset=None, k0=0, max_iter=32, lower=None, upper=None):
         from pisa_amd import kernels as K
 
-        data, expected, response, sigma2, ips, center, offset = [self._up(a) for a in (
-            data, expected, response, sigma2, inv_prior_sigma, center, offset)]
+        data, expected, response, sigma2, ips, center, offset, lower, upper = [self._up(a) for a in (
+            data, expected, response, sigma2, inv_prior_sigma, center, offset, lower, upper)]
         return K.profiled_metric_matrix_best(kind, data, expected, response, sigma2, ips, center, offset, int(k0),
-                                             max_iter=max_iter)
+                                             max_iter=max_iter, lower=lower, upper=upper)
 
     def draw(self, mu, n_trials, seed, stream, first_trial=0):
         """[n_trials, B] Poisson draws of the row `mu` on the device (`kernels.poisson_fluctuate`)"""
@@ -297,10 +305,12 @@ class NuisanceResponse:
     0 without one; `center` [K, J] the parameter's value at point k minus its prior mean; `prior_at_point` [K] the
     named parameters' share of `priors_penalty` at point k, which the drivers take out of `grid.penalty` (the fit
     adds the prior at the FITTED value: no prior is counted twice); `values` [K, J] the parameters' values at the
-    points, to which a fitted displacement eta is added.  Arrays of whatever kind the solver takes."""
+    points, to which a fitted displacement eta is added; `lower` / `upper` [J] or [K, J] host arrays (either may be
+    None): the box lower <= eta <= upper every displacement is fitted in, -inf / +inf for no bound (a NaN, or lower >
+    upper, raises ValueError).  Arrays of whatever kind the solver takes."""
 
     def __init__(self, names, response, inv_prior_sigma=None, center=None, prior_at_point=None, values=None,
-                 max_iter=32):
+                 max_iter=32, lower=None, upper=None):
         self.names = tuple(names)
         self.response = response
         n_j = len(self.names)
@@ -315,6 +325,34 @@ class NuisanceResponse:
         self.max_iter = int(max_iter)
         if self.inv_prior_sigma.shape != (n_j,) or np.any(self.inv_prior_sigma < 0):
             raise ValueError("NuisanceResponse: inv_prior_sigma holds one value >= 0 per parameter")
+        self.lower = None if lower is None else np.asarray(lower, dtype=np.float64)
+        self.upper = None if upper is None else np.asarray(upper, dtype=np.float64)
+        shapes = [(n_j,)] + ([(int(response.shape[0]), n_j)] if len(response.shape) == 3 else [])
+        for name, b in (("lower", self.lower), ("upper", self.upper)):
+            if b is None:
+                continue
+            if b.ndim == 2 and len(shapes) == 1:
+                shapes.append((b.shape[0], n_j))        # (a shared response: K is the bounds' own)
+            if b.shape not in shapes:
+                raise ValueError("NuisanceResponse: %s is [%d] or [K, %d], got %s" % (name, n_j, n_j, b.shape))
+            if np.isnan(b).any():
+                raise ValueError("NuisanceResponse: %s holds a NaN" % name)
+        if self.lower is not None and self.upper is not None:
+            if self.lower.ndim != self.upper.ndim:         # one form for both: the kernels take one stride
+                n_k = (self.lower if self.lower.ndim == 2 else self.upper).shape[0]
+                self.lower = np.ascontiguousarray(np.broadcast_to(self.lower, (n_k, n_j)))
+                self.upper = np.ascontiguousarray(np.broadcast_to(self.upper, (n_k, n_j)))
+            if self.lower.shape != self.upper.shape:
+                raise ValueError("NuisanceResponse: lower %s and upper %s do not fit" % (self.lower.shape,
+                                                                                         self.upper.shape))
+            if np.any(self.lower > self.upper):
+                raise ValueError("NuisanceResponse: lower > upper")
+
+    bounded = property(lambda self: self.lower is not None or self.upper is not None)
+
+    def bounds(self):
+        """the keywords a driver passes to the solver's profiled methods: none for a response without bounds"""
+        return dict(lower=self.lower, upper=self.upper) if self.bounded else {}
 
     def offset(self, grid):
         """grid.penalty without the named parameters' share, or None if that is zero everywhere"""
@@ -322,14 +360,16 @@ class NuisanceResponse:
         return off if np.any(off != 0.0) else None
 
     @classmethod
-    def from_maker(cls, hypo_maker, grid, names, test_vals, max_iter=32):
+    def from_maker(cls, hypo_maker, grid, names, test_vals, max_iter=32, bounded=False):
         """The response of `grid`'s templates to the free parameters `names` of `hypo_maker`: at every point of
         `grid.points` the gradients (T_hi - T_lo) / (hi - lo) of `hypo_maker._fisher_templates` (one call per
         parameter, every other parameter at the point's own value; one sweep of the events each where the pipeline
         has the replayable shape) between the point's own value + test_vals[name][0] and + test_vals[name][1]
         (displacements: numbers in the parameter's units, or quantities).  1 / sigma and
         the mean are read from a Gaussian prior; a uniform prior (or none) gives 0; any other kind raises
-        ValueError.  On return the free parameters hold the values they had at entry."""
+        ValueError.  bounded=True: every displacement is fitted inside the parameter's `range`, lower[k, j] =
+        range_j[0] - values[k, j] and upper[k, j] = range_j[1] - values[k, j] in the parameter's units (-inf / +inf
+        for a parameter without a range).  On return the free parameters hold the values they had at entry."""
         from pisa_amd import kernels as K
 
         names = list(names)
@@ -381,7 +421,23 @@ class NuisanceResponse:
         finally:
             hypo_maker.set_free_params(saved)
         center = np.where(ips[None, :] > 0, values - means[None, :], 0.0)
-        return cls(names, K.to_device(resp), ips, center, at_point, values, max_iter)
+        lower = upper = None
+        if bounded:
+            lower, upper = np.full(values.shape, -np.inf), np.full(values.shape, np.inf)
+            for j, name in enumerate(names):
+                prm = free[name]
+                if prm._range is not None:
+                    lower[:, j] = float(prm._range[0].m_as(prm._units)) - values[:, j]
+                    upper[:, j] = float(prm._range[1].m_as(prm._units)) - values[:, j]
+        return cls(names, K.to_device(resp), ips, center, at_point, values, max_iter, lower, upper)
+
+
+def _takes_bounds(method):
+    import inspect
+
+    params = inspect.signature(method).parameters
+    return ("lower" in params and "upper" in params) or any(
+        p.kind is inspect.Parameter.VAR_KEYWORD for p in params.values())
 
 
 def _check_response(response, grid, solver, what, metric=None):
@@ -391,10 +447,17 @@ def _check_response(response, grid, solver, what, metric=None):
     if not hasattr(solver, "profiled_matrix") or not hasattr(solver, "profiled_best"):
         raise ValueError("ensemble: response= needs a solver with profiled_matrix and profiled_best; %s has none"
                          % type(solver).__name__)
+    if response.bounded and not (_takes_bounds(solver.profiled_matrix) and _takes_bounds(solver.profiled_best)):
+        raise ValueError("ensemble: a response with bounds needs a solver whose profiled_matrix and profiled_best "
+                         "take lower= and upper=; those of %s do not" % type(solver).__name__)
     shape = tuple(response.response.shape)
     if shape[-1] != grid.n_bins or (len(shape) == 3 and shape[0] != len(grid)):
         raise ValueError("%s: the response does not belong to this grid (%s against %d points, %d bins)"
                          % (what, shape, len(grid), grid.n_bins))
+    for b in (response.lower, response.upper):
+        if b is not None and b.ndim == 2 and b.shape[0] != len(grid):
+            raise ValueError("%s: the response's bounds do not belong to this grid (%s against %d points)"
+                             % (what, b.shape, len(grid)))
 
 
 GENERATORS = ("host", "device")
@@ -538,7 +601,8 @@ def metric_matrix(data, grid, metric, with_penalty=True, solver=None, response=N
     else:
         _check_response(response, grid, solver, "metric_matrix", metric)
         m = solver.profiled_matrix(metric, _data_rows(data), grid.hist, response.response, grid.sigma2_for(metric),
-                                   response.inv_prior_sigma, response.center, response.max_iter)["value"]
+                                   response.inv_prior_sigma, response.center, response.max_iter,
+                                   **response.bounds())["value"]
         penalty = response.offset(grid)
     if with_penalty and penalty is not None:
         if hasattr(m, "cpu"):
@@ -571,7 +635,7 @@ def delta_metric(data, grid, metric, k0, solver=None, response=None, return_info
     _check_response(response, grid, solver, "delta_metric", metric)
     out = solver.profiled_best(metric, _data_rows(data), grid.hist, response.response, grid.sigma2_for(metric),
                                response.inv_prior_sigma, response.center, response.offset(grid), int(k0),
-                               response.max_iter)
+                               response.max_iter, **response.bounds())
     best, at = _host(out["best"]), _host(out["at"])
     delta = best - at if metric in _MAXIMISED else at - best
     if not return_info:

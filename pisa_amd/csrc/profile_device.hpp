@@ -11,8 +11,11 @@
 // the trial point or halves the step, factors the Hessian (left-looking Cholesky, the pivot rule of hsfit.hip),
 // forms the next step and tests the Newton decrement against the rounding floor of Phi.  When the pair is done,
 // one sweep of `pf_value_bin` forms the reported metric at the last accepted eta the way ens_direct_kernel does.
+// The bounded form (`pf_init_bounded`, `pf_decide_bounded`; profile_bounded.hip) is the same state machine with a
+// projected step: eta_hat minimises Phi over lo_j <= eta_j <= hi_j ("Profiled trial ensembles: bounds";
+// restated in tests/profile_bounded_cases.py).
 // No HIP type or call: the same source compiles for the host with a plain C++ compiler; tests/test_host_profiled.py
-// runs it there, under the sanitizers, against the numpy restatement.
+// and tests/test_host_profiled_bounded.py run it there, under the sanitizers, against the numpy restatements.
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -28,6 +31,7 @@ namespace pisa {
 constexpr int PF_MAX_PARAMS = 8;           // PISA_HIP_PROFILE_MAX_PARAMS
 constexpr int PF_LLH = 0, PF_POISSON_LLH = 1, PF_CHI2 = 2, PF_MOD_CHI2 = 3;   // PISA_HIP_METRIC_*
 constexpr int PF_NOT_CONVERGED = 1, PF_BOUNDARY = 2, PF_NOT_POSDEF = 4, PF_START_OUTSIDE = 8;   // PISA_HIP_PROFILE_*
+constexpr int PF_BAD_BOUNDS = 16;          // (the bounded form alone)
 constexpr double PF_SMALL_POS = 1e-10;     // stats.py:40 (SMALL_POS of metric_device.hpp)
 constexpr double PF_EPS = 2.220446049250313e-16;
 constexpr double PF_PIVOT_REL = 1e-13;     // HS_PIVOT_REL of hsfit.hip
@@ -84,6 +88,7 @@ struct PfState {
     double Phi, floor_, alpha;   // at eta: Phi and its rounding floor; the share of `step` of the trial point
     double lam2;                 // at eta: the squared Newton decrement of `step`
     int32_t n_iter, n_halve, status;
+    uint32_t on_bound;           // the bounded form: bit j: eta_t[j] == lo[j], bit 8 + j: eta_t[j] == hi[j] (`pf_hold`)
     bool inside, cut, boundary, first, done;
 };
 
@@ -94,8 +99,47 @@ PISA_PF_HD void pf_init(PfState<J> &st) {
     st.Phi = st.floor_ = st.lam2 = 0.0;
     st.alpha = 1.0;
     st.n_iter = st.n_halve = st.status = 0;
+    st.on_bound = 0;
     st.cut = st.boundary = st.done = false;
     st.first = true;
+}
+
+// x held inside [lo, hi].  Comparisons, not fmin / fmax: a NaN passes through unchanged, and a clamped coordinate
+// holds the bound's own double, so that `eta == bound` recognises it.
+PISA_PF_HD double pf_clamp(double x, double lo, double hi) { return x < lo ? lo : (x > hi ? hi : x); }
+
+// x [J] held inside the box, and which of its coordinates now equal a bound.  The bounds are read here, where a step
+// has just been formed and gradient and Hessian are dead, and nowhere else: `pf_bind` needs the marks alone.
+template <int J>
+PISA_PF_HD void pf_hold(PfState<J> &st, double *x, const double *lo, const double *hi) {
+    uint32_t m = 0;
+#pragma unroll
+    for (int j = 0; j < J; j++) {
+        const double l = lo[j], h = hi[j], y = pf_clamp(x[j], l, h);
+        if (y == l) m |= 1u << j;
+        if (y == h) m |= 0x100u << j;
+        x[j] = y;
+    }
+    st.on_bound = m;
+}
+
+// the bounded form ("Profiled trial ensembles: bounds"): the fit starts at 0 held inside the box.  A
+// box with a bound that does not satisfy lo <= hi (a NaN among them) is refused: the pair takes no step, eta = 0.
+template <int J>
+PISA_PF_HD void pf_init_bounded(PfState<J> &st, const double *lo, const double *hi) {
+    pf_init<J>(st);
+    bool ok = true;
+#pragma unroll
+    for (int j = 0; j < J; j++)
+        if (!(lo[j] <= hi[j])) ok = false;
+    if (!ok) {
+        st.status |= PF_BAD_BOUNDS;
+        st.done = true;
+        return;
+    }
+    pf_hold<J>(st, st.eta_t, lo, hi);
+#pragma unroll
+    for (int j = 0; j < J; j++) st.eta[j] = st.eta_t[j];
 }
 
 template <int J>
@@ -216,10 +260,44 @@ PISA_PF_HD void pf_trial(PfState<J> &st) {
     for (int j = 0; j < J; j++) st.eta_t[j] = st.eta[j] + st.alpha * st.step[j];
 }
 
+template <int J>
+PISA_PF_HD void pf_trial_bounded(PfState<J> &st, const double *lo, const double *hi) {
+    pf_trial<J>(st);
+    pf_hold<J>(st, st.eta_t, lo, hi);
+}
+
+// The bound set of the projected Newton step at the accepted eta: the coordinates that sit on a bound with the
+// gradient pointing out of the box.  They leave the system that `pf_factor` and `pf_solve` see (g_j = 0, row and
+// column j of H those of the unit matrix: their step is 0 and `lam2` is the decrement of the free block).  A
+// coordinate on a bound whose gradient points inward stays free; if its Newton step points outward the clamp holds it.
+// A pinned coordinate (lo == hi) is no variable and belongs to the set whatever its gradient: at an exact fit the
+// gradient is 0 in every coordinate, and a pinned one set free there would bring back the singular Hessian it was
+// pinned to avoid.
+template <int J>
+PISA_PF_HD void pf_bind(PfState<J> &st) {
+    const uint32_t on = st.on_bound;   // (of the trial point that has just become eta)
+    uint32_t bound = 0;
+#pragma unroll
+    for (int j = 0; j < J; j++) {
+        const double gj = st.g[j];
+        const bool at_lo = on >> j & 1u, at_hi = on >> (8 + j) & 1u;
+        if ((at_lo && at_hi) || (at_lo && gj > 0.0) || (at_hi && gj < 0.0)) bound |= 1u << j;
+    }
+#pragma unroll
+    for (int i = 0; i < J; i++) {
+        if (bound >> i & 1u) st.g[i] = 0.0;
+#pragma unroll
+        for (int j = 0; j <= i; j++)
+            if ((bound >> i | bound >> j) & 1u) st.H[pf_at(i, j)] = i == j ? 1.0 : 0.0;
+    }
+}
+
 // after a sweep at eta_t: the priors join, the trial point is accepted or the step halved; on acceptance the next
-// step is formed.  Sets `done` when the pair has its final eta.
-template <int KIND, int J>
-PISA_PF_HD void pf_decide(PfState<J> &st, const double *ips, const double *c, int32_t max_iter) {
+// step is formed.  Sets `done` when the pair has its final eta.  BOUNDED: every trial point and the last step are
+// held inside [lo, hi] and the step is that of the free block (`pf_bind`); nothing else differs.
+template <int KIND, int J, bool BOUNDED>
+PISA_PF_HD void pf_decide_any(PfState<J> &st, const double *ips, const double *c, const double *lo, const double *hi,
+                              int32_t max_iter) {
     constexpr double w = PfKind<KIND>::w;
     double phi_t = st.phi_s + st.phi_c;
 #pragma unroll
@@ -248,7 +326,10 @@ PISA_PF_HD void pf_decide(PfState<J> &st, const double *ips, const double *c, in
             return;
         }
         st.alpha *= 0.5;
-        pf_trial<J>(st);
+        if (BOUNDED)
+            pf_trial_bounded<J>(st, lo, hi);
+        else
+            pf_trial<J>(st);
         return;
     }
     // accepted
@@ -257,6 +338,7 @@ PISA_PF_HD void pf_decide(PfState<J> &st, const double *ips, const double *c, in
     st.Phi = phi_t;
     st.floor_ = (0.5 * PF_EPS) * st.scale;
     st.boundary = st.cut;
+    if (BOUNDED) pf_bind<J>(st);
     if (!pf_factor<J>(st.H)) {
         st.status |= PF_NOT_POSDEF;
         st.done = true;
@@ -266,6 +348,7 @@ PISA_PF_HD void pf_decide(PfState<J> &st, const double *ips, const double *c, in
     if (st.lam2 <= PF_STOP_REL * st.floor_) {
 #pragma unroll
         for (int j = 0; j < J; j++) st.eta[j] = st.eta[j] + st.step[j];
+        if (BOUNDED) pf_hold<J>(st, st.eta, lo, hi);
         st.boundary = false;   // a stationary point inside the domain, however the last step got there
         st.done = true;
         return;
@@ -279,7 +362,21 @@ PISA_PF_HD void pf_decide(PfState<J> &st, const double *ips, const double *c, in
     st.alpha = 1.0;
     st.n_halve = 0;
     st.cut = false;
-    pf_trial<J>(st);
+    if (BOUNDED)
+        pf_trial_bounded<J>(st, lo, hi);
+    else
+        pf_trial<J>(st);
+}
+
+template <int KIND, int J>
+PISA_PF_HD void pf_decide(PfState<J> &st, const double *ips, const double *c, int32_t max_iter) {
+    pf_decide_any<KIND, J, false>(st, ips, c, nullptr, nullptr, max_iter);
+}
+
+template <int KIND, int J>
+PISA_PF_HD void pf_decide_bounded(PfState<J> &st, const double *ips, const double *c, const double *lo,
+                                  const double *hi, int32_t max_iter) {
+    pf_decide_any<KIND, J, true>(st, ips, c, lo, hi, max_iter);
 }
 
 template <int J>

@@ -819,17 +819,37 @@ def _profile_args(what, kind, data, expected, response, sigma2, inv_prior_sigma,
     return data, expected, response, sigma2, inv_prior_sigma, center, stride, data.shape[0], n_k, n_b, n_j
 
 
+def _bound_args(what, lower, upper, n_k, n_j):
+    """(lower, upper, stride) of the bounded entry points: float64 device tensors [n_params] (stride 0: shared by all
+    templates) or [n_templates, n_params]; either may be None (no bound on that side).  One of each form: the shared
+    one is written out per template, since both are read with one stride."""
+    for name, b in (("lower", lower), ("upper", upper)):
+        if b is not None and (b.dtype != F8 or tuple(b.shape) not in ((n_j,), (n_k, n_j))):
+            raise ValueError("%s: %s is float64 [n_params] or [n_templates, n_params]" % (what, name))
+    per_template = any(b is not None and b.dim() == 2 for b in (lower, upper))
+    out = [None if b is None else (b.expand(n_k, n_j) if per_template else b).contiguous() for b in (lower, upper)]
+    return out[0], out[1], n_j if per_template else 0
+
+
 def profiled_metric_matrix(kind, data, expected, response, sigma2=None, inv_prior_sigma=None, center=None,
-                           max_iter=32, want_eta=True, status=None):
+                           max_iter=32, want_eta=True, status=None, lower=None, upper=None):
     """`metric_matrix` with linearised nuisance parameters fitted per (trial, template) pair
     (`pisa_hip_profiled_metric_matrix`): the template of pair (t, k) is expected[k] + sum_j response[k, j]
     eta_j with eta minimising the metric's own convex objective plus the Gaussian priors (inv_prior_sigma_j (eta_j +
     center[k, j]))^2.  data [T, B], expected / sigma2 [K, B], response [K, J, B] or [J, B] (shared), inv_prior_sigma
     [J], center [K, J]: float64 device tensors.  -> dict(value [T, K], eta [T, K, J] (None unless want_eta), n_iter
     [T, K] int32, status [T, K] int32: the `_lib.PROFILE_*` bit flags; a flagged pair holds the metric at its last
-    accepted eta).  A negative datum or expectation raises ValueError."""
+    accepted eta).  A negative datum or expectation raises ValueError.
+    lower / upper (float64 device tensors [J] or [K, J]; either may be None): eta is fitted inside lower <= eta <= upper
+    (`pisa_hip_profiled_metric_matrix_bounded`; displacements in the parameter's units, -inf / +inf for no bound,
+    lower == upper pins a parameter).  A fitted coordinate on a bound equals the bound; a template with lower > upper
+    or a NaN bound gives pairs flagged `_lib.PROFILE_BAD_BOUNDS` that stay at eta = 0.  With both None the call is
+    what it was before the arguments existed."""
     (data, expected, response, sigma2, ips, center, stride, n_t, n_k, n_bins, n_j) = _profile_args(
         "profiled_metric_matrix", kind, data, expected, response, sigma2, inv_prior_sigma, center, max_iter)
+    bounded = lower is not None or upper is not None
+    if bounded:
+        lower, upper, b_stride = _bound_args("profiled_metric_matrix", lower, upper, n_k, n_j)
     dev = data.device
     value = torch.empty((n_t, n_k), dtype=F8, device=dev)
     eta = torch.empty((n_t, n_k, n_j), dtype=F8, device=dev) if want_eta else None
@@ -837,6 +857,12 @@ def profiled_metric_matrix(kind, data, expected, response, sigma2=None, inv_prio
     pair_status = torch.empty((n_t, n_k), dtype=torch.int32, device=dev)
 
     def launch(status):
+        if bounded:
+            _lib.check(_lib.lib().pisa_hip_profiled_metric_matrix_bounded(
+                METRIC_KIND[kind], _ptr(data), _ptr(expected), _ptr(sigma2), _ptr(response), stride, _ptr(ips),
+                _ptr(center), _ptr(lower), _ptr(upper), b_stride, n_j, int(max_iter), n_t, n_k, n_bins, _ptr(value),
+                _ptr(eta), _ptr(n_iter), _ptr(pair_status), _ptr(status), _stream()))
+            return
         _lib.check(_lib.lib().pisa_hip_profiled_metric_matrix(
             METRIC_KIND[kind], _ptr(data), _ptr(expected), _ptr(sigma2), _ptr(response), stride, _ptr(ips),
             _ptr(center), n_j, int(max_iter), n_t, n_k, n_bins, _ptr(value), _ptr(eta), _ptr(n_iter),
@@ -847,13 +873,17 @@ def profiled_metric_matrix(kind, data, expected, response, sigma2=None, inv_prio
 
 
 def profiled_metric_matrix_best(kind, data, expected, response, sigma2=None, inv_prior_sigma=None, center=None,
-                                offset=None, k0=0, max_iter=32, status=None):
+                                offset=None, k0=0, max_iter=32, status=None, lower=None, upper=None):
     """the matrix of `profiled_metric_matrix` (+ offset [K] per column) reduced per trial without being written
     (`pisa_hip_profiled_metric_matrix_best`) -> dict(best [T], arg [T] int32, at [T]: column k0, eta_best and eta_at
     [T, J]: the fitted displacements at both columns, status [T] int32: the flags of the pair at arg OR those of
-    the pair at k0), bit for bit the reduction of the full output"""
+    the pair at k0), bit for bit the reduction of the full output.  lower / upper: as in `profiled_metric_matrix`
+    (`pisa_hip_profiled_metric_matrix_best_bounded`)"""
     (data, expected, response, sigma2, ips, center, stride, n_t, n_k, n_bins, n_j) = _profile_args(
         "profiled_metric_matrix_best", kind, data, expected, response, sigma2, inv_prior_sigma, center, max_iter)
+    bounded = lower is not None or upper is not None
+    if bounded:
+        lower, upper, b_stride = _bound_args("profiled_metric_matrix_best", lower, upper, n_k, n_j)
     dev = data.device
     offset = _offset_arg("profiled_metric_matrix_best", offset, n_k)
     best = torch.empty(n_t, dtype=F8, device=dev)
@@ -864,6 +894,13 @@ def profiled_metric_matrix_best(kind, data, expected, response, sigma2=None, inv
     trial_status = torch.empty(n_t, dtype=torch.int32, device=dev)
 
     def launch(status):
+        if bounded:
+            _lib.check(_lib.lib().pisa_hip_profiled_metric_matrix_best_bounded(
+                METRIC_KIND[kind], _ptr(data), _ptr(expected), _ptr(sigma2), _ptr(response), stride, _ptr(ips),
+                _ptr(center), _ptr(lower), _ptr(upper), b_stride, _ptr(offset), int(k0), n_j, int(max_iter), n_t, n_k,
+                n_bins, _ptr(best), _ptr(arg), _ptr(at), _ptr(eta_best), _ptr(eta_at), _ptr(trial_status),
+                _ptr(status), _stream()))
+            return
         _lib.check(_lib.lib().pisa_hip_profiled_metric_matrix_best(
             METRIC_KIND[kind], _ptr(data), _ptr(expected), _ptr(sigma2), _ptr(response), stride, _ptr(ips),
             _ptr(center), _ptr(offset), int(k0), n_j, int(max_iter), n_t, n_k, n_bins, _ptr(best), _ptr(arg),

@@ -110,9 +110,12 @@ def kernel_lines(reps, forms=("direct", "product")):
         del d, e
 
 
-def profiled_lines(n_params, reps):
+def profiled_lines(n_params, reps, bounded=None):
     """`profiled_metric_matrix_best` with J = n_params fitted nuisance displacements per pair, every kind, against the
     unprofiled direct reduced form of the same run; iteration counts from the full output on the first trials.
+    `bounded` = H: the bounded reduced form (every eta_j inside -H ... +H prior sigmas) is timed in the same run, with
+    its own iteration counts, the share of the head's pairs that end with a coordinate on a bound and the time per
+    sweep of both forms (ms / (mean Newton steps + 2): the sweeps of the fit and the one of the value).
     Executed flops: per bin of a sweep 2 J (mu) + 2 J (its reach) + 2 J (gradient) + J + J (J + 1) (Hessian) + 20 (the
     terms of phi, a transcendental counted as one), sweeps = Newton steps + 1 (halved steps not counted), + one sweep
     of 2 J + 10 for the value."""
@@ -150,6 +153,24 @@ def profiled_lines(n_params, reps):
                                   iter_mean=round(float(it.mean().item()), 3), iter_max=int(it.max().item()),
                                   flagged_of_head=flagged, head_pairs=int(it.numel()), tflops=round(tflops, 3),
                                   frac_of_fp64_vector_peak=round(tflops / FP64_PEAK_TFLOPS, 4))), flush=True)
+            if bounded is not None:
+                hi = float(bounded) / ips
+                lo = -hi
+                head_b = K.profiled_metric_matrix(kind, d[:n_head], e, r, sig, ips, status=status, lower=lo, upper=hi)
+                it_b = head_b["n_iter"].double()
+                on = ((head_b["eta"] == lo) | (head_b["eta"] == hi)).any(dim=2)
+                res_b = _time(lambda: K.profiled_metric_matrix_best(kind, d, e, r, sig, ips, k0=n_k // 2, status=status,
+                                                                    lower=lo, upper=hi), reps)
+                sweeps, sweeps_b = float(it.mean().item()) + 2.0, float(it_b.mean().item()) + 2.0
+                print(json.dumps(dict(workload="profiled_kernel_bounded", T=n_t, K=n_k, B=n_b, J=J, kind=kind,
+                                      output="reduced", half_width_sigmas=float(bounded), **res_b,
+                                      ms_unbounded=res["ms_median"],
+                                      ratio_to_unbounded=round(res_b["ms_median"] / res["ms_median"], 3),
+                                      iter_mean=round(float(it_b.mean().item()), 3), iter_max=int(it_b.max().item()),
+                                      flagged_of_head=int((head_b["status"] != 0).sum().item()),
+                                      on_bound_of_head=round(float(on.double().mean().item()), 4),
+                                      ms_per_sweep=round(res_b["ms_median"] / sweeps_b, 3),
+                                      ms_per_sweep_unbounded=round(res["ms_median"] / sweeps, 3))), flush=True)
         assert int(status.item()) == 0
         del d, e, r
 
@@ -327,6 +348,9 @@ def main():
     ap.add_argument("--method", default="poisson", help="the fluctuation method of the end-to-end run")
     ap.add_argument("--profiled", type=int, default=0, metavar="J",
                     help="also time the profiled reduced form with J fitted nuisance parameters (1 to 8)")
+    ap.add_argument("--bounded", type=float, default=None, metavar="H",
+                    help="with --profiled: also time the bounded reduced form, every displacement inside -H ... +H "
+                         "prior sigmas")
     ap.add_argument("--mc", action="store_true",
                     help="time the MC-uncertainty metrics against the loop over kernels.metric, and nothing else")
     args = ap.parse_args()
@@ -339,7 +363,7 @@ def main():
     if not args.skip_kernels:
         kernel_lines(args.reps, tuple(args.forms.split(",")))
     if args.profiled:
-        profiled_lines(args.profiled, args.reps)
+        profiled_lines(args.profiled, args.reps, args.bounded)
     if not args.skip_draw:
         draw_lines(args.reps)
     if not args.skip_e2e:
