@@ -3,7 +3,7 @@
 //   gpllh_bin_sums_kernel   Sigma w, Sigma w^2 over the events of each bin (CSR event lists)
 //   gpllh_params_kernel     (Sigma w, Sigma w^2, n, mean adjustment) -> alpha, beta, pseudo-filled weight sum
 //   gpllh_metric_kernel     per-bin values (gpllh_device.hpp) and their total
-// The fused tail of an evaluation (limbs -> the same three steps in one launch) is finalize_gpllh_kernel in hist.hip.
+// The fused tail of an evaluation (limbs -> the same three steps in one launch) is finalize_gpllh_kernel in hist_tail.hip.
 #include "gpllh_device.hpp"
 
 namespace pisa {

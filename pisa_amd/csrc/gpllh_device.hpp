@@ -1,5 +1,5 @@
 // gpllh_device.hpp -- the generalized Poisson-gamma likelihood (arXiv:1902.08831, eq. 91) shared by the
-// unfused kernels (gpllh.hip) and the fused tail of an evaluation (hist.hip): both call these functions with
+// unfused kernels (gpllh.hip) and the fused tail of an evaluation (hist_tail.hip): both call these functions with
 // the same inputs in the same launch shape, so the two paths agree bit for bit.
 //
 // Launch shape of the bin evaluation: ONE wavefront (a 64-thread workgroup) per bin.  Bins whose every container

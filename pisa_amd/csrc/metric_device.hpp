@@ -1,5 +1,5 @@
 // metric_device.hpp -- per-bin metric term shared by metric_kernel
-// (metric_flux.hip) and the fused finalize+metric kernel (hist.hip).
+// (metric_flux.hip) and the fused finalize+metric kernel (hist_tail.hip).
 #pragma once
 #include "common.hpp"
 

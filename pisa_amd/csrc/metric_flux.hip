@@ -9,7 +9,7 @@
 
 namespace pisa {
 
-// The metrics beyond the four of the fused tail (hist.hip), per bin, from the raw expectation and its variance:
+// The metrics beyond the four of the fused tail (hist_tail.hip), per bin, from the raw expectation and its variance:
 //   correct_chi2          (k - l)^2 / (s2 + l) + ln(s2 + l)                        stats.py:697-730
 //   signed_sqrt_mod_chi2  (k - l) / sqrt(s2 + l)                                   stats.py:762-786
 //   mcllh_mean / _eff     Poisson-gamma mixture with a = 0 / 1, b = 0              stats.py:328-438,
@@ -134,7 +134,7 @@ metric_kernel(int kind, const double *__restrict__ actual, const double *__restr
 // bin per thread, the per-workgroup sums (the same tree as above) go to scratch, and a second
 // single-workgroup kernel adds them in index order with the same tree.  Deterministic for a
 // given n_bins; the association of the total differs from the one-workgroup form, which is
-// why small maps keep that one (it is what the fused tail kernel of hist.hip reproduces).
+// why small maps keep that one (it is what the fused tail kernel of hist_tail.hip reproduces).
 constexpr int64_t METRIC_ONE_WG_MAX = 4096;  // = PISA_HIP_FINALIZE_METRIC_MAX: every map the fused tail can take
 
 __global__ void __launch_bounds__(256)

@@ -136,7 +136,7 @@ order_interleave_kernel(const uint32_t *__restrict__ seq, int64_t n, const unsig
 //   call 2 (`_assemble`): the bank order inside whole 4 096-event windows of every partition with >= 8 192 events (the
 //                     window kernel above, per segment), then every output position's source in closed form from the
 //                     host's table (depositing blocks spread evenly among a partition's idle blocks).
-constexpr int PORD_MAX_PART = 255;      // (PART_MAX of hist.hip)
+constexpr int PORD_MAX_PART = 255;      // (PART_MAX of hist_device.hpp)
 
 __global__ void __launch_bounds__(256)
 part_key_kernel(const int32_t *__restrict__ node, const int32_t *__restrict__ bin, int64_t n, uint32_t n_nodes, uint32_t width,

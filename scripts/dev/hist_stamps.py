@@ -1,4 +1,5 @@
-"""time stamps inside hist_accumulate_kernel (library built with EXTRA=-DPISA_HIST_STAMPS):
+"""time stamps inside hist_planned_kernel, or with HIST_STAMPS=general inside hist_accumulate_kernel (what a binning
+without a plan, e.g. fine3d, runs) (library built with EXTRA=-DPISA_HIST_STAMPS):
 per workgroup: entry, container found + first loads issued, accumulators cleared, loop done, barrier,
 flushed -- in us relative to the first workgroup's entry (wall_clock64 = 100 MHz)"""
 import ctypes as C
@@ -24,8 +25,9 @@ for _ in range(5):
 torch.cuda.synchronize()
 buf = (C.c_ulonglong * (8 * 1024))()
 lib = _lib.lib()
-lib.pisa_hip_debug_hist_stamps.argtypes = [C.c_void_p]
-assert lib.pisa_hip_debug_hist_stamps(buf) == 0
+read = lib.pisa_hip_debug_hist_stamps_general if os.environ.get("HIST_STAMPS") == "general" else lib.pisa_hip_debug_hist_stamps
+read.argtypes = [C.c_void_p]
+assert read(buf) == 0
 t = np.frombuffer(buf, dtype=np.uint64).reshape(1024, 8).astype(np.float64)
 used = t[:, 0] > 0
 t = t[used][:, :6]

@@ -1,6 +1,6 @@
 """Basic blocks of one kernel in a compiler assembly file, with instruction counts by class (development; no GPU).
-    python scripts/dev/hist_sweep_mix.py hist.s '_ZN4pisa22hist_accumulate_kernelILi7ELb1ELi0ELb1EE' [first_block last_block]
-hist.s: hist.hip compiled with the Makefile's flags plus `-S --cuda-device-only`.  Without a block range: one line per
+    python scripts/dev/hist_sweep_mix.py hist_planned.s '_ZN4pisa19hist_planned_kernelE' [first_block last_block]
+hist_planned.s: hist_planned.hip compiled with the Makefile's flags plus `-S --cuda-device-only`.  Without a block range: one line per
 basic block (label, loop depth, counts, where it branches to) -- enough to follow the path a wavefront takes through the
 sweep; with a range: the totals over those blocks (the blocks of the all-fast path of one sweep are contiguous)."""
 import collections, re, sys

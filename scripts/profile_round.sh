@@ -103,21 +103,22 @@ import csv, json
 OUT = "$OUT"
 def per_launch(path, kernel, name):
     v = [float(r["Counter_Value"]) for r in csv.DictReader(open(path))
-         if kernel in r["Kernel_Name"] and r["Counter_Name"] == name]
+         if any(k in r["Kernel_Name"] for k in kernel) and r["Counter_Name"] == name]
     return (sum(v) / len(v), len(v)) if v else (float("nan"), 0)
 METHOD = ("timeout 600 rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes (bench.py --steps 3 --no-kernel-timing); "
           "FETCH_SIZE is in KiB and on gfx950 reports half of the bytes of 16-B/lane coalesced streams "
           "(MI355X_MICROARCH.md, HBM section) -> doubled; WRITE_SIZE exact")
+ACCUMULATE = ("hist_accumulate_kernel", "hist_planned_kernel")   # the general forms / the planned sweep of the headline
 def traffic(tag, label, alg, fname):
-    f, nf = per_launch("%s/pmc_%s_FETCH_SIZE.csv" % (OUT, tag), "hist_accumulate_kernel", "FETCH_SIZE")
-    w, nw = per_launch("%s/pmc_%s_WRITE_SIZE.csv" % (OUT, tag), "hist_accumulate_kernel", "WRITE_SIZE")
+    f, nf = per_launch("%s/pmc_%s_FETCH_SIZE.csv" % (OUT, tag), ACCUMULATE, "FETCH_SIZE")
+    w, nw = per_launch("%s/pmc_%s_WRITE_SIZE.csv" % (OUT, tag), ACCUMULATE, "WRITE_SIZE")
     d = {"kernel": label, "FETCH_SIZE_KB": f, "WRITE_SIZE_KB": w, "launches": [nf, nw],
          "fetch_bytes_corrected": f * 1024 * 2, "write_bytes": w * 1024, "hbm_bytes": f * 1024 * 2 + w * 1024,
          "method": METHOD, "algorithmic_bytes": alg, "ratio_to_algorithmic": (f * 1024 * 2 + w * 1024) / alg}
     json.dump(d, open("%s/%s" % (OUT, fname), "w"), indent=1)
     print(fname, d["hbm_bytes"], d["ratio_to_algorithmic"], d["launches"])
-traffic("main", "hist_accumulate_kernel<7,true> (16-bit index layout, 20 B/event), 9999996 events", 20 * 9999996, "traffic.json")
-traffic("l3", "hist_accumulate_kernel<7,true>, 39999996 events (800 MB resident: beyond the 256 MiB Infinity Cache)", 20 * 39999996, "traffic_l3_exceeding.json")
+traffic("main", "hist_planned_kernel (16-bit index layout, 20 B/event), 9999996 events", 20 * 9999996, "traffic.json")
+traffic("l3", "hist_planned_kernel, 39999996 events (800 MB resident: beyond the 256 MiB Infinity Cache)", 20 * 39999996, "traffic_l3_exceeding.json")
 traffic("coord", "hist_accumulate_kernel<1,true> (coordinate form, SURVEY 8(d) 72 B/event), 9999996 events", 72 * 9999996, "traffic_coordinate_form.json")
 traffic("fine", "hist_accumulate_kernel<7,true>, 40x40x3 = 4 800 output bins (partitioned LDS-window order), 9999996 events", 20 * 9999996, "traffic_fine_binning.json")
 # executed fp64 lane operations of prob3_events_kernel.  One evaluation = one launch per sign, each over
@@ -189,7 +190,8 @@ for r in list(csv.reader(open(OUT + "/kernel_stats.csv")))[:8]:
 rows = sorted(csv.DictReader(open(OUT + "/stats/bench_kernel_trace.csv")), key=lambda r: int(r["Start_Timestamp"]))
 phase = {}
 for key in ("hist_accumulate_kernel", "prob3_terms_kernel", "prob3_chain_kernel", "finalize_metric_kernel"):
-    d = [int(r["End_Timestamp"]) - int(r["Start_Timestamp"]) for r in rows if key in r["Kernel_Name"]]
+    names = ("hist_accumulate_kernel", "hist_planned_kernel") if key == "hist_accumulate_kernel" else (key,)   # (the accumulate launch: either kernel)
+    d = [int(r["End_Timestamp"]) - int(r["Start_Timestamp"]) for r in rows if any(k in r["Kernel_Name"] for k in names)]
     loop = d[21:521]
     phase[key] = {"timed_loop_mean_us": sum(loop) / len(loop) / 1e3, "all_launches_mean_us": sum(d) / len(d) / 1e3,
                   "launches": len(d)}

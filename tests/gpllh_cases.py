@@ -1,6 +1,6 @@
 """Shared pieces of the tests of the generalized Poisson-gamma likelihood (arXiv:1902.08831 eq. 91; `gpllh_bin`,
 `gpllh_params`, `gpllh_publish_and_total` of csrc/gpllh_device.hpp, called by `gpllh_metric_kernel` of csrc/gpllh.hip
-and by `finalize_gpllh_kernel` of csrc/hist.hip, and `gpllh_bin_sums_kernel`): the case families, a numpy restatement
+and by `finalize_gpllh_kernel` of csrc/hist_tail.hip, and `gpllh_bin_sums_kernel`): the case families, a numpy restatement
 of the kernels' arithmetic in the kernels' own order, and the gate.  A plain helper module (no fixtures, no GPU, no
 mpmath); `tests/test_host_gpllh_cases.py` pins everything here without a GPU, `tests/test_gpu_gpllh_exact.py` runs the
 kernels.  The exact values (eq. 91 in mpmath at 60 digits, `python oracle/gen_gpllh_exact.py`) are committed as

@@ -71,7 +71,7 @@ def _fields(x):
 
 
 def kernel_general(x):
-    """`deposit_units_general` (csrc/hist.hip) on Python integers with the kernel's word sizes: the list
+    """`deposit_units_general` (csrc/hist_device.hpp) on Python integers with the kernel's word sizes: the list
     of (digit index, signed count) it hands to `add`, or None where it refuses"""
     hi, lo = _fields(x)
     ex = (hi >> 20) & 0x7FF

@@ -1,5 +1,5 @@
 """Shared pieces of the tests of the nine map metrics (`metric_bin` of csrc/metric_device.hpp, shared by `metric_kernel`
-and the fused tails of hist.hip, and `metric_bin_wide` of csrc/metric_flux.hip): the seeded case families, the gate
+and the fused tails of hist_tail.hip, and `metric_bin_wide` of csrc/metric_flux.hip): the seeded case families, the gate
 and a host replica of the kernels' reduction trees.  A plain helper module (no fixtures);
 `tests/test_host_metric_cases.py` pins everything here without a GPU, `tests/test_gpu_metric_exact.py` runs the kernels.
 

@@ -1,4 +1,4 @@
-"""The planned sweep's lean body (`hist_accumulate_kernel<7, true, 0, true>`, what `pisa_hip_reweight_hist_planned`
+"""The planned sweep's lean body (`hist_planned_kernel`, csrc/hist_planned.hip: what `pisa_hip_reweight_hist_planned`
 launches): blocks the plan did not mark run without the 0xffff guards, a half-sweep whose weights all pass ONE combined
 range test (2^-26 <= w < 2^38: w and w w both in the fast range of `deposit_units`) deposits without a branch, anything
 else takes the shared per-deposit code.  Whatever path a sweep takes, the limbs are the exact sums and the status word

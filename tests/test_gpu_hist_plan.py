@@ -130,9 +130,10 @@ class _Launch:
     def limbs(self, fill=0):
         return torch.full((self.n_cont, N_BINS, 2, NL), fill, dtype=torch.int64, device="cuda")
 
-    def run(self, planned, limbs, clear_first=True, n_cont=None, cont=None):
-        """status of the call; limbs are written in place, the device status word is in `self.status`"""
-        self.status.zero_()
+    def run(self, planned, limbs, clear_first=True, n_cont=None, cont=None, status=0):
+        """status of the call; limbs are written in place, the device status word (`status` before the call) is in
+        `self.status`"""
+        self.status.fill_(status)
         a = (cont if cont is not None else self.cont, self.n_cont if n_cont is None else n_cont, C.byref(self.grid), None, None,
              self.K._ptr(self.tab), C.byref(self.outb), self.K._ptr(limbs), self.K._ptr(self.status))
         if planned:
@@ -268,6 +269,57 @@ def test_stale_plans_are_refused():
         changed[1].n_events = 256
         assert la.run(True, limbs, cont=changed) == -1
         assert la.run(True, limbs) == 0
+    finally:
+        la.close()
+
+
+def test_planned_call_validates_by_itself():
+    """a binning or calc grid of another size than the plan's, a container without its index column, a flavour that
+    does not exist: refused, with the caller's limbs and status word as they were"""
+    la = _Launch([(4097, "alternating"), (257, "all")])
+    try:
+        L = la.L
+        limbs = la.limbs(fill=5)
+        grid, outb = la.grid, la.outb
+
+        def refused(cont=None):
+            rc = la.run(True, limbs, cont=cont, status=0x40)     # (a bit no kernel sets)
+            return rc == -1 and bool((limbs == 5).all()) and int(la.status.item()) == 0x40   # PISA_HIP_ERR_INVALID
+
+        la.outb = L.make_binning([0.0, -1.0], [1.0, 1.0], [8, 8])      # 64 bins, the plan's binning has 128
+        assert refused()
+        la.outb, la.grid = outb, L.make_binning([0.0, -1.0], [1.0, 1.0], [4, 5])   # 20 nodes, the plan's grid 16
+        assert refused()
+        la.grid = grid
+        stripped = (L.Container * 2)(*la.cont)
+        stripped[1].d_node_bin16 = None
+        assert refused(stripped)
+        flavour = (L.Container * 2)(*la.cont)
+        flavour[0].flav = 3
+        assert refused(flavour)
+        assert la.run(True, limbs) == 0 and np.array_equal(limbs.cpu().numpy(), la.expected())
+    finally:
+        la.close()
+
+
+def test_planned_launch_records_the_profile_events():
+    """`pisa_hip_profile_events`: the planned call records the pair around its launch (bench.py times the sweep with it)"""
+    la = _Launch([(4097, "all"), (257, "alternating")])
+    try:
+        start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        start.record(); stop.record()          # materialise the handles
+        torch.cuda.synchronize()
+        empty = start.elapsed_time(stop)
+        assert empty < 1.0                     # back to back: nothing in between
+        assert la.lib.pisa_hip_profile_events(start.cuda_event, stop.cuda_event) == 0
+        try:
+            assert la.run(True, la.limbs()) == 0
+        finally:
+            assert la.lib.pisa_hip_profile_events(None, None) == 0
+        dt = start.elapsed_time(stop)
+        assert dt > 0.0 and dt != empty        # recorded again, with the launch in between
+        assert la.run(True, la.limbs()) == 0   # disabled: the pair keeps its last recording
+        assert start.elapsed_time(stop) == dt
     finally:
         la.close()
 

@@ -1,6 +1,6 @@
 """The nine map metrics on the device against exact values: `pisa_hip_metric` per bin (`metric_bin` of
 csrc/metric_device.hpp, `metric_bin_wide` of csrc/metric_flux.hip) on every family of tests/metric_cases.py, its totals
-against a host replica of the kernels' own reduction trees, and the fused tails of hist.hip
+against a host replica of the kernels' own reduction trees, and the fused tails of hist_tail.hip
 (`pisa_hip_finalize_metric[_multi|_split|_parts|_scaled]`) on the same inputs, laid out as accumulator limbs.
 
 The gate (tests/metric_cases.py): |got - exact| <= G_kind eps (m + 1) per bin, G_kind = 4 max(1, G_REF_kind), with

@@ -1,7 +1,7 @@
 """The rule of the exact accumulator, pinned where no GPU is needed: a weight x contributes
 sign(x) floor(|x| 2^116) units, and is refused iff it is not finite or |x| >= 2^76.  `engine.float_to_limbs`
 states it, `tests/limb_cases.units` is the fast form the GPU tests use for every event, and
-`limb_cases.kernel_units` is a port of the two shift forms of csrc/hist.hip (`deposit_units`,
+`limb_cases.kernel_units` is a port of the two shift forms of csrc/hist_device.hpp (`deposit_units`,
 `deposit_units_general`) to Python integers with the kernel's word sizes.  All three must agree."""
 import math
 from fractions import Fraction
