@@ -905,6 +905,37 @@ int pisa_hip_fluctuate(const double *d_mu, const double *d_sigma /* NULL: poisso
                        int64_t n_bins, int64_t n_trials, uint64_t seed, uint32_t stream_id, uint32_t first_trial,
                        double *d_out /* [n_trials][n_bins] */, int32_t *d_status, void *stream);
 
+/* Pseudo-data of a LINEARISED template whose nuisance parameters fluctuate (csrc/fluctuate_linear.hip; DESIGN.md
+ * section 4, "pseudo-data with drawn nuisance truths"): every trial draws the truths of J = n_params parameters from
+ * their priors and its data from the template at those truths, on the generator above.
+ *   truth  d_eta_true[t][j]: h_scale[j] == 0 gives h_shift[j] (nothing is drawn, the box is not read); otherwise the
+ *          first of the candidates h_shift[j] + h_scale[j] z_r, r = 0, 1, ..., that lies inside [h_lower[j],
+ *          h_upper[j]], z_r = PPND16(u) of the first double (open interval) of the block with the counter
+ *          (0x80000000 + j, first_trial + t, stream_id, r) -- a bin word is at most 2^31 - 2, so no block of an entry
+ *          has such a counter.  A truncated normal by rejection.  After 256 refused candidates the last one is held
+ *          inside the box and d_status[0] becomes PISA_HIP_FLUCT_TRUTH_EXHAUSTED (a caller that refuses a box with
+ *          less than a quarter of the prior's mass never sees it: 0.75^256).
+ *   mean   mu_t[b] = d_mu[b] + d_response[0][b] eta[t][0] + ... + d_response[J-1][b] eta[t][J-1], ascending j, every
+ *          product and sum rounded: the template of pisa_hip_profiled_metric_matrix at eta.  A NaN d_mu[b] stays NaN;
+ *          a negative mu_t[b] becomes 0 and is counted in d_status[1] (a count modulo 2^32, no error).
+ *   entry  d_out[t][b] is the entry of pisa_hip_fluctuate for the mean mu_t[b]: _POISSON, _GAUSS or _GAUSS_POISSON.
+ *          _SCALED_POISSON is refused (its row rules compare a row's variance with its mean, which moves per trial).
+ * With every scale and shift 0 and no negative d_mu the output is pisa_hip_fluctuate's, bit for bit.  An entry and a
+ * truth depend on (seed, stream_id, first_trial + t, b or j, the inputs) alone.
+ * h_scale, h_shift, h_lower, h_upper: HOST arrays [J]; h_lower / h_upper may be NULL (no bound on that side).
+ * d_response [J][n_bins], d_eta_true [n_trials][J], d_status[2] (int32, zeroed by the caller): [0] the error word of
+ * pisa_hip_fluctuate (_ERR_NEGATIVE takes precedence over _TRUTH_EXHAUSTED), [1] the number of clipped means.
+ * PISA_HIP_ERR_INVALID before any launch: as pisa_hip_fluctuate; n_params outside [1, PISA_HIP_PROFILE_MAX_PARAMS];
+ * a scale that is NaN, negative or infinite, a shift that is not finite, a NaN bound, lower > upper; a NULL pointer
+ * other than h_lower, h_upper and (for _POISSON) d_sigma. */
+#define PISA_HIP_FLUCT_TRUTH_EXHAUSTED 1
+int pisa_hip_fluctuate_linear(const double *d_mu, const double *d_sigma /* NULL: poisson only */,
+                              const double *d_response, int32_t n_params, const double *h_scale,
+                              const double *h_shift, const double *h_lower, const double *h_upper, int32_t method,
+                              int64_t n_bins, int64_t n_trials, uint64_t seed, uint32_t stream_id,
+                              uint32_t first_trial, double *d_out, double *d_eta_true, int32_t *d_status,
+                              void *stream);
+
 /* ----------------------------------------------- binned post-histogram stages */
 
 /* d_out[i] = d_x[i] * d_scale[i] * scalar  (d_scale may be NULL = 1), then, if
@@ -1293,6 +1324,34 @@ int pisa_hip_profiled_metric_matrix_best_bounded(int32_t kind, const double *d_d
                                                  int64_t n_bins, double *d_best, int32_t *d_arg, double *d_at,
                                                  double *d_eta_best, double *d_eta_at, int32_t *d_trial_status,
                                                  int32_t *d_status, void *stream);
+
+/* The covariance of the fitted displacements (csrc/profile_hesse.hip; DESIGN.md section 4, "Profiled trial ensembles:
+ * covariance and pulls"): for trial t, its template k_t = d_k_of_trial[t] (the d_arg of the reduced fit; NULL: k0 for
+ * every trial) and the point d_eta[t] ([n_trials][J]; normally d_eta_best or d_eta_at of that fit), one sweep over the
+ * bins in ascending order forms gradient and Hessian H of Phi at eta exactly as the solver does, prior terms included.
+ *   unbounded (d_lower and d_upper NULL)  d_cov[t] = c H^-1 by the solver's Cholesky factorisation and pivot rule;
+ *       c = 1 for _LLH and _POISSON_LLH (Phi is -ln L), c = 2 for _CHI2 and _MOD_CHI2 (Phi is chi2).
+ *   bounded   eta is held inside the box of template k_t; the coordinates on a bound with the gradient pointing out of
+ *       the box, and the pinned ones, leave the system as in the fit: their rows and columns of d_cov are 0,
+ *       d_trial_status[t] has _HELD, and the free block is inverted.  With every bound infinite: the unbounded bits.
+ *   d_trial_status [n_trials]: 0, _HELD, or a flag with its meaning above and a NaN covariance: _NOT_POSDEF (the
+ *       free block has no Cholesky factor), _START_OUTSIDE (eta is outside the domain: a responding bin with
+ *       mu < 1e-10), _BAD_BOUNDS.
+ *   d_cov [n_trials][J][J], symmetric bit for bit, written in full.
+ * The bits of row t depend on row t of d_data, row k_t of d_expected / d_sigma2 / d_response / d_center / the bounds
+ * and d_eta[t] alone.  d_status[1] (int32, zeroed by the caller): PISA_HIP_ERR_NEGATIVE for a negative datum or
+ * expectation in a row that is read; PISA_HIP_ERR_INVALID for a k_t outside [0, n_templates) (that row is NaN, its
+ * status -1).  PISA_HIP_ERR_INVALID before any device access: as pisa_hip_profiled_metric_matrix_best_bounded where
+ * the arguments are the same ones; k0 is checked where d_k_of_trial is NULL; a NULL d_eta, d_cov or d_trial_status;
+ * more than 2^32 trials' lanes. */
+#define PISA_HIP_PROFILE_HELD 32
+int pisa_hip_profiled_hesse(int32_t kind, const double *d_data, const double *d_expected, const double *d_sigma2,
+                            const double *d_response, int64_t response_stride_k, const double *d_inv_prior_sigma,
+                            const double *d_center, const double *d_lower, const double *d_upper,
+                            int64_t bound_stride_k, int32_t n_params, int64_t n_trials, int64_t n_templates,
+                            int64_t n_bins, const int32_t *d_k_of_trial /* NULL: k0 */, int32_t k0,
+                            const double *d_eta, double *d_cov, int32_t *d_trial_status, int32_t *d_status,
+                            void *stream);
 
 /* ------------------------------------------------------- raw device memory */
 /* Thin wrappers so hosts without torch (a cgo/ctypes binding of the

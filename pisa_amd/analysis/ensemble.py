@@ -59,8 +59,23 @@ and, for a `response` that has bounds, the same two methods with the keywords
     lower=, upper=  ([J] or [K, J] host arrays of displacements, -inf / +inf for no bound)
 which the drivers pass ONLY for such a response: a solver that knows nothing of bounds keeps working with responses
 that have none, and a bounded response on it is refused,
+and, for `generator="device"` with `nuisance="prior"`,
+    draw_linear(mu [B], response [J, B], sigma [B] or None, method, n_trials, seed, stream, scale, shift, lower, upper
+                ([J] host arrays; lower / upper may be None), first_trial=0)
+        -> dict(data [n_trials, B], eta [n_trials, J], clipped)
+and, for `covariance=True` and `pulls`,
+    hesse(kind, data, expected, response, eta [T, J], k (an int or [T] ints), sigma2, inv_prior_sigma, center,
+          lower=, upper=) -> dict(cov [T, J, J], sigma [T, J], status [T])
 so that everything around the kernels can run with a numpy restatement (tests/ensemble_cases.py,
-tests/fluctuate_cases.py, tests/fluctuate_method_cases.py, tests/profile_cases.py).
+tests/fluctuate_cases.py, tests/fluctuate_method_cases.py, tests/profile_cases.py, tests/truth_cases.py,
+tests/hesse_cases.py).
+
+`nuisance="prior"` (`pseudo_data`, `feldman_cousins`; needs `response=`) makes pseudo-experiments with the systematics
+fluctuated: every trial draws the truths of the response's parameters from their priors and its data from the
+linearised template at those truths (csrc/fluctuate_linear.hip; DESIGN.md §4, "pseudo-data with drawn nuisance
+truths"), where the default `nuisance="fixed"` leaves them at the point's values.  `delta_metric(..., covariance=True)`
+returns the covariance of the fitted displacements (csrc/profile_hesse.hip; "covariance and pulls") and `pulls` the
+distribution (eta_hat - eta_true) / sigma_hat an analyst checks a profiled ensemble with.
 """
 import math
 
@@ -70,7 +85,7 @@ from pisa_amd.core.map import FLUCTUATE_METHODS
 from pisa_amd.utils.comparisons import ALLCLOSE_KW
 
 __all__ = ["METRICS", "GENERATORS", "FLUCTUATE_METHODS", "DeviceSolver", "TemplateGrid", "NuisanceResponse", "grid_points", "pseudo_data",
-           "metric_matrix", "delta_metric", "critical_values", "feldman_cousins", "accepted"]
+           "metric_matrix", "delta_metric", "pulls", "critical_values", "feldman_cousins", "accepted", "NUISANCE"]
 
 # kernels.METRIC_KIND, then kernels.ENSEMBLE_MC_KINDS: the metrics that account for finite MC statistics, which read
 # the templates' sumw2 and have no profiled form
@@ -135,6 +150,21 @@ class DeviceSolver:
         return K.profiled_metric_matrix_best(kind, data, expected, response, sigma2, ips, center, offset, int(k0),
                                              max_iter=max_iter, lower=lower, upper=upper)
 
+    def hesse(self, kind, data, expected, response, eta, k, sigma2=None, inv_prior_sigma=None, center=None, lower=None,
+              upper=None):
+        """dict(cov [T, J, J], sigma [T, J], status [T]): the covariance of the displacements eta [T, J] fitted at the
+        template k (one int, or [T] ints: the fit's `arg`) of every trial (`kernels.profiled_hesse`)"""
+        import torch
+
+        from pisa_amd import kernels as K
+
+        data, expected, response, eta, sigma2, ips, center, lower, upper = [self._up(a) for a in (
+            data, expected, response, eta, sigma2, inv_prior_sigma, center, lower, upper)]
+        if not isinstance(k, (int, np.integer)):
+            k = k if isinstance(k, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(k, dtype=np.int32))
+            k = k.to(device=data.device, dtype=torch.int32)
+        return K.profiled_hesse(kind, data, expected, response, eta, k, sigma2, ips, center, lower, upper)
+
     def draw(self, mu, n_trials, seed, stream, first_trial=0):
         """[n_trials, B] Poisson draws of the row `mu` on the device (`kernels.poisson_fluctuate`)"""
         from pisa_amd import kernels as K
@@ -148,6 +178,17 @@ class DeviceSolver:
 
         return K.fluctuate(self._up(mu).reshape(-1), n_trials, seed, method=method, sigma=self._up(sigma).reshape(-1),
                            stream=stream, first_trial=first_trial)
+
+    def draw_linear(self, mu, response, sigma, method, n_trials, seed, stream, scale, shift, lower=None, upper=None,
+                    first_trial=0):
+        """dict(data [n_trials, B], eta [n_trials, J], clipped): every trial's nuisance truths drawn from N(shift,
+        scale) inside [lower, upper] and its data by `method` from mu + sum_j response[j] eta_j on the device
+        (`kernels.fluctuate_linear`); for "poisson" sigma is None"""
+        from pisa_amd import kernels as K
+
+        sigma = None if sigma is None else self._up(sigma).reshape(-1)
+        return K.fluctuate_linear(self._up(mu).reshape(-1), self._up(response), n_trials, seed, scale, shift, lower,
+                                  upper, method=method, sigma=sigma, stream=stream, first_trial=first_trial)
 
 
 def _rescaled(param, value):
@@ -538,7 +579,113 @@ def _device_draw(solver, grid, k, sigma, method, n_trials, seed, first_trial=0):
     return solver.fluctuate(grid.hist[k], sigma, method, n_trials, seed, stream=k, first_trial=first_trial)
 
 
-def pseudo_data(grid, k, n_trials, random_state=None, generator="host", solver=None, method="poisson"):
+NUISANCE = ("fixed", "prior")
+TRUTH_MIN_MASS = 0.25          # the least share of a prior's mass a parameter's box may hold (kernels.TRUTH_MIN_MASS)
+
+
+def _check_nuisance(nuisance, response, grid, solver, generator, method, metric, what):
+    """`nuisance="prior"` needs a response of this grid, a metric with a profiled form, a method whose mean may move
+    per trial and, for the device generator, a solver that draws such data"""
+    if nuisance not in NUISANCE:
+        raise ValueError("ensemble: nuisance '%s' not among %s" % (nuisance, list(NUISANCE)))
+    if generator not in GENERATORS:
+        raise ValueError("ensemble: generator '%s' not among %s" % (generator, list(GENERATORS)))
+    if nuisance == "fixed":
+        return
+    if response is None:
+        raise ValueError("%s: nuisance='prior' needs response=, the linear response whose parameters are drawn" % what)
+    if metric in _MC_METRICS:
+        raise ValueError("%s: nuisance='prior' is not available for '%s' (response= has no form for the "
+                         "MC-uncertainty metrics)" % (what, metric))
+    if method == "scaled_poisson":
+        raise ValueError("%s: nuisance='prior' has no scaled_poisson draws (the method's row rules compare a row's "
+                         "variance with its mean, which moves per trial)" % what)
+    if generator == "device" and not hasattr(solver, "draw_linear"):
+        raise ValueError("ensemble: generator='device' with nuisance='prior' needs a solver with draw_linear(mu, "
+                         "response, sigma, method, n_trials, seed, stream, scale, shift, lower, upper, first_trial); "
+                         "%s has none" % type(solver).__name__)
+    shape = tuple(response.response.shape)
+    if shape[-1] != grid.n_bins or (len(shape) == 3 and shape[0] != len(grid)):
+        raise ValueError("%s: the response does not belong to this grid (%s against %d points, %d bins)"
+                         % (what, shape, len(grid), grid.n_bins))
+
+
+def _truth_priors(response, k):
+    """what the truths of point k are drawn from -> (R [J, B] as the response holds it, scale, shift, lower, upper
+    [J] host arrays): a parameter with a Gaussian prior has scale = its stddev = 1 / inv_prior_sigma and shift =
+    -center[k] = prior mean - the parameter's value at the point, so that value + eta ~ N(prior mean, stddev); one
+    without keeps scale 0 and shift 0 (it stays at the point's value); the box is the response's at k (None: none)"""
+    R = response.response[k] if len(response.response.shape) == 3 else response.response
+    ips = np.asarray(response.inv_prior_sigma, dtype=np.float64)
+    has = ips > 0
+    scale = np.where(has, 1.0 / np.where(has, ips, 1.0), 0.0)
+    center = np.zeros(ips.size) if response.center is None else np.asarray(response.center, dtype=np.float64)[k]
+    shift = np.where(has, -center, 0.0)
+    box = [None if b is None else np.ascontiguousarray(b[k] if b.ndim == 2 else b) for b in (response.lower,
+                                                                                             response.upper)]
+    return R, scale, shift, box[0], box[1]
+
+
+def _host_truths(scale, shift, lower, upper, rs):
+    """one trial's truths on the stream `rs`: for j ascending, shift_j where scale_j is 0 (nothing is drawn), else
+    shift_j + scale_j rs.standard_normal() again and again until the candidate is inside [lower_j, upper_j]"""
+    eta = np.array(shift, dtype=np.float64)
+    for j in np.nonzero(scale > 0)[0]:
+        lo = -np.inf if lower is None else lower[j]
+        hi = np.inf if upper is None else upper[j]
+        while True:
+            x = shift[j] + scale[j] * rs.standard_normal()
+            if lo <= x <= hi:
+                break
+        eta[j] = x
+    return eta
+
+
+def _linear_mean(mu0, R, eta):
+    """mu0 + R[0] eta_0 + ... in ascending j, every step rounded (the template the profiled fit works with); a
+    negative mean becomes 0, a NaN stays"""
+    mu = np.array(mu0, dtype=np.float64)
+    for j in range(R.shape[0]):
+        mu = mu + R[j] * eta[j]
+    with np.errstate(invalid="ignore"):
+        return np.where(mu < 0.0, 0.0, mu)
+
+
+def _prior_data(grid, k, n_trials, seed_or_rs, generator, solver, method, response, first_trial=0):
+    """(data [n_trials, B], eta_true [n_trials, J]) of `nuisance="prior"` at point k: module docstring"""
+    R, scale, shift, lower, upper = _truth_priors(response, k)
+    sigma = _sigma_row(grid, k, method)
+    if generator != "host":
+        out = solver.draw_linear(grid.hist[k], R, sigma, method, n_trials, seed_or_rs, stream=k, scale=scale,
+                                 shift=shift, lower=lower, upper=upper, first_trial=first_trial)
+        return out["data"], out["eta"]
+    from scipy.stats import norm, poisson
+
+    for j in np.nonzero(scale > 0)[0]:                 # the device generator's rule, so that both refuse alike
+        lo, hi = (-np.inf if lower is None else lower[j]), (np.inf if upper is None else upper[j])
+        mass = norm.cdf((hi - shift[j]) / scale[j]) - norm.cdf((lo - shift[j]) / scale[j])
+        if mass < TRUTH_MIN_MASS:
+            raise ValueError("pseudo_data: the box [%g, %g] of '%s' holds %.3g of the mass of its prior; at least %g "
+                             "is needed" % (lo, hi, response.names[j], mass, TRUTH_MIN_MASS))
+    rs = seed_or_rs
+    mu0 = np.asarray(grid.host("hist")[k], dtype=np.float64).ravel()
+    R = _host(R).astype(np.float64)
+    data, truth = np.empty((max(n_trials, 0), mu0.size)), np.empty((max(n_trials, 0), scale.size))
+    for t in range(data.shape[0]):
+        truth[t] = _host_truths(scale, shift, lower, upper, rs)
+        mu = _linear_mean(mu0, R, truth[t])
+        if method != "poisson":
+            data[t] = _host_fluctuate(mu, sigma, method, rs)
+            continue
+        ok = ~np.isnan(mu)
+        data[t] = np.nan
+        if ok.any():
+            data[t, ok] = poisson.rvs(mu[ok], random_state=rs)
+    return data, truth
+
+
+def pseudo_data(grid, k, n_trials, random_state=None, generator="host", solver=None, method="poisson", response=None,
+                nuisance="fixed", return_truth=False):
     """[n_trials, B] pseudo-data of template k by `method` (one of `FLUCTUATE_METHODS`; every method but "poisson"
     reads sigma = sqrt(grid.sumw2[k]), and "scaled_poisson" applies the reference's row rules to it first: module
     docstring).  With another method than "poisson" the host generator is the loop of `Map.fluctuate(method,
@@ -550,8 +697,33 @@ def pseudo_data(grid, k, n_trials, random_state=None, generator="host", solver=N
     generator="device": what `solver.draw(grid.hist[k], n_trials, seed, stream=k)` returns (from `DeviceSolver`, the
     default, a device tensor: `kernels.poisson_fluctuate`), seed = `random_state` or one draw from it if it is a
     RandomState, as in `feldman_cousins`.  A counter-based generator of its own definition, NOT the reference's
-    stream; NaN bins stay NaN and a zero bin stays 0 here as well."""
+    stream; NaN bins stay NaN and a zero bin stays 0 here as well.
+    nuisance="prior" (with `response`, a `NuisanceResponse` of this grid): the parameters of the response do not sit
+    at the point's values when the data are made; every trial draws their truths eta from their priors -- N(prior
+    mean, stddev) for a parameter with a Gaussian prior, truncated to the response's box if it has one; a parameter
+    without a prior stays at the point's value -- and its data by `method` ("scaled_poisson" is refused) from the
+    linearised template hist[k] + sum_j response[k, j] eta_j, a negative mean taken as 0 ("pseudo-data
+    with drawn nuisance truths").  generator="device": `solver.draw_linear` (`kernels.fluctuate_linear`);
+    generator="host": per trial, for j ascending, shift_j + scale_j rs.standard_normal() until the candidate is inside
+    the box, then the method's own scipy calls on that trial's mean, all on the one RandomState.  nuisance="fixed"
+    (the default) is the call without the argument.  return_truth=True returns (data, eta_true [n_trials, J]: the
+    displacements from the point's values the fit's eta estimates; None for "fixed")."""
     method = _check_method(method, grid)
+    if nuisance != "fixed":
+        solver_ = (DeviceSolver() if solver is None else solver) if generator != "host" else solver
+        _check_nuisance(nuisance, response, grid, solver_, generator, method, grid.metric, "pseudo_data")
+    if nuisance == "prior":
+        if not 0 <= int(k) < len(grid):
+            raise ValueError("pseudo_data: point %s outside the grid's %d points" % (k, len(grid)))
+        if generator == "host":
+            source = random_state if isinstance(random_state, np.random.RandomState) else np.random.RandomState(
+                random_state)
+        else:
+            source = _base_seed(random_state)
+        data, truth = _prior_data(grid, int(k), int(n_trials), source, generator, solver_, method, response)
+        return (data, truth) if return_truth else data
+    if return_truth:
+        return pseudo_data(grid, k, n_trials, random_state, generator, solver, method), None
     if generator != "host":
         solver = DeviceSolver() if solver is None else solver
         _check_generator(generator, solver, method)
@@ -614,14 +786,20 @@ def metric_matrix(data, grid, metric, with_penalty=True, solver=None, response=N
     return m
 
 
-def delta_metric(data, grid, metric, k0, solver=None, response=None, return_info=False):
+def delta_metric(data, grid, metric, k0, solver=None, response=None, return_info=False, covariance=False):
     """[T] host array: per data row the distance of point k0 from the best point of the grid, penalties included --
     best - at for the llh metrics, at - best for the chi2 metrics (>= 0; no factor of 2 is applied).  The T x K
     matrix is never written (`pisa_hip_metric_matrix_best`).  With `response` both values are profiled over the
     response's parameters (`pisa_hip_profiled_metric_matrix_best`); `return_info=True` then returns (delta, info) with
     info = dict(flagged: the number of trials whose pair at the best point or at k0 carries a status flag, status
-    [T], arg [T], eta_best and eta_at [T, J]: the fitted displacements at both points)."""
+    [T], arg [T], eta_best and eta_at [T, J]: the fitted displacements at both points).  `covariance=True` (with
+    `return_info`; needs a solver with `hesse`) adds cov_best and cov_at [T, J, J], the covariance of the displacements
+    at both points -- the inverse Hessian of -ln L there with the prior terms, a coordinate the fit holds on a bound
+    having zero rows and columns ("Profiled trial ensembles: covariance and pulls") --, sigma_best and
+    sigma_at [T, J] = sqrt of their diagonals, and hesse_status [T]: the flags of both calls ORed."""
     _check_metric(metric)
+    if covariance and not (return_info and response is not None):
+        raise ValueError("delta_metric: covariance=True belongs to response= and return_info=True")
     if not 0 <= int(k0) < len(grid):
         raise ValueError("delta_metric: k0 = %s outside the grid's %d points" % (k0, len(grid)))
     solver = DeviceSolver() if solver is None else solver
@@ -633,6 +811,8 @@ def delta_metric(data, grid, metric, k0, solver=None, response=None, return_info
         best, at = _host(best), _host(at)
         return best - at if metric in _MAXIMISED else at - best
     _check_response(response, grid, solver, "delta_metric", metric)
+    if covariance:
+        _check_hesse(solver)
     out = solver.profiled_best(metric, _data_rows(data), grid.hist, response.response, grid.sigma2_for(metric),
                                response.inv_prior_sigma, response.center, response.offset(grid), int(k0),
                                response.max_iter, **response.bounds())
@@ -641,8 +821,44 @@ def delta_metric(data, grid, metric, k0, solver=None, response=None, return_info
     if not return_info:
         return delta
     status = _host(out["status"])
-    return delta, dict(flagged=int(np.count_nonzero(status)), status=status, arg=_host(out["arg"]),
-                       eta_best=_host(out["eta_best"]), eta_at=_host(out["eta_at"]))
+    info = dict(flagged=int(np.count_nonzero(status)), status=status, arg=_host(out["arg"]),
+                eta_best=_host(out["eta_best"]), eta_at=_host(out["eta_at"]))
+    if covariance:
+        hesse_status = 0
+        for which, k in (("best", out["arg"]), ("at", int(k0))):
+            h = solver.hesse(metric, _data_rows(data), grid.hist, response.response, out["eta_" + which], k,
+                             grid.sigma2_for(metric), response.inv_prior_sigma, response.center, **response.bounds())
+            info["cov_" + which], info["sigma_" + which] = _host(h["cov"]), _host(h["sigma"])
+            hesse_status = hesse_status | _host(h["status"])
+        info["hesse_status"] = hesse_status
+    return delta, info
+
+
+def _check_hesse(solver):
+    if not hasattr(solver, "hesse"):
+        raise ValueError("ensemble: covariances and pulls need a solver with hesse(kind, data, expected, response, eta, "
+                         "k, sigma2, inv_prior_sigma, center, lower=, upper=); %s has none" % type(solver).__name__)
+
+
+def pulls(data, grid, metric, k0, response, truth, solver=None):
+    """[T, J] host array: the pulls (eta_at - truth) / sigma_at of the displacements fitted at point k0 to every data
+    row -- `truth` [T, J] the displacements the rows were drawn at (`pseudo_data(..., nuisance="prior",
+    return_truth=True)`; zeros for nuisance="fixed"), sigma_at from `delta_metric(..., covariance=True)`.  For an
+    ensemble drawn and fitted with the same linear response they are standard normal where the priors are Gaussian
+    and the counts large: the closure check of a profiled ensemble.  NaN where sigma is 0 (a coordinate held on a
+    bound) or NaN (a flagged fit)."""
+    solver = DeviceSolver() if solver is None else solver
+    _check_hesse(solver)
+    rows = _data_rows(data)
+    truth = _host(truth)
+    n_j = len(response.names)
+    if truth.shape != (int(rows.shape[0]), n_j):
+        raise ValueError("pulls: truth holds one displacement per data row and parameter [%d, %d], got %s"
+                         % (int(rows.shape[0]), n_j, truth.shape))
+    _, info = delta_metric(rows, grid, metric, k0, solver, response, return_info=True, covariance=True)
+    sigma = info["sigma_at"]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return np.where(sigma > 0, (info["eta_at"] - truth) / sigma, np.nan)
 
 
 def critical_values(delta, cl):
@@ -671,7 +887,8 @@ def _base_seed(random_state):
 
 
 def feldman_cousins(grid, metric, n_trials, cl=(0.6827, 0.90), random_state=None, true_points=None, solver=None,
-                    generator="host", chunk_bytes=CHUNK_BYTES, response=None, method="poisson"):
+                    generator="host", chunk_bytes=CHUNK_BYTES, response=None, method="poisson",
+                    nuisance="fixed"):
     """Critical values of the Feldman-Cousins ordering on the grid: for every true point k0 (default: all), n_trials
     pseudo-data maps of template k0, their `delta_metric` at k0 and `critical_values` -> crit [len(true_points),
     len(cl)].  seed: `random_state`, or one draw from it if it is a RandomState.
@@ -684,13 +901,17 @@ def feldman_cousins(grid, metric, n_trials, cl=(0.6827, 0.90), random_state=None
     as far as they are dimensions of the grid (module docstring).  With `response` (a `NuisanceResponse`) every
     distance is profiled over the response's parameters and the return value is (crit, info), info = dict(flagged
     [len(true_points)]: per true point the number of trials whose pair at the best point or at the true point carries
-    a status flag of the fit)."""
+    a status flag of the fit).  nuisance="prior" (needs `response`): the pseudo-data of every true point are those of
+    `pseudo_data(..., response=response, nuisance="prior")` -- the response's parameters drawn from their priors trial
+    by trial --, the device generator drawing them in the same chunks through the solver's `draw_linear`."""
     _check_metric(metric)
     if n_trials < 1:
         raise ValueError("feldman_cousins: n_trials >= 1")
     solver = DeviceSolver() if solver is None else solver
     method = _check_method(method, grid)
-    _check_generator(generator, solver, method)
+    _check_nuisance(nuisance, response, grid, solver, generator, method, metric, "feldman_cousins")
+    if nuisance == "fixed":
+        _check_generator(generator, solver, method)
     if response is not None:
         _check_response(response, grid, solver, "feldman_cousins", metric)
     seed = _base_seed(random_state)
@@ -712,7 +933,15 @@ def feldman_cousins(grid, metric, n_trials, cl=(0.6827, 0.90), random_state=None
     rows = max(1, int(chunk_bytes) // (8 * grid.n_bins))
     for i, k0 in enumerate(points):
         flagged.append(0)
-        if generator == "host":
+        if nuisance == "prior":
+            parts = []
+            source = np.random.RandomState([seed, k0]) if generator == "host" else seed
+            for first in range(0, n_trials, n_trials if generator == "host" else rows):
+                n = n_trials if generator == "host" else min(rows, n_trials - first)
+                parts.append(distances(_prior_data(grid, k0, n, source, generator, solver, method, response, first)[0],
+                                       k0))
+            delta = np.concatenate(parts)
+        elif generator == "host":
             data = pseudo_data(grid, k0, n_trials, np.random.RandomState([seed, k0]), method=method)
             delta = distances(data, k0)
         else:

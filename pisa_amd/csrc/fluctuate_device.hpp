@@ -195,4 +195,41 @@ PISA_FL_HD double fl_fluctuate(int method, double mu, double sigma, uint32_t b, 
     return method == FL_GAUSS ? g : fl_draw(g, b, trial, stream, k0, k1, bad);
 }
 
+// ---- pseudo-data of a linearised template with drawn nuisance truths (fluctuate_linear.hip) ----
+constexpr uint32_t FL_TRUTH_WORD = 0x80000000u;   // the first counter word of parameter j's blocks is FL_TRUTH_WORD + j
+constexpr int FL_TRUTH_ATTEMPTS = 256;            // candidates of one truth before the last one is clamped
+
+// The truth of parameter j in trial number `trial`: shift where scale == 0 (nothing is drawn, the box is not read);
+// otherwise the first candidate shift + scale z_r, r = 0, 1, ..., inside [lower, upper], z_r the normal deviate of
+// the block (FL_TRUTH_WORD + j, trial, stream, r) -- a normal truncated to the box by rejection.  A bin word is at
+// most 2^31 - 2, so no block of an entry's draws (Poisson or Gaussian) has this counter.  After FL_TRUTH_ATTEMPTS
+// refused candidates the last one is held inside the box by comparisons and `exhausted` is set.
+PISA_FL_HD double fl_truth(uint32_t j, uint32_t trial, uint32_t stream, uint32_t k0, uint32_t k1, double scale,
+                           double shift, double lower, double upper, bool &exhausted) {
+    if (scale == 0.0) return shift;
+    double x = shift;
+    for (uint32_t r = 0; r < (uint32_t)FL_TRUTH_ATTEMPTS; r++) {
+        const FlWords w = fl_philox(FL_TRUTH_WORD + j, trial, stream, r, k0, k1);
+        const double sz = scale * fl_normal_quantile(fl_unit_open(w.w[0], w.w[1]));
+        x = shift + sz;
+        if (x >= lower && x <= upper) return x;
+    }
+    exhausted = true;
+    return x < lower ? lower : (x > upper ? upper : x);
+}
+
+// The mean of bin b at the truths: mu0 + r[0] eta_0 + ... + r[J - 1] eta_(J-1) in ascending j, every product and sum
+// rounded -- the expression of pf_mu (profile_device.hpp) --, r[j * stride] the response of parameter j in this bin.
+// A NaN stays NaN; a negative mean becomes 0 and `clipped` is set.
+PISA_FL_HD double fl_linear_mean(double mu0, const double *r, int64_t stride, const double *eta, int n_params,
+                                 bool &clipped) {
+    double mu = mu0;
+    for (int j = 0; j < n_params; j++) {
+        const double t = r[j * stride] * eta[j];
+        mu = mu + t;
+    }
+    clipped = mu < 0.0;
+    return clipped ? 0.0 : mu;
+}
+
 }  // namespace pisa

@@ -384,6 +384,102 @@ PISA_PF_HD int32_t pf_status(const PfState<J> &st) {
     return st.status | (st.boundary ? PF_BOUNDARY : 0);
 }
 
+// ------------------------------------------------------------------ the covariance of the displacements at eta
+// (profile_hesse.hip; DESIGN.md §4, "Profiled trial ensembles: covariance and pulls"; restated in tests/hesse_cases.py)
+constexpr int PF_HELD = 32;                // PISA_HIP_PROFILE_HELD: a coordinate of the bound set has zero rows and columns
+
+// the bound set `pf_bind` takes out of the system, as a mask (bit j: coordinate j), from the same marks and gradient
+template <int J>
+PISA_PF_HD uint32_t pf_bound_set(const PfState<J> &st) {
+    const uint32_t on = st.on_bound;
+    uint32_t bound = 0;
+#pragma unroll
+    for (int j = 0; j < J; j++) {
+        const double gj = st.g[j];
+        const bool at_lo = on >> j & 1u, at_hi = on >> (8 + j) & 1u;
+        if ((at_lo && at_hi) || (at_lo && gj > 0.0) || (at_hi && gj < 0.0)) bound |= 1u << j;
+    }
+    return bound;
+}
+
+// inv (packed lower triangle) = (L L^T)^-1 from the factor L of `pf_factor`: column k is the solution of
+// L L^T x = e_k by forward and back substitution, of which the entries i >= k are kept (the forward solution is 0
+// above k, and the back substitution of entry i reads the entries below it alone).
+template <int J>
+PISA_PF_HD void pf_inverse(const double *L, double *inv) {
+#pragma unroll
+    for (int k = 0; k < J; k++) {
+        double z[J];
+#pragma unroll
+        for (int i = k; i < J; i++) {
+            double v = i == k ? 1.0 : 0.0;
+#pragma unroll
+            for (int m = k; m < i; m++) v -= L[pf_at(i, m)] * z[m];
+            z[i] = v / L[pf_at(i, i)];
+        }
+#pragma unroll
+        for (int i = J - 1; i >= k; i--) {
+            double v = z[i];
+#pragma unroll
+            for (int m = i + 1; m < J; m++) v -= L[pf_at(m, i)] * z[m];
+            z[i] = v / L[pf_at(i, i)];
+            inv[pf_at(i, k)] = z[i];
+        }
+    }
+}
+
+// Before the one sweep of `pf_bin`: the point eta becomes the sweep's point, held inside the box where there is one
+// (`boxed`; lo and hi are not read otherwise; a point of the domain inside its box is not moved, and its coordinates
+// on a bound are marked).  False, and nothing else, for a box with a bound that does not satisfy lo <= hi:
+// PF_BAD_BOUNDS.
+template <int J>
+PISA_PF_HD bool pf_hesse_begin(PfState<J> &st, const double *eta, const double *lo, const double *hi, bool boxed) {
+    pf_init<J>(st);
+#pragma unroll
+    for (int j = 0; j < J; j++) st.eta_t[j] = eta[j];
+    if (boxed) {
+        bool ok = true;
+#pragma unroll
+        for (int j = 0; j < J; j++)
+            if (!(lo[j] <= hi[j])) ok = false;
+        if (!ok) return false;
+        pf_hold<J>(st, st.eta_t, lo, hi);
+    }
+    pf_sweep_begin<J>(st);
+    return true;
+}
+
+// After the sweep: the prior terms join gradient and Hessian as in `pf_decide_any`, the bound set leaves the system
+// (`pf_bind`), the free block is factored (`pf_factor`, its pivot rule) and inverted, and
+//     cov = c H^-1,  c = 1 for the llh kinds (Phi is -ln L), c = 2 for the chi2 kinds (Phi is chi2 = -2 ln L + const)
+// goes to `cov` (packed lower triangle) with zero rows and columns for the bound set.  Returns the status bits:
+// PF_START_OUTSIDE (eta is outside the domain: a responding bin with mu < 1e-10), PF_NOT_POSDEF -- `cov` is not
+// written then --, or PF_HELD where the bound set is not empty, else 0.
+template <int KIND, int J>
+PISA_PF_HD int32_t pf_hesse_end(PfState<J> &st, const double *ips, const double *c, double *cov) {
+    constexpr double w = PfKind<KIND>::w;
+#pragma unroll
+    for (int j = 0; j < J; j++) {
+        const double p = ips[j] * (st.eta_t[j] + c[j]);
+        st.g[j] += (2.0 * w) * (ips[j] * p);
+        st.H[pf_at(j, j)] += (2.0 * w) * (ips[j] * ips[j]);
+    }
+    if (!st.inside) return PF_START_OUTSIDE;
+    const uint32_t held = pf_bound_set<J>(st);
+    pf_bind<J>(st);
+    if (!pf_factor<J>(st.H)) return PF_NOT_POSDEF;
+    pf_inverse<J>(st.H, cov);
+#pragma unroll
+    for (int i = 0; i < J; i++) {
+#pragma unroll
+        for (int j = 0; j <= i; j++) {
+            const double v = PfKind<KIND>::is_llh ? cov[pf_at(i, j)] : 2.0 * cov[pf_at(i, j)];
+            cov[pf_at(i, j)] = ((held >> i | held >> j) & 1u) ? 0.0 : v;
+        }
+    }
+    return held ? PF_HELD : 0;
+}
+
 // ----------------------------------------------------------------------------------- the reported metric at eta
 struct PfValue {
     double sum, comp;

@@ -787,6 +787,72 @@ def fluctuate(mu, n_trials, seed, method="poisson", sigma=None, stream=0, first_
     return out
 
 
+TRUTH_MIN_MASS = 0.25        # the least share of a prior's mass a parameter's box may hold (`fluctuate_linear`)
+
+
+def _truth_args(what, n_j, scale, shift, lower, upper):
+    """the parameters' numbers of `fluctuate_linear` as contiguous float64 host arrays [J] (lower / upper: -inf / +inf
+    where None).  A box that holds less than TRUTH_MIN_MASS of its prior's mass raises ValueError: the rejection
+    loop of the truth draw then ends within its 256 candidates (0.75^256).  A NaN, a negative scale or lower > upper
+    goes on to the library, which refuses it."""
+    from scipy.stats import norm
+
+    arrays = []
+    for name, a, fill in (("scale", scale, None), ("shift", shift, None), ("lower", lower, -np.inf),
+                          ("upper", upper, np.inf)):
+        a = np.full(n_j, fill) if a is None and fill is not None else np.ascontiguousarray(a, dtype=np.float64)
+        if a.shape != (n_j,):
+            raise ValueError("%s: %s holds one number per parameter [%d]" % (what, name, n_j))
+        arrays.append(a)
+    scale, shift, lower, upper = arrays
+    with np.errstate(all="ignore"):
+        drawn = (scale > 0) & np.isfinite(scale) & np.isfinite(shift) & (lower <= upper)
+        s = np.where(drawn, scale, 1.0)
+        mass = norm.cdf((upper - shift) / s) - norm.cdf((lower - shift) / s)
+    for j in np.nonzero(drawn & (mass < TRUTH_MIN_MASS))[0]:
+        raise ValueError("%s: the box [%g, %g] of parameter %d holds %.3g of the mass of its prior N(%g, %g); at least "
+                         "%g is needed" % (what, lower[j], upper[j], j, mass[j], shift[j], scale[j], TRUTH_MIN_MASS))
+    return arrays
+
+
+def fluctuate_linear(mu, response, n_trials, seed, scale, shift, lower=None, upper=None, method="poisson", sigma=None,
+                     stream=0, first_trial=0):
+    """Pseudo-data of a linearised template whose nuisance parameters fluctuate (`pisa_hip_fluctuate_linear`,
+    DESIGN.md §4): mu [B], response [J, B] and (for "gauss" and "gauss+poisson") sigma [B] float64 device tensors;
+    scale, shift, lower, upper [J] host numbers.  Trial t draws the truth of parameter j from N(shift_j, scale_j)
+    truncated to [lower_j, upper_j] (scale_j == 0: shift_j itself; None: no bound on that side) and its data by
+    `method` from mu + sum_j response[j] eta_j, a negative mean taken as 0.  -> dict(data [n_trials, B], eta
+    [n_trials, J]: device tensors; clipped: the number of means that were negative).  With every scale and shift 0 the
+    data are `fluctuate`'s, bit for bit.  Entries and truths depend on (seed, stream, first_trial + t, b or j, the
+    inputs) alone.  "scaled_poisson" is refused (ValueError), and so is a box that holds less than `TRUTH_MIN_MASS` of
+    its prior's mass; errors of the draws are those of `fluctuate`."""
+    name = fluctuate_method(method)
+    if name == "scaled_poisson":
+        raise ValueError("fluctuate_linear: no scaled_poisson draws from a mean that moves per trial (its row rules "
+                         "compare a row's variance with its mean)")
+    if response.dim() != 2 or response.dtype != F8 or mu.dim() != 1 or response.shape[1] != mu.shape[0] or (
+            response.device != mu.device):
+        raise ValueError("fluctuate_linear: response is float64 [n_params, n_bins] on mu's device")
+    n_j = response.shape[0]
+    if not 1 <= n_j <= _lib.PROFILE_MAX_PARAMS:
+        raise ValueError("fluctuate_linear: %d nuisance parameters, 1 to %d are drawn" % (n_j, _lib.PROFILE_MAX_PARAMS))
+    mu, sigma, n_bins, n_trials, seed, stream, first_trial, out = _draw_args(
+        "fluctuate_linear", mu, sigma, name, n_trials, seed, stream, first_trial, None)
+    scale, shift, lower, upper = _truth_args("fluctuate_linear", n_j, scale, shift, lower, upper)
+    response = response.contiguous()
+    eta = torch.empty((out.shape[0], n_j), dtype=F8, device=mu.device)
+    status = torch.zeros(2, dtype=torch.int32, device=mu.device)
+    _lib.check(_lib.lib().pisa_hip_fluctuate_linear(
+        _ptr(mu), _ptr(sigma), _ptr(response), n_j, scale.ctypes.data, shift.ctypes.data, lower.ctypes.data,
+        upper.ctypes.data, FLUCTUATE_METHOD[name], n_bins, n_trials, seed, stream, first_trial, _ptr(out), _ptr(eta),
+        _ptr(status), _stream()))
+    word, clipped = (int(x) for x in status.cpu().numpy())
+    if word == _lib.FLUCT_TRUTH_EXHAUSTED:
+        raise ValueError("fluctuate_linear: a truth found no candidate inside its box")
+    _lib.check(word)
+    return dict(data=out, eta=eta, clipped=clipped & 0xFFFFFFFF)
+
+
 def _profile_args(what, kind, data, expected, response, sigma2, inv_prior_sigma, center, max_iter):
     if kind in ENSEMBLE_MC_KINDS:
         raise ValueError("%s: '%s' has no profiled form (its per-bin function is not convex in the response)"
@@ -908,6 +974,48 @@ def profiled_metric_matrix_best(kind, data, expected, response, sigma2=None, inv
 
     _with_status(status, dev, launch)
     return dict(best=best, arg=arg, at=at, eta_best=eta_best, eta_at=eta_at, status=trial_status)
+
+
+def profiled_hesse(kind, data, expected, response, eta, k, sigma2=None, inv_prior_sigma=None, center=None, lower=None,
+                   upper=None):
+    """The covariance of the fitted displacements of `profiled_metric_matrix_best` (`pisa_hip_profiled_hesse`,
+    DESIGN.md §4): eta [T, J] float64 device tensor (normally `eta_best` or `eta_at` of that call) and k, the template
+    of every trial: an int32 device tensor [T] (normally `arg`) or one int for all.  The other arguments are the
+    fit's.  -> dict(cov [T, J, J]: the inverse Hessian of -ln L at eta, the prior terms included (for the chi2 kinds
+    2 / the Hessian of chi2), symmetric bit for bit; sigma [T, J] = sqrt(diag cov); status [T] int32).  With lower /
+    upper the coordinates the fit holds on a bound have zero rows and columns (sigma 0) and the trial
+    `_lib.PROFILE_HELD`; a trial flagged NOT_POSDEF, START_OUTSIDE or BAD_BOUNDS has a NaN covariance.  A negative datum
+    or expectation raises ValueError, a k outside the templates `_lib.PisaHipError`."""
+    (data, expected, response, sigma2, ips, center, stride, n_t, n_k, n_bins, n_j) = _profile_args(
+        "profiled_hesse", kind, data, expected, response, sigma2, inv_prior_sigma, center, 0)
+    b_stride = 0
+    if lower is not None or upper is not None:
+        lower, upper, b_stride = _bound_args("profiled_hesse", lower, upper, n_k, n_j)
+    if eta.dtype != F8 or tuple(eta.shape) != (n_t, n_j):
+        raise ValueError("profiled_hesse: eta is float64 [n_trials, n_params]")
+    eta = eta.contiguous()
+    k_of_trial, k0 = None, 0
+    if isinstance(k, torch.Tensor):
+        if k.dtype != torch.int32 or tuple(k.shape) != (n_t,) or k.device != data.device:
+            raise ValueError("profiled_hesse: k is one int, or an int32 tensor [n_trials] on the data's device")
+        k_of_trial = k.contiguous()
+    else:
+        k0 = int(k)
+        if not 0 <= k0 < n_k:
+            raise ValueError("profiled_hesse: k = %d outside the %d templates" % (k0, n_k))
+    dev = data.device
+    cov = torch.empty((n_t, n_j, n_j), dtype=F8, device=dev)
+    trial_status = torch.empty(n_t, dtype=torch.int32, device=dev)
+
+    def launch(status):
+        _lib.check(_lib.lib().pisa_hip_profiled_hesse(
+            METRIC_KIND[kind], _ptr(data), _ptr(expected), _ptr(sigma2), _ptr(response), stride, _ptr(ips),
+            _ptr(center), _ptr(lower), _ptr(upper), b_stride, n_j, n_t, n_k, n_bins, _ptr(k_of_trial), k0, _ptr(eta),
+            _ptr(cov), _ptr(trial_status), _ptr(status), _stream()))
+
+    _with_status(None, dev, launch)
+    sigma = bin_sqrt(torch.diagonal(cov, dim1=1, dim2=2).contiguous())
+    return dict(cov=cov, sigma=sigma, status=trial_status)
 
 
 # --------------------------------------------------- generalized Poisson-gamma likelihood

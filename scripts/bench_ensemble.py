@@ -21,8 +21,13 @@
     launch + the pair kernel), and in the same run the only way there was before: a loop of `kernels.metric` over the
     pairs of a 64 x 16 sub-block (wall time, synchronised at its end), scaled to the full size by T K / 1024.
 
+  * `--truth` (alone: nothing else runs): the pseudo-data with drawn nuisance truths and the covariance of the fitted
+    displacements at (T, K, B, J) = (1e4, 1e2, 128, 8), median of 5 launches, HIP events: `pisa_hip_fluctuate_linear`
+    (its two launches, the status not read) against `kernels.fluctuate` of the same run, poisson and gauss+poisson;
+    `kernels.profiled_hesse` at the fitted eta_best / arg against `kernels.profiled_metric_matrix_best`, llh and chi2.
+
     python scripts/bench_ensemble.py [--reps 20] [--skip-e2e] [--skip-kernels] [--skip-draw] [--forms direct,product]
-                                     [--true-points N] [--generator host|device|both] [--e2e-reps 3] [--mc]
+                                     [--true-points N] [--generator host|device|both] [--e2e-reps 3] [--mc] [--truth]
                                      [--metric llh] [--method poisson]
 """
 import argparse
@@ -173,6 +178,60 @@ def profiled_lines(n_params, reps, bounded=None):
                                       ms_per_sweep_unbounded=round(res["ms_median"] / sweeps, 3))), flush=True)
         assert int(status.item()) == 0
         del d, e, r
+
+
+def truth_lines(reps=5):
+    """one line per method for `fluctuate_linear` against `fluctuate`, one per kind for `profiled_hesse` against
+    `profiled_metric_matrix_best`, at (T, K, B, J) = (1e4, 1e2, 128, 8); the inputs of `profiled_lines`"""
+    import torch
+
+    from pisa_amd import _lib
+    from pisa_amd import kernels as K
+
+    dev = K.device()
+    n_t, n_k, n_b, J = 10 ** 4, 10 ** 2, 128, 8
+    e_host = _templates(n_k, n_b)
+    rs = np.random.RandomState(1)
+    x = (np.arange(n_b) + 0.5) / n_b
+    r_host = 0.05 * np.cos((np.arange(J)[:, None] + 1) * np.pi * x[None, :])[None] * e_host[:, None, :]
+    e, r = torch.from_numpy(e_host).to(dev), torch.from_numpy(r_host).to(dev)
+    k0 = n_k // 2
+    mu, sigma, resp = e[k0].contiguous(), torch.sqrt(0.3 * e[k0]).contiguous(), r[k0].contiguous()
+    scale, shift = np.full(J, 0.5), np.zeros(J)
+    lower, upper = np.full(J, -1.5), np.full(J, 1.5)
+    out = torch.empty((n_t, n_b), dtype=torch.float64, device=dev)
+    eta = torch.empty((n_t, J), dtype=torch.float64, device=dev)
+    status = torch.zeros(2, dtype=torch.int32, device=dev)
+    lib = _lib.lib()
+    for method in ("poisson", "gauss+poisson"):
+        sg = None if method == "poisson" else sigma
+        code = K.FLUCTUATE_METHOD[method]
+
+        def linear():
+            _lib.check(lib.pisa_hip_fluctuate_linear(
+                mu.data_ptr(), None if sg is None else sg.data_ptr(), resp.data_ptr(), J, scale.ctypes.data,
+                shift.ctypes.data, lower.ctypes.data, upper.ctypes.data, code, n_b, n_t, 1, k0, 0, out.data_ptr(),
+                eta.data_ptr(), status.data_ptr(), None))
+
+        base = _time(lambda: K.fluctuate(mu, n_t, 1, method=method, sigma=sg, stream=k0, out=out, status=status[:1]), reps)
+        res = _time(linear, reps)
+        print(json.dumps(dict(workload="fluctuate_linear", T=n_t, B=n_b, J=J, method=method, **res,
+                              ms_fluctuate=base["ms_median"], ratio_to_fluctuate=round(res["ms_median"] / base["ms_median"], 3),
+                              clipped=int(status[1].item()))), flush=True)
+        assert int(status[0].item()) == 0
+        status.zero_()
+    drawn = K.fluctuate_linear(mu, resp, n_t, 1, scale, shift, lower, upper, stream=k0)
+    ips = torch.ones(J, dtype=torch.float64, device=dev)
+    for kind in ("llh", "chi2"):
+        fit = K.profiled_metric_matrix_best(kind, drawn["data"], e, r, None, ips, k0=k0)
+        base = _time(lambda: K.profiled_metric_matrix_best(kind, drawn["data"], e, r, None, ips, k0=k0, status=status[:1]),
+                     reps)
+        res = _time(lambda: K.profiled_hesse(kind, drawn["data"], e, r, fit["eta_best"], fit["arg"], None, ips), reps)
+        h = K.profiled_hesse(kind, drawn["data"], e, r, fit["eta_best"], fit["arg"], None, ips)
+        print(json.dumps(dict(workload="profiled_hesse", T=n_t, K=n_k, B=n_b, J=J, kind=kind, **res,
+                              ms_profiled_best=base["ms_median"],
+                              ratio_to_profiled_best=round(res["ms_median"] / base["ms_median"], 5),
+                              flagged=int((h["status"] != 0).sum().item()))), flush=True)
 
 
 def mc_lines(reps=5):
@@ -353,12 +412,18 @@ def main():
                          "prior sigmas")
     ap.add_argument("--mc", action="store_true",
                     help="time the MC-uncertainty metrics against the loop over kernels.metric, and nothing else")
+    ap.add_argument("--truth", action="store_true",
+                    help="time fluctuate_linear against fluctuate and profiled_hesse against profiled_metric_matrix_best, "
+                         "and nothing else")
     args = ap.parse_args()
     import torch
 
     torch.cuda.set_device(0)
     if args.mc:
         mc_lines()
+        return
+    if args.truth:
+        truth_lines()
         return
     if not args.skip_kernels:
         kernel_lines(args.reps, tuple(args.forms.split(",")))
