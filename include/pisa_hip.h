@@ -936,6 +936,32 @@ int pisa_hip_fluctuate_linear(const double *d_mu, const double *d_sigma /* NULL:
                               uint32_t first_trial, double *d_out, double *d_eta_true, int32_t *d_status,
                               void *stream);
 
+/* pisa_hip_fluctuate_linear with CORRELATED truths: those of a fit to an observed map (DESIGN.md section 4,
+ * "pseudo-data at nuisances fitted to the observed data").  Every trial draws eta ~ N(h_mean, h_cov) inside the box:
+ *   factor h_cov [J][J] (row-major, its lower triangle is read) = L L^T, computed once on the host before the launch.
+ *          A coordinate with h_cov[j][j] == 0 is dead (what pisa_hip_profiled_hesse writes for a coordinate held on a
+ *          bound): its row and column must be zero, it is never drawn and its truth is h_mean[j].  Plain Cholesky row
+ *          by row over the live coordinates in ascending order, every operation rounded on its own.
+ *   truth  for the attempt r = 0, 1, ...: z_k = PPND16(u) of the block with the counter (0x80000000 + k, first_trial
+ *          + t, stream_id, r) for the live k -- the counters of pisa_hip_fluctuate_linear's truths --, and the
+ *          candidate x_j = h_mean[j] + L[j][0] z_0 + ... + L[j][j] z_j over the live k in ascending order, every step
+ *          rounded.  The first candidate with EVERY coordinate inside [h_lower[j], h_upper[j]] is d_eta_true[t]: the
+ *          whole vector is rejected, which samples the normal truncated to the box.  After 256 refused candidates the
+ *          last one is held inside the box coordinate by coordinate and d_status[0] becomes
+ *          PISA_HIP_FLUCT_TRUTH_EXHAUSTED.
+ *   mean, entry, d_status: as pisa_hip_fluctuate_linear.
+ * With a diagonal h_cov the truths (and so the data) are those of pisa_hip_fluctuate_linear with h_scale[j] =
+ * sqrt(h_cov[j][j]) and h_shift = h_mean, bit for bit, as long as no candidate of that call is refused.
+ * PISA_HIP_ERR_INVALID before any launch: as pisa_hip_fluctuate_linear; a NULL h_mean or h_cov; an entry of h_mean or
+ * h_cov that is not finite; a mean outside its box; a NaN bound, lower > upper; a dead coordinate with a non-zero
+ * entry in its row or column; a pivot that is <= 0 or NaN (h_cov is not positive definite on its live coordinates). */
+int pisa_hip_fluctuate_linear_mvn(const double *d_mu, const double *d_sigma /* NULL: poisson only */,
+                                  const double *d_response, int32_t n_params, const double *h_mean,
+                                  const double *h_cov /* [n_params][n_params] */, const double *h_lower,
+                                  const double *h_upper, int32_t method, int64_t n_bins, int64_t n_trials,
+                                  uint64_t seed, uint32_t stream_id, uint32_t first_trial, double *d_out,
+                                  double *d_eta_true, int32_t *d_status, void *stream);
+
 /* ----------------------------------------------- binned post-histogram stages */
 
 /* d_out[i] = d_x[i] * d_scale[i] * scalar  (d_scale may be NULL = 1), then, if

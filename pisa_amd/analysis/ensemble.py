@@ -63,12 +63,17 @@ and, for `generator="device"` with `nuisance="prior"`,
     draw_linear(mu [B], response [J, B], sigma [B] or None, method, n_trials, seed, stream, scale, shift, lower, upper
                 ([J] host arrays; lower / upper may be None), first_trial=0)
         -> dict(data [n_trials, B], eta [n_trials, J], clipped)
-and, for `covariance=True` and `pulls`,
+(`nuisance="profiled"` draws through it as well, with every scale 0), and, for `generator="device"` with
+`nuisance="fitted"`,
+    draw_linear_mvn(mu [B], response [J, B], sigma [B] or None, method, n_trials, seed, stream, mean [J], cov [J, J],
+                    lower, upper ([J] host arrays; either may be None), first_trial=0)
+        -> dict(data [n_trials, B], eta [n_trials, J], clipped)
+and, for `covariance=True`, `pulls` and `nuisance="fitted"`,
     hesse(kind, data, expected, response, eta [T, J], k (an int or [T] ints), sigma2, inv_prior_sigma, center,
           lower=, upper=) -> dict(cov [T, J, J], sigma [T, J], status [T])
 so that everything around the kernels can run with a numpy restatement (tests/ensemble_cases.py,
 tests/fluctuate_cases.py, tests/fluctuate_method_cases.py, tests/profile_cases.py, tests/truth_cases.py,
-tests/hesse_cases.py).
+tests/hesse_cases.py, tests/observed_cases.py).
 
 `nuisance="prior"` (`pseudo_data`, `feldman_cousins`; needs `response=`) makes pseudo-experiments with the systematics
 fluctuated: every trial draws the truths of the response's parameters from their priors and its data from the
@@ -76,6 +81,18 @@ linearised template at those truths (csrc/fluctuate_linear.hip; DESIGN.md §4, "
 truths"), where the default `nuisance="fixed"` leaves them at the point's values.  `delta_metric(..., covariance=True)`
 returns the covariance of the fitted displacements (csrc/profile_hesse.hip; "covariance and pulls") and `pulls` the
 distribution (eta_hat - eta_true) / sigma_hat an analyst checks a profiled ensemble with.
+
+Once a data map exists, two more modes generate at the nuisance values that map prefers (`observed=`, with
+`response=`; DESIGN.md §4, "pseudo-data at nuisances fitted to the observed data").  `fit_observed` fits the observed
+map at every point of the grid in one launch: eta_obs [K, J], and with `covariance=True` the fit's covariance cov_obs
+[K, J, J].  `nuisance="profiled"` is the profile construction of a Feldman-Cousins analysis with systematics: the
+pseudo-data of true point k are drawn from hist[k] + sum_j response[k, j] eta_obs[k, j], the same truths in every
+trial -- the generator of "prior" with every scale 0 and the shift eta_obs[k].  `nuisance="fitted"` draws every
+trial's truths from the fit's Gaussian N(eta_obs[k], cov_obs[k]) truncated to the response's box: the truths are
+CORRELATED, so the whole vector is drawn and rejected at once (`fl_truth_factor`, `fl_truth_mvn` of
+csrc/fluctuate_device.hpp; `kernels.fluctuate_linear_mvn`), and a coordinate the fit holds on a bound (a zero row and
+column of cov_obs[k]) stays on it.  A true posterior (anything but the fit's Gaussian) is not built, and
+`nuisance="posterior"` stays an unknown name.
 """
 import math
 
@@ -85,7 +102,7 @@ from pisa_amd.core.map import FLUCTUATE_METHODS
 from pisa_amd.utils.comparisons import ALLCLOSE_KW
 
 __all__ = ["METRICS", "GENERATORS", "FLUCTUATE_METHODS", "DeviceSolver", "TemplateGrid", "NuisanceResponse", "grid_points", "pseudo_data",
-           "metric_matrix", "delta_metric", "pulls", "critical_values", "feldman_cousins", "accepted", "NUISANCE"]
+           "metric_matrix", "delta_metric", "pulls", "critical_values", "feldman_cousins", "accepted", "NUISANCE", "fit_observed"]
 
 # kernels.METRIC_KIND, then kernels.ENSEMBLE_MC_KINDS: the metrics that account for finite MC statistics, which read
 # the templates' sumw2 and have no profiled form
@@ -189,6 +206,16 @@ class DeviceSolver:
         sigma = None if sigma is None else self._up(sigma).reshape(-1)
         return K.fluctuate_linear(self._up(mu).reshape(-1), self._up(response), n_trials, seed, scale, shift, lower,
                                   upper, method=method, sigma=sigma, stream=stream, first_trial=first_trial)
+
+    def draw_linear_mvn(self, mu, response, sigma, method, n_trials, seed, stream, mean, cov, lower=None, upper=None,
+                        first_trial=0):
+        """`draw_linear` with every trial's truths drawn from N(mean [J], cov [J, J]) inside [lower, upper], the whole
+        vector rejected (`kernels.fluctuate_linear_mvn`)"""
+        from pisa_amd import kernels as K
+
+        sigma = None if sigma is None else self._up(sigma).reshape(-1)
+        return K.fluctuate_linear_mvn(self._up(mu).reshape(-1), self._up(response), n_trials, seed, mean, cov, lower,
+                                      upper, method=method, sigma=sigma, stream=stream, first_trial=first_trial)
 
 
 def _rescaled(param, value):
@@ -579,30 +606,45 @@ def _device_draw(solver, grid, k, sigma, method, n_trials, seed, first_trial=0):
     return solver.fluctuate(grid.hist[k], sigma, method, n_trials, seed, stream=k, first_trial=first_trial)
 
 
-NUISANCE = ("fixed", "prior")
+NUISANCE = ("fixed", "prior", "profiled", "fitted")
+_OBSERVED = NUISANCE[2:]       # the modes that read an observed map
+TRUTH_ATTEMPTS = 256           # candidates of one trial's truths before the draw gives up (FL_TRUTH_ATTEMPTS)
+_PROFILE_HELD = 32             # PISA_HIP_PROFILE_HELD: a coordinate held on a bound; the one flag that is no failure
 TRUTH_MIN_MASS = 0.25          # the least share of a prior's mass a parameter's box may hold (kernels.TRUTH_MIN_MASS)
 
 
-def _check_nuisance(nuisance, response, grid, solver, generator, method, metric, what):
-    """`nuisance="prior"` needs a response of this grid, a metric with a profiled form, a method whose mean may move
-    per trial and, for the device generator, a solver that draws such data"""
+def _check_nuisance(nuisance, response, grid, solver, generator, method, metric, what, observed=None):
+    """every mode but "fixed" needs a response of this grid, a metric with a profiled form, a method whose mean may
+    move per trial and, for the device generator, a solver that draws such data; "profiled" and "fitted" need the
+    observed map, which the other two refuse"""
     if nuisance not in NUISANCE:
         raise ValueError("ensemble: nuisance '%s' not among %s" % (nuisance, list(NUISANCE)))
     if generator not in GENERATORS:
         raise ValueError("ensemble: generator '%s' not among %s" % (generator, list(GENERATORS)))
+    if observed is not None and nuisance not in _OBSERVED:
+        raise ValueError("%s: observed= belongs to nuisance='profiled' and 'fitted'; nuisance='%s' reads no data"
+                         % (what, nuisance))
     if nuisance == "fixed":
         return
+    if nuisance in _OBSERVED and observed is None:
+        raise ValueError("%s: nuisance='%s' needs observed=, the map the nuisance parameters are fitted to"
+                         % (what, nuisance))
     if response is None:
-        raise ValueError("%s: nuisance='prior' needs response=, the linear response whose parameters are drawn" % what)
+        raise ValueError("%s: nuisance='%s' needs response=, the linear response whose parameters are drawn"
+                         % (what, nuisance))
     if metric in _MC_METRICS:
-        raise ValueError("%s: nuisance='prior' is not available for '%s' (response= has no form for the "
-                         "MC-uncertainty metrics)" % (what, metric))
+        raise ValueError("%s: nuisance='%s' is not available for '%s' (response= has no form for the "
+                         "MC-uncertainty metrics)" % (what, nuisance, metric))
     if method == "scaled_poisson":
-        raise ValueError("%s: nuisance='prior' has no scaled_poisson draws (the method's row rules compare a row's "
-                         "variance with its mean, which moves per trial)" % what)
-    if generator == "device" and not hasattr(solver, "draw_linear"):
-        raise ValueError("ensemble: generator='device' with nuisance='prior' needs a solver with draw_linear(mu, "
+        raise ValueError("%s: nuisance='%s' has no scaled_poisson draws (the method's row rules compare a row's "
+                         "variance with its mean, which moves per trial)" % (what, nuisance))
+    if generator == "device" and nuisance != "fitted" and not hasattr(solver, "draw_linear"):
+        raise ValueError("ensemble: generator='device' with nuisance='%s' needs a solver with draw_linear(mu, "
                          "response, sigma, method, n_trials, seed, stream, scale, shift, lower, upper, first_trial); "
+                         "%s has none" % (nuisance, type(solver).__name__))
+    if generator == "device" and nuisance == "fitted" and not hasattr(solver, "draw_linear_mvn"):
+        raise ValueError("ensemble: generator='device' with nuisance='fitted' needs a solver with draw_linear_mvn(mu, "
+                         "response, sigma, method, n_trials, seed, stream, mean, cov, lower, upper, first_trial); "
                          "%s has none" % type(solver).__name__)
     shape = tuple(response.response.shape)
     if shape[-1] != grid.n_bins or (len(shape) == 3 and shape[0] != len(grid)):
@@ -659,7 +701,7 @@ def _prior_data(grid, k, n_trials, seed_or_rs, generator, solver, method, respon
         out = solver.draw_linear(grid.hist[k], R, sigma, method, n_trials, seed_or_rs, stream=k, scale=scale,
                                  shift=shift, lower=lower, upper=upper, first_trial=first_trial)
         return out["data"], out["eta"]
-    from scipy.stats import norm, poisson
+    from scipy.stats import norm
 
     for j in np.nonzero(scale > 0)[0]:                 # the device generator's rule, so that both refuse alike
         lo, hi = (-np.inf if lower is None else lower[j]), (np.inf if upper is None else upper[j])
@@ -673,19 +715,172 @@ def _prior_data(grid, k, n_trials, seed_or_rs, generator, solver, method, respon
     data, truth = np.empty((max(n_trials, 0), mu0.size)), np.empty((max(n_trials, 0), scale.size))
     for t in range(data.shape[0]):
         truth[t] = _host_truths(scale, shift, lower, upper, rs)
-        mu = _linear_mean(mu0, R, truth[t])
-        if method != "poisson":
-            data[t] = _host_fluctuate(mu, sigma, method, rs)
-            continue
-        ok = ~np.isnan(mu)
-        data[t] = np.nan
-        if ok.any():
-            data[t, ok] = poisson.rvs(mu[ok], random_state=rs)
+        data[t] = _host_row(_linear_mean(mu0, R, truth[t]), sigma, method, rs)
+    return data, truth
+
+
+def _host_row(mu, sigma, method, rs):
+    """one trial's data by `method` from its own mean `mu` on the stream `rs`: the method's own scipy calls"""
+    if method != "poisson":
+        return _host_fluctuate(mu, sigma, method, rs)
+    from scipy.stats import poisson
+
+    ok = ~np.isnan(mu)
+    row = np.full(mu.size, np.nan)
+    if ok.any():
+        row[ok] = poisson.rvs(mu[ok], random_state=rs)
+    return row
+
+
+def _truth_factor(cov):
+    """`fl_truth_factor` of csrc/fluctuate_device.hpp in numpy: L [J, J] lower triangular with cov = L L^T over the live
+    coordinates (cov[j, j] != 0), rows and columns of the dead ones 0; None where the factor is refused (an entry that
+    is not finite, a dead coordinate with a non-zero entry in its row or column, a pivot <= 0 or NaN)"""
+    cov = np.asarray(cov, dtype=np.float64)
+    J = cov.shape[0]
+    L = np.zeros((J, J))
+    if cov.shape != (J, J) or not np.isfinite(cov).all():
+        return None
+    dead = np.diagonal(cov) == 0.0
+    if np.any(cov[dead, :] != 0.0) or np.any(cov[:, dead] != 0.0):
+        return None
+    with np.errstate(all="ignore"):
+        for i in np.nonzero(~dead)[0]:
+            for j in np.nonzero(~dead[:i + 1])[0]:
+                s = cov[i, j]
+                for k in range(j):
+                    s = s - L[i, k] * L[j, k]
+                if j < i:
+                    s = s / L[j, j]
+                else:
+                    if not s > 0.0:
+                        return None
+                    s = np.sqrt(s)
+                if not np.isfinite(s):
+                    return None
+                L[i, j] = s
+    return L
+
+
+def _host_truths_mvn(mean, L, lower, upper, rs):
+    """one trial's truths of `nuisance="fitted"` on the stream `rs`: per attempt one rs.standard_normal() per live k
+    (L[k, k] != 0) in ascending k, x_j = mean_j + L[j, 0] z_0 + ... + L[j, j] z_j over the live k, and the first
+    candidate with every coordinate inside [lower_j, upper_j]; ValueError after TRUTH_ATTEMPTS refused ones (where the
+    device generator reports its truths exhausted)"""
+    J = mean.size
+    live = np.nonzero(np.diagonal(L) != 0.0)[0]
+    lo = np.full(J, -np.inf) if lower is None else lower
+    hi = np.full(J, np.inf) if upper is None else upper
+    for _ in range(TRUTH_ATTEMPTS):
+        z = np.zeros(J)
+        for k in live:
+            z[k] = rs.standard_normal()
+        x = np.array(mean, dtype=np.float64)
+        for j in live:
+            for k in live[live <= j]:
+                x[j] = x[j] + L[j, k] * z[k]
+        if np.all((lo <= x) & (x <= hi)):
+            return x
+    raise ValueError("pseudo_data: a trial found no candidate inside the box")
+
+
+def fit_observed(observed, grid, metric, response, solver=None, covariance=False):
+    """The conditional fit of ONE observed map at every point of the grid: `observed` a Map, a MapSet of one map or
+    [B] values -> dict of host arrays, eta [K, J] the displacements of the response's parameters that fit the map best
+    given point k and status [K] the fit's flags (one `solver.profiled_matrix` call with T = 1), value [K] the
+    profiled metric there without the points' penalties; with covariance=True also cov [K, J, J], sigma [K, J] and
+    hesse_status [K] (one `solver.hesse` call on the K (map, point) pairs: `delta_metric(..., covariance=True)`
+    describes them).  What `nuisance="profiled"` and "fitted" generate their pseudo-data at."""
+    _check_metric(metric)
+    solver = DeviceSolver() if solver is None else solver
+    if response is None:
+        raise ValueError("fit_observed: needs response=, the linear response whose parameters are fitted")
+    _check_response(response, grid, solver, "fit_observed", metric)
+    if covariance:
+        _check_hesse(solver)
+    rows = _data_rows(observed)
+    if int(rows.shape[0]) != 1 or int(rows.shape[1]) != grid.n_bins:
+        raise ValueError("fit_observed: one observed map of %d bins, got %s" % (grid.n_bins, tuple(rows.shape)))
+    args = (grid.sigma2_for(metric), response.inv_prior_sigma, response.center)
+    out = solver.profiled_matrix(metric, rows, grid.hist, response.response, *args, response.max_iter,
+                                 **response.bounds())
+    fit = dict(eta=_host(out["eta"])[0], status=_host(out["status"])[0], value=_host(out["value"])[0])
+    if covariance:
+        n_k = len(grid)
+        rep = rows.expand(n_k, -1).contiguous() if hasattr(rows, "expand") else np.repeat(rows, n_k, axis=0)
+        h = solver.hesse(metric, rep, grid.hist, response.response, out["eta"][0], np.arange(n_k, dtype=np.int32),
+                         *args, **response.bounds())
+        fit.update(cov=_host(h["cov"]), sigma=_host(h["sigma"]), hesse_status=_host(h["status"]))
+    return fit
+
+
+def _observed_truths(observed, grid, metric, response, solver, nuisance, points, what):
+    """the fit of the observed map the pseudo-data of `points` are generated at, checked -> (eta [K, J], cov [K, J, J]
+    or None): a point whose fit carries a flag, has no covariance, whose covariance has no factor or whose box holds
+    too little of a coordinate's marginal is refused"""
+    from scipy.stats import norm
+
+    for k in points:
+        if not 0 <= k < len(grid):
+            raise ValueError("%s: point %s outside the grid's %d points" % (what, k, len(grid)))
+    fit = fit_observed(observed, grid, metric, response, solver, covariance=nuisance == "fitted")
+    bad = [k for k in points if int(fit["status"][k]) & ~_PROFILE_HELD]
+    if bad:
+        raise ValueError("%s: the fit of the observed map carries a status flag at the points %s (status %s)"
+                         % (what, bad, [int(fit["status"][k]) for k in bad]))
+    if nuisance != "fitted":
+        return fit["eta"], None
+    bad = [k for k in points if np.isnan(fit["cov"][k]).any()]
+    if bad:
+        raise ValueError("%s: the fit of the observed map has no covariance at the points %s (hesse_status %s)"
+                         % (what, bad, [int(fit["hesse_status"][k]) for k in bad]))
+    bad = [k for k in points if _truth_factor(fit["cov"][k]) is None]
+    if bad:
+        raise ValueError("%s: the covariance of the fit of the observed map has no Cholesky factor at the points %s"
+                         % (what, bad))
+    for k in points:
+        _, _, _, lower, upper = _truth_priors(response, k)
+        mean, var = fit["eta"][k], np.diagonal(fit["cov"][k])
+        for j in np.nonzero(var > 0)[0]:
+            lo, hi = (-np.inf if lower is None else lower[j]), (np.inf if upper is None else upper[j])
+            sd = math.sqrt(var[j])
+            mass = norm.cdf((hi - mean[j]) / sd) - norm.cdf((lo - mean[j]) / sd)
+            if mass < TRUTH_MIN_MASS:
+                raise ValueError("%s: at point %d the box [%g, %g] of '%s' holds %.3g of the mass of its fitted N(%g, "
+                                 "%g); at least %g is needed" % (what, k, lo, hi, response.names[j], mass, mean[j], sd,
+                                                                 TRUTH_MIN_MASS))
+    return fit["eta"], fit["cov"]
+
+
+def _observed_data(grid, k, n_trials, seed_or_rs, generator, solver, method, response, eta, cov, first_trial=0):
+    """(data [n_trials, B], eta_true [n_trials, J]) of `nuisance="profiled"` (cov None: every trial's truths are `eta`
+    [J]) and "fitted" (truths from N(eta, cov) inside the response's box) at point k: module docstring"""
+    R, _, _, lower, upper = _truth_priors(response, k)
+    sigma = _sigma_row(grid, k, method)
+    eta = np.ascontiguousarray(eta, dtype=np.float64)
+    if generator != "host":
+        if cov is None:
+            out = solver.draw_linear(grid.hist[k], R, sigma, method, n_trials, seed_or_rs, stream=k,
+                                     scale=np.zeros(eta.size), shift=eta, lower=lower, upper=upper,
+                                     first_trial=first_trial)
+        else:
+            out = solver.draw_linear_mvn(grid.hist[k], R, sigma, method, n_trials, seed_or_rs, stream=k, mean=eta,
+                                         cov=np.ascontiguousarray(cov, dtype=np.float64), lower=lower, upper=upper,
+                                         first_trial=first_trial)
+        return out["data"], out["eta"]
+    rs = seed_or_rs
+    L = None if cov is None else _truth_factor(cov)
+    mu0 = np.asarray(grid.host("hist")[k], dtype=np.float64).ravel()
+    R = _host(R).astype(np.float64)
+    data, truth = np.empty((max(n_trials, 0), mu0.size)), np.empty((max(n_trials, 0), eta.size))
+    for t in range(data.shape[0]):
+        truth[t] = eta if L is None else _host_truths_mvn(eta, L, lower, upper, rs)
+        data[t] = _host_row(_linear_mean(mu0, R, truth[t]), sigma, method, rs)
     return data, truth
 
 
 def pseudo_data(grid, k, n_trials, random_state=None, generator="host", solver=None, method="poisson", response=None,
-                nuisance="fixed", return_truth=False):
+                nuisance="fixed", return_truth=False, observed=None):
     """[n_trials, B] pseudo-data of template k by `method` (one of `FLUCTUATE_METHODS`; every method but "poisson"
     reads sigma = sqrt(grid.sumw2[k]), and "scaled_poisson" applies the reference's row rules to it first: module
     docstring).  With another method than "poisson" the host generator is the loop of `Map.fluctuate(method,
@@ -706,21 +901,40 @@ def pseudo_data(grid, k, n_trials, random_state=None, generator="host", solver=N
     with drawn nuisance truths").  generator="device": `solver.draw_linear` (`kernels.fluctuate_linear`);
     generator="host": per trial, for j ascending, shift_j + scale_j rs.standard_normal() until the candidate is inside
     the box, then the method's own scipy calls on that trial's mean, all on the one RandomState.  nuisance="fixed"
-    (the default) is the call without the argument.  return_truth=True returns (data, eta_true [n_trials, J]: the
+    (the default) is the call without the argument.
+    nuisance="profiled" and "fitted" (with `response` and `observed`, the data map: a Map, a MapSet of one map or [B]
+    values) generate at the nuisance values fitted to the OBSERVED map given point k (`fit_observed`; DESIGN.md §4,
+    "pseudo-data at nuisances fitted to the observed data").  "profiled", the profile construction: every trial's
+    truths are the fitted displacements eta_obs[k] -- the generator of "prior" with every scale 0 and the shift
+    eta_obs[k], bit for bit, on both generators.  "fitted": every trial draws its truths from the fit's Gaussian
+    N(eta_obs[k], cov_obs[k]) truncated to the response's box by rejection of the whole vector, a coordinate the fit
+    holds on a bound staying there; generator="device": `solver.draw_linear_mvn` (`kernels.fluctuate_linear_mvn`);
+    generator="host": per attempt one rs.standard_normal() per live coordinate k in ascending k, x_j = eta_obs[k, j] +
+    L[j, 0] z_0 + ... + L[j, j] z_j with the Cholesky factor L of cov_obs[k], until every coordinate is inside the
+    box, then the method's own scipy calls.  return_truth=True returns (data, eta_true [n_trials, J]: the
     displacements from the point's values the fit's eta estimates; None for "fixed")."""
     method = _check_method(method, grid)
     if nuisance != "fixed":
         solver_ = (DeviceSolver() if solver is None else solver) if generator != "host" else solver
-        _check_nuisance(nuisance, response, grid, solver_, generator, method, grid.metric, "pseudo_data")
-    if nuisance == "prior":
+        _check_nuisance(nuisance, response, grid, solver_, generator, method, grid.metric, "pseudo_data", observed)
+    elif observed is not None:
+        _check_nuisance(nuisance, response, grid, solver, generator, method, grid.metric, "pseudo_data", observed)
+    if nuisance != "fixed":
         if not 0 <= int(k) < len(grid):
             raise ValueError("pseudo_data: point %s outside the grid's %d points" % (k, len(grid)))
+        if nuisance in _OBSERVED:
+            eta, cov = _observed_truths(observed, grid, grid.metric, response, solver_, nuisance, [int(k)],
+                                        "pseudo_data")
         if generator == "host":
             source = random_state if isinstance(random_state, np.random.RandomState) else np.random.RandomState(
                 random_state)
         else:
             source = _base_seed(random_state)
-        data, truth = _prior_data(grid, int(k), int(n_trials), source, generator, solver_, method, response)
+        if nuisance == "prior":
+            data, truth = _prior_data(grid, int(k), int(n_trials), source, generator, solver_, method, response)
+        else:
+            data, truth = _observed_data(grid, int(k), int(n_trials), source, generator, solver_, method, response,
+                                         eta[int(k)], None if cov is None else cov[int(k)])
         return (data, truth) if return_truth else data
     if return_truth:
         return pseudo_data(grid, k, n_trials, random_state, generator, solver, method), None
@@ -888,7 +1102,7 @@ def _base_seed(random_state):
 
 def feldman_cousins(grid, metric, n_trials, cl=(0.6827, 0.90), random_state=None, true_points=None, solver=None,
                     generator="host", chunk_bytes=CHUNK_BYTES, response=None, method="poisson",
-                    nuisance="fixed"):
+                    nuisance="fixed", observed=None):
     """Critical values of the Feldman-Cousins ordering on the grid: for every true point k0 (default: all), n_trials
     pseudo-data maps of template k0, their `delta_metric` at k0 and `critical_values` -> crit [len(true_points),
     len(cl)].  seed: `random_state`, or one draw from it if it is a RandomState.
@@ -903,13 +1117,18 @@ def feldman_cousins(grid, metric, n_trials, cl=(0.6827, 0.90), random_state=None
     [len(true_points)]: per true point the number of trials whose pair at the best point or at the true point carries
     a status flag of the fit).  nuisance="prior" (needs `response`): the pseudo-data of every true point are those of
     `pseudo_data(..., response=response, nuisance="prior")` -- the response's parameters drawn from their priors trial
-    by trial --, the device generator drawing them in the same chunks through the solver's `draw_linear`."""
+    by trial --, the device generator drawing them in the same chunks through the solver's `draw_linear`.
+    nuisance="profiled" and "fitted" (need `response` and `observed`, the data map): the observed map is fitted once
+    at all points (`fit_observed`) and the pseudo-data of true point k0 are those of `pseudo_data(..., nuisance=...,
+    observed=observed)` -- generated at the displacements fitted to the observed map given k0 (the profile
+    construction), or at truths drawn from that fit's Gaussian --, in the chunks, seeds and streams of "prior"; info
+    gains eta_observed [len(true_points), J] and, for "fitted", cov_observed [len(true_points), J, J]."""
     _check_metric(metric)
     if n_trials < 1:
         raise ValueError("feldman_cousins: n_trials >= 1")
     solver = DeviceSolver() if solver is None else solver
     method = _check_method(method, grid)
-    _check_nuisance(nuisance, response, grid, solver, generator, method, metric, "feldman_cousins")
+    _check_nuisance(nuisance, response, grid, solver, generator, method, metric, "feldman_cousins", observed)
     if nuisance == "fixed":
         _check_generator(generator, solver, method)
     if response is not None:
@@ -930,16 +1149,23 @@ def feldman_cousins(grid, metric, n_trials, cl=(0.6827, 0.90), random_state=None
             raise ValueError("feldman_cousins: true point %d outside the grid's %d points" % (k0, len(grid)))
     cl = np.atleast_1d(np.asarray(cl, dtype=np.float64))
     crit = np.empty((len(points), cl.size))
+    if nuisance in _OBSERVED:
+        eta_obs, cov_obs = _observed_truths(observed, grid, metric, response, solver, nuisance, list(points),
+                                            "feldman_cousins")
     rows = max(1, int(chunk_bytes) // (8 * grid.n_bins))
     for i, k0 in enumerate(points):
         flagged.append(0)
-        if nuisance == "prior":
+        if nuisance != "fixed":
             parts = []
             source = np.random.RandomState([seed, k0]) if generator == "host" else seed
             for first in range(0, n_trials, n_trials if generator == "host" else rows):
                 n = n_trials if generator == "host" else min(rows, n_trials - first)
-                parts.append(distances(_prior_data(grid, k0, n, source, generator, solver, method, response, first)[0],
-                                       k0))
+                if nuisance == "prior":
+                    data = _prior_data(grid, k0, n, source, generator, solver, method, response, first)[0]
+                else:
+                    data = _observed_data(grid, k0, n, source, generator, solver, method, response, eta_obs[k0],
+                                          None if cov_obs is None else cov_obs[k0], first)[0]
+                parts.append(distances(data, k0))
             delta = np.concatenate(parts)
         elif generator == "host":
             data = pseudo_data(grid, k0, n_trials, np.random.RandomState([seed, k0]), method=method)
@@ -954,7 +1180,12 @@ def feldman_cousins(grid, metric, n_trials, cl=(0.6827, 0.90), random_state=None
         crit[i] = critical_values(delta, cl)
     if response is None:
         return crit
-    return crit, dict(flagged=np.array(flagged, dtype=np.int64))
+    info = dict(flagged=np.array(flagged, dtype=np.int64))
+    if nuisance in _OBSERVED:
+        info["eta_observed"] = eta_obs[list(points)]
+        if cov_obs is not None:
+            info["cov_observed"] = cov_obs[list(points)]
+    return crit, info
 
 
 def accepted(data_map, grid, metric, crit, solver=None, response=None):

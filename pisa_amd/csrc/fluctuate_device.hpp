@@ -232,4 +232,89 @@ PISA_FL_HD double fl_linear_mean(double mu0, const double *r, int64_t stride, co
     return clipped ? 0.0 : mu;
 }
 
+// ---- truths drawn from a fit's Gaussian N(mean, cov) inside a box (fluctuate_linear.hip; DESIGN.md §4, "pseudo-data
+// at nuisances fitted to the observed data") ----
+constexpr int FL_MVN_MAX = 8;   // parameters at most; L is kept [FL_MVN_MAX][FL_MVN_MAX] whatever J is
+
+// The factor of cov [J][J] (row-major; its lower triangle is read): L [FL_MVN_MAX][FL_MVN_MAX] lower triangular with
+// cov = L L^T, entries outside the leading J x J block 0.  A coordinate with cov[j][j] == 0 is dead: its row and
+// column of cov must hold zeros alone (else refused), row and column j of L are 0 and the coordinate is never drawn.
+// Over the live coordinates in ascending order plain Cholesky row by row,
+//     L[i][j] = (cov[i][j] - sum_{k<j} L[i][k] L[j][k]) / L[j][j],   L[j][j] = sqrt(cov[j][j] - sum_{k<j} L[j][k]^2),
+// the sums in ascending k, every product, subtraction, division and the sqrt rounded on its own.  false (refused): a J
+// outside [1, FL_MVN_MAX], an entry of cov that is not finite, a dead coordinate with a non-zero entry, a pivot that is
+// <= 0 or NaN, an entry of L that is not finite.
+PISA_FL_HD bool fl_truth_factor(const double *cov, int J, double *L) {
+    for (int i = 0; i < FL_MVN_MAX * FL_MVN_MAX; i++) L[i] = 0.0;
+    if (J < 1 || J > FL_MVN_MAX) return false;
+    for (int i = 0; i < J * J; i++)
+        if (!(fabs(cov[i]) <= 1.7976931348623157e308)) return false;
+    for (int j = 0; j < J; j++) {
+        if (cov[j * J + j] != 0.0) continue;
+        for (int i = 0; i < J; i++)
+            if (cov[j * J + i] != 0.0 || cov[i * J + j] != 0.0) return false;
+    }
+    for (int i = 0; i < J; i++) {
+        if (cov[i * J + i] == 0.0) continue;
+        for (int j = 0; j <= i; j++) {
+            if (cov[j * J + j] == 0.0) continue;
+            double s = cov[i * J + j];
+            for (int k = 0; k < j; k++) {
+                const double t = L[i * FL_MVN_MAX + k] * L[j * FL_MVN_MAX + k];   // (0 for a dead k)
+                s = s - t;
+            }
+            if (j < i) {
+                s = s / L[j * FL_MVN_MAX + j];
+            } else {
+                if (!(s > 0.0)) return false;
+                s = sqrt(s);
+            }
+            if (!(fabs(s) <= 1.7976931348623157e308)) return false;
+            L[i * FL_MVN_MAX + j] = s;
+        }
+    }
+    return true;
+}
+
+// The truths x [J] of trial number `trial`: for the attempt r = 0, 1, ... the deviates z_k of the blocks (FL_TRUTH_WORD
+// + k, trial, stream, r) -- the counters of fl_truth -- for the live k (L[k][k] != 0) alone, and the candidate
+//     x_j = mean_j + L[j][0] z_0 + ... + L[j][j] z_j   over the live k in ascending order, every step rounded
+// (x_j = mean_j for a dead j).  The first candidate ALL of whose coordinates lie inside [lower_j, upper_j] is the
+// truth: rejection of the whole vector, which is what samples the normal truncated to the box.  After
+// FL_TRUTH_ATTEMPTS refused candidates the last one is held inside the box coordinate by coordinate and `exhausted`
+// is set.  The loops have constant bounds so that z and x stay in registers in the kernel.
+PISA_FL_HD void fl_truth_mvn(uint32_t trial, uint32_t stream, uint32_t k0, uint32_t k1, const double *mean,
+                             const double *L, int J, const double *lower, const double *upper, double *x,
+                             bool &exhausted) {
+    double z[FL_MVN_MAX];
+    for (uint32_t r = 0; r < (uint32_t)FL_TRUTH_ATTEMPTS; r++) {
+        bool inside = true;
+#pragma unroll
+        for (int j = 0; j < FL_MVN_MAX; j++) {
+            if (j < J) {
+                double xj = mean[j];
+                z[j] = 0.0;
+                if (L[j * FL_MVN_MAX + j] != 0.0) {
+                    const FlWords w = fl_philox(FL_TRUTH_WORD + (uint32_t)j, trial, stream, r, k0, k1);
+                    z[j] = fl_normal_quantile(fl_unit_open(w.w[0], w.w[1]));
+#pragma unroll
+                    for (int k = 0; k <= j; k++) {
+                        if (L[k * FL_MVN_MAX + k] != 0.0) {
+                            const double t = L[j * FL_MVN_MAX + k] * z[k];
+                            xj = xj + t;
+                        }
+                    }
+                }
+                x[j] = xj;
+                inside = inside && xj >= lower[j] && xj <= upper[j];
+            }
+        }
+        if (inside) return;
+    }
+    exhausted = true;
+#pragma unroll
+    for (int j = 0; j < FL_MVN_MAX; j++)
+        if (j < J) x[j] = x[j] < lower[j] ? lower[j] : (x[j] > upper[j] ? upper[j] : x[j]);
+}
+
 }  // namespace pisa

@@ -18,6 +18,10 @@
 // no cross-lane operation.  The number of clipped means is the one thing the lanes share: a lane that clipped adds
 // its own count to the word with ONE atomic after its last entry -- integer addition, so the word does not depend on
 // the order --, and a lane that clipped nothing (every lane of an ordinary call) touches nothing.
+// pisa_hip_fluctuate_linear_mvn is the same call with CORRELATED truths, those of a fit to an observed map: eta[t] ~
+// N(mean, cov) inside the box by rejection of the whole vector (fl_truth_factor, fl_truth_mvn; DESIGN.md §4,
+// "pseudo-data at nuisances fitted to the observed data"; tests/observed_cases.py).  truth_mvn_kernel, one lane per
+// trial, takes the place of truth_kernel; linear_kernel runs unchanged on its truths.
 #include "common.hpp"
 #include "fluctuate_device.hpp"
 
@@ -108,6 +112,47 @@ static bool truth_priors(int32_t n_params, const double *h_scale, const double *
     return true;
 }
 
+// ---- truths from a fit's Gaussian: pisa_hip_fluctuate_linear_mvn ----
+// The truths of a trial are correlated, so a lane takes a whole trial: J Philox blocks and a J x J triangle of
+// multiply-adds per attempt, everything in registers, nothing shared between lanes.  The mean, the box and the factor
+// L (computed once per launch on the host by fl_truth_factor) are the kernel's arguments.
+struct TruthMvn {
+    double mean[FL_MVN_MAX], lower[FL_MVN_MAX], upper[FL_MVN_MAX], L[FL_MVN_MAX * FL_MVN_MAX];
+};
+
+static_assert(FL_MVN_MAX == FLL_MAX_PARAMS, "one limit on the number of parameters");
+
+// lane i0 takes the trials i0, i0 + lanes of the grid, ...
+__global__ void __launch_bounds__(FLL_THREADS)
+truth_mvn_kernel(TruthMvn p, int J, int64_t T, uint32_t k0, uint32_t k1, uint32_t stream, uint32_t first_trial,
+                 double *__restrict__ eta, int32_t *__restrict__ status) {
+    bool exhausted = false;
+    const int64_t step = (int64_t)gridDim.x * FLL_THREADS;
+    for (int64_t t = (int64_t)blockIdx.x * FLL_THREADS + threadIdx.x; t < T; t += step) {
+        double x[FL_MVN_MAX];
+        fl_truth_mvn(first_trial + (uint32_t)t, stream, k0, k1, p.mean, p.L, J, p.lower, p.upper, x, exhausted);
+#pragma unroll
+        for (int j = 0; j < FL_MVN_MAX; j++)
+            if (j < J) eta[t * J + j] = x[j];
+    }
+    if (exhausted) status[0] = PISA_HIP_FLUCT_TRUTH_EXHAUSTED;   // (every writer stores the same word)
+}
+
+// the fit's numbers checked and copied: the mean finite and inside its box, lower <= upper (no NaN), a factor of cov
+static bool truth_mvn(int32_t n_params, const double *h_mean, const double *h_cov, const double *h_lower,
+                      const double *h_upper, TruthMvn &p) {
+    if (n_params < 1 || n_params > FLL_MAX_PARAMS || !h_mean || !h_cov) return false;
+    for (int j = 0; j < FL_MVN_MAX; j++) {
+        const bool live = j < n_params;
+        p.mean[j] = live ? h_mean[j] : 0.0;
+        p.lower[j] = live && h_lower ? h_lower[j] : -INFINITY;
+        p.upper[j] = live && h_upper ? h_upper[j] : INFINITY;
+        if (!(fabs(p.mean[j]) <= 1.7976931348623157e308)) return false;
+        if (!(p.lower[j] <= p.mean[j] && p.mean[j] <= p.upper[j])) return false;
+    }
+    return fl_truth_factor(h_cov, n_params, p.L);
+}
+
 }  // namespace pisa
 
 using namespace pisa;
@@ -132,6 +177,32 @@ PISA_API int pisa_hip_fluctuate_linear(const double *d_mu, const double *d_sigma
                        (uint32_t)n_params, pairs, (uint32_t)(seed & 0xffffffffu), (uint32_t)(seed >> 32), stream_id,
                        first_trial, d_eta_true, d_status);
     PISA_CHECK_LAUNCH("truth_kernel");
+    return dispatch_int<FL_POISSON, FL_GAUSS, FL_GAUSS_POISSON>(method, [&](auto m) {
+        return linear_launch<decltype(m)::value>(d_mu, d_sigma, d_response, n_params, n_bins, n_trials, seed,
+                                                 stream_id, first_trial, d_out, d_eta_true, d_status, stream);
+    });
+}
+
+PISA_API int pisa_hip_fluctuate_linear_mvn(const double *d_mu, const double *d_sigma, const double *d_response,
+                                           int32_t n_params, const double *h_mean, const double *h_cov,
+                                           const double *h_lower, const double *h_upper, int32_t method,
+                                           int64_t n_bins, int64_t n_trials, uint64_t seed, uint32_t stream_id,
+                                           uint32_t first_trial, double *d_out, double *d_eta_true, int32_t *d_status,
+                                           void *stream) {
+    if (!d_mu || !d_response || !d_out || !d_eta_true || !d_status) return PISA_HIP_ERR_INVALID;
+    if (n_bins < 1 || n_trials < 1 || n_bins > 0x7FFFFFFF || n_trials > 0x7FFFFFFF) return PISA_HIP_ERR_INVALID;
+    if ((int64_t)first_trial + n_trials > ((int64_t)1 << 32)) return PISA_HIP_ERR_INVALID;
+    if (method != FL_POISSON && method != FL_GAUSS && method != FL_GAUSS_POISSON) return PISA_HIP_ERR_INVALID;
+    if (method != FL_POISSON && !d_sigma) return PISA_HIP_ERR_INVALID;
+    TruthMvn p;
+    if (!truth_mvn(n_params, h_mean, h_cov, h_lower, h_upper, p)) return PISA_HIP_ERR_INVALID;
+
+    const int64_t want = (n_trials + FLL_THREADS - 1) / FLL_THREADS;
+    const int64_t blocks = want < FLL_MAX_BLOCKS ? want : FLL_MAX_BLOCKS;
+    hipLaunchKernelGGL(truth_mvn_kernel, dim3((unsigned)blocks), dim3(FLL_THREADS), 0, as_stream(stream), p,
+                       (int)n_params, n_trials, (uint32_t)(seed & 0xffffffffu), (uint32_t)(seed >> 32), stream_id,
+                       first_trial, d_eta_true, d_status);
+    PISA_CHECK_LAUNCH("truth_mvn_kernel");
     return dispatch_int<FL_POISSON, FL_GAUSS, FL_GAUSS_POISSON>(method, [&](auto m) {
         return linear_launch<decltype(m)::value>(d_mu, d_sigma, d_response, n_params, n_bins, n_trials, seed,
                                                  stream_id, first_trial, d_out, d_eta_true, d_status, stream);

@@ -853,6 +853,52 @@ def fluctuate_linear(mu, response, n_trials, seed, scale, shift, lower=None, upp
     return dict(data=out, eta=eta, clipped=clipped & 0xFFFFFFFF)
 
 
+def fluctuate_linear_mvn(mu, response, n_trials, seed, mean, cov, lower=None, upper=None, method="poisson", sigma=None,
+                         stream=0, first_trial=0):
+    """`fluctuate_linear` with correlated truths, those of a fit to an observed map (`pisa_hip_fluctuate_linear_mvn`;
+    DESIGN.md §4, "pseudo-data at nuisances fitted to the observed data"): mean [J] and cov [J, J] host numbers, the
+    fitted displacements and their covariance.  Trial t draws its truths from N(mean, cov) truncated to the box
+    [lower, upper] by rejection of the whole vector; a coordinate with cov[j, j] == 0 (one the fit holds on a bound:
+    its row and column are zero) stays at mean[j].  -> dict(data [n_trials, B], eta [n_trials, J]: device tensors;
+    clipped), with the conventions of `fluctuate_linear`.  With a diagonal cov and no box it is `fluctuate_linear(...,
+    scale=sqrt(diag(cov)), shift=mean)`, bit for bit.  Refused (ValueError): "scaled_poisson"; a coordinate whose
+    marginal N(mean_j, cov_jj) holds less than `TRUTH_MIN_MASS` inside [lower_j, upper_j].  The library refuses
+    (PisaHipError, nothing is launched) a cov that is not finite or has no Cholesky factor on its live coordinates, a
+    dead coordinate with a non-zero entry in its row or column, and a mean that is not finite or outside its box."""
+    name = fluctuate_method(method)
+    if name == "scaled_poisson":
+        raise ValueError("fluctuate_linear_mvn: no scaled_poisson draws from a mean that moves per trial (its row "
+                         "rules compare a row's variance with its mean)")
+    if response.dim() != 2 or response.dtype != F8 or mu.dim() != 1 or response.shape[1] != mu.shape[0] or (
+            response.device != mu.device):
+        raise ValueError("fluctuate_linear_mvn: response is float64 [n_params, n_bins] on mu's device")
+    n_j = response.shape[0]
+    if not 1 <= n_j <= _lib.PROFILE_MAX_PARAMS:
+        raise ValueError("fluctuate_linear_mvn: %d nuisance parameters, 1 to %d are drawn"
+                         % (n_j, _lib.PROFILE_MAX_PARAMS))
+    mu, sigma, n_bins, n_trials, seed, stream, first_trial, out = _draw_args(
+        "fluctuate_linear_mvn", mu, sigma, name, n_trials, seed, stream, first_trial, None)
+    cov = np.ascontiguousarray(cov, dtype=np.float64)
+    if cov.shape != (n_j, n_j):
+        raise ValueError("fluctuate_linear_mvn: cov is [%d, %d]" % (n_j, n_j))
+    with np.errstate(all="ignore"):
+        var = np.diagonal(cov)
+        scale = np.where(var > 0, np.sqrt(np.where(var > 0, var, 0.0)), 0.0)     # (anything else: the library's)
+    _, mean, lower, upper = _truth_args("fluctuate_linear_mvn", n_j, scale, mean, lower, upper)
+    response = response.contiguous()
+    eta = torch.empty((out.shape[0], n_j), dtype=F8, device=mu.device)
+    status = torch.zeros(2, dtype=torch.int32, device=mu.device)
+    _lib.check(_lib.lib().pisa_hip_fluctuate_linear_mvn(
+        _ptr(mu), _ptr(sigma), _ptr(response), n_j, mean.ctypes.data, cov.ctypes.data, lower.ctypes.data,
+        upper.ctypes.data, FLUCTUATE_METHOD[name], n_bins, n_trials, seed, stream, first_trial, _ptr(out), _ptr(eta),
+        _ptr(status), _stream()))
+    word, clipped = (int(x) for x in status.cpu().numpy())
+    if word == _lib.FLUCT_TRUTH_EXHAUSTED:
+        raise ValueError("fluctuate_linear_mvn: a trial found no candidate inside the box")
+    _lib.check(word)
+    return dict(data=out, eta=eta, clipped=clipped & 0xFFFFFFFF)
+
+
 def _profile_args(what, kind, data, expected, response, sigma2, inv_prior_sigma, center, max_iter):
     if kind in ENSEMBLE_MC_KINDS:
         raise ValueError("%s: '%s' has no profiled form (its per-bin function is not convex in the response)"

@@ -26,8 +26,14 @@
     (its two launches, the status not read) against `kernels.fluctuate` of the same run, poisson and gauss+poisson;
     `kernels.profiled_hesse` at the fitted eta_best / arg against `kernels.profiled_metric_matrix_best`, llh and chi2.
 
+  * `--observed` (alone: nothing else runs): the pseudo-data at nuisances fitted to an observed map at (T, K, B, J) =
+    (1e4, 1e2, 128, 8), median of 5 launches, HIP events: `pisa_hip_fluctuate_linear_mvn` (its two launches, truths
+    N(0, cov) with sigma 0.5 and correlation 0.5 inside +-1.5, the status not read) against `pisa_hip_fluctuate_linear`
+    and `kernels.fluctuate` of the same run, poisson and gauss+poisson; then one `feldman_cousins(generator="device")`
+    with `nuisance="prior"`, "profiled" and "fitted" over the grid's points (wall time after a warm-up run).
+
     python scripts/bench_ensemble.py [--reps 20] [--skip-e2e] [--skip-kernels] [--skip-draw] [--forms direct,product]
-                                     [--true-points N] [--generator host|device|both] [--e2e-reps 3] [--mc] [--truth]
+                                     [--true-points N] [--generator host|device|both] [--e2e-reps 3] [--mc] [--truth] [--observed]
                                      [--metric llh] [--method poisson]
 """
 import argparse
@@ -234,6 +240,77 @@ def truth_lines(reps=5):
                               flagged=int((h["status"] != 0).sum().item()))), flush=True)
 
 
+def observed_lines(reps=5):
+    """one line per method for `pisa_hip_fluctuate_linear_mvn` against `pisa_hip_fluctuate_linear` (and `fluctuate`) of
+    the same run at (T, K, B, J) = (1e4, 1e2, 128, 8), then one `feldman_cousins(nuisance="fitted")` over the grid
+    against `nuisance="prior"` and "profiled" (wall time, synchronised, after a warm-up run with few trials); the inputs
+    of `truth_lines`"""
+    import torch
+
+    from pisa_amd import _lib
+    from pisa_amd import kernels as K
+    from pisa_amd.analysis import ensemble as en
+
+    dev = K.device()
+    n_t, n_k, n_b, J = 10 ** 4, 10 ** 2, 128, 8
+    e_host = _templates(n_k, n_b)
+    x = (np.arange(n_b) + 0.5) / n_b
+    r_host = 0.05 * np.cos((np.arange(J)[:, None] + 1) * np.pi * x[None, :])[None] * e_host[:, None, :]
+    e, r = torch.from_numpy(e_host).to(dev), torch.from_numpy(r_host).to(dev)
+    k0 = n_k // 2
+    mu, sigma, resp = e[k0].contiguous(), torch.sqrt(0.3 * e[k0]).contiguous(), r[k0].contiguous()
+    scale, shift = np.full(J, 0.5), np.zeros(J)
+    lower, upper = np.full(J, -1.5), np.full(J, 1.5)
+    cov = np.ascontiguousarray(0.25 * (0.5 * np.ones((J, J)) + 0.5 * np.eye(J)))      # sigma 0.5, correlation 0.5
+    out = torch.empty((n_t, n_b), dtype=torch.float64, device=dev)
+    eta = torch.empty((n_t, J), dtype=torch.float64, device=dev)
+    status = torch.zeros(2, dtype=torch.int32, device=dev)
+    lib = _lib.lib()
+    for method in ("poisson", "gauss+poisson"):
+        sg = None if method == "poisson" else sigma
+        code = K.FLUCTUATE_METHOD[method]
+
+        def call(entry, first, second):          # (scale, shift) of the one entry point, (mean, cov) of the other
+            _lib.check(entry(mu.data_ptr(), None if sg is None else sg.data_ptr(), resp.data_ptr(), J,
+                             first.ctypes.data, second.ctypes.data, lower.ctypes.data,
+                             upper.ctypes.data, code, n_b, n_t, 1, k0, 0, out.data_ptr(), eta.data_ptr(),
+                             status.data_ptr(), None))
+
+        base = _time(lambda: K.fluctuate(mu, n_t, 1, method=method, sigma=sg, stream=k0, out=out, status=status[:1]), reps)
+        lin = _time(lambda: call(lib.pisa_hip_fluctuate_linear, scale, shift), reps)
+        res = _time(lambda: call(lib.pisa_hip_fluctuate_linear_mvn, shift, cov), reps)
+        print(json.dumps(dict(workload="fluctuate_linear_mvn", T=n_t, B=n_b, J=J, method=method, **res,
+                              ms_fluctuate_linear=lin["ms_median"], ms_fluctuate=base["ms_median"],
+                              ratio_to_fluctuate_linear=round(res["ms_median"] / lin["ms_median"], 3),
+                              ratio_to_fluctuate=round(res["ms_median"] / base["ms_median"], 3),
+                              clipped=int(status[1].item()))), flush=True)
+        assert int(status[0].item()) == 0
+        status.zero_()
+    # end to end: the priors N(0, 0.5) of the lines above, the observed map one draw of point k0 at displaced truths
+    grid = en.TemplateGrid(e, None, np.zeros((n_k, 1)), None, None, "llh")
+    response = en.NuisanceResponse(["p%d" % j for j in range(J)], r, np.full(J, 2.0), np.zeros((n_k, J)), np.zeros(n_k),
+                                   np.zeros((n_k, J)), lower=lower, upper=upper)
+    observed = K.fluctuate_linear(mu, resp, 1, 7, np.zeros(J), 0.3 * np.cos(np.arange(J)), stream=k0)["data"]
+    fit = en.fit_observed(observed, grid, "llh", response, covariance=True)
+    good = [k for k in range(n_k) if not (int(fit["status"][k]) & ~32) and not np.isnan(fit["cov"][k]).any()]
+    wall = {}
+    for nuisance in ("prior", "profiled", "fitted"):
+        kw = dict(generator="device", response=response, nuisance=nuisance, true_points=good)
+        if nuisance != "prior":
+            kw["observed"] = observed
+        en.feldman_cousins(grid, "llh", 64, random_state=1, **kw)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        crit, info = en.feldman_cousins(grid, "llh", n_t, random_state=1, **kw)
+        torch.cuda.synchronize()
+        wall[nuisance] = time.perf_counter() - t0
+        print(json.dumps(dict(workload="feldman_cousins_nuisance", nuisance=nuisance, T=n_t, K=n_k, B=n_b, J=J,
+                              true_points=len(good), wall_s=round(wall[nuisance], 3),
+                              ratio_to_prior=round(wall[nuisance] / wall["prior"], 3),
+                              flagged=int(info["flagged"].sum()), crit_68_mean=round(float(crit[:, 0].mean()), 4))),
+              flush=True)
+
+
 def mc_lines(reps=5):
     import torch
 
@@ -415,6 +492,9 @@ def main():
     ap.add_argument("--truth", action="store_true",
                     help="time fluctuate_linear against fluctuate and profiled_hesse against profiled_metric_matrix_best, "
                          "and nothing else")
+    ap.add_argument("--observed", action="store_true",
+                    help="time fluctuate_linear_mvn against fluctuate_linear and feldman_cousins(nuisance='fitted') "
+                         "against nuisance='prior', and nothing else")
     args = ap.parse_args()
     import torch
 
@@ -424,6 +504,9 @@ def main():
         return
     if args.truth:
         truth_lines()
+        return
+    if args.observed:
+        observed_lines()
         return
     if not args.skip_kernels:
         kernel_lines(args.reps, tuple(args.forms.split(",")))
