@@ -962,6 +962,16 @@ int pisa_hip_fluctuate_linear_mvn(const double *d_mu, const double *d_sigma /* N
                                   uint64_t seed, uint32_t stream_id, uint32_t first_trial, double *d_out,
                                   double *d_eta_true, int32_t *d_status, void *stream);
 
+/* pisa_hip_fluctuate_linear at truths the caller gives: d_eta [n_trials][J] is an INPUT on the device and no truth is
+ * drawn; mean, entry and d_status ([0] the error word, [1] the number of clipped means) are those stated there.  With
+ * every row of d_eta equal to h_shift the output is that of pisa_hip_fluctuate_linear with every scale 0, bit for bit.
+ * A NaN eta entry gives NaN means, which follow the NaN rule (NaN entries, nothing drawn); an infinite one gives means
+ * that are infinite or NaN and follow the rules of such a mean.  _SCALED_POISSON is refused.  PISA_HIP_ERR_INVALID before any launch: as there, and a NULL d_eta. */
+int pisa_hip_fluctuate_linear_at(const double *d_mu, const double *d_sigma /* NULL: poisson only */,
+                                 const double *d_response, int32_t n_params, const double *d_eta, int32_t method,
+                                 int64_t n_bins, int64_t n_trials, uint64_t seed, uint32_t stream_id,
+                                 uint32_t first_trial, double *d_out, int32_t *d_status, void *stream);
+
 /* ----------------------------------------------- binned post-histogram stages */
 
 /* d_out[i] = d_x[i] * d_scale[i] * scalar  (d_scale may be NULL = 1), then, if
@@ -1378,6 +1388,53 @@ int pisa_hip_profiled_hesse(int32_t kind, const double *d_data, const double *d_
                             int64_t n_bins, const int32_t *d_k_of_trial /* NULL: k0 */, int32_t k0,
                             const double *d_eta, double *d_cov, int32_t *d_trial_status, int32_t *d_status,
                             void *stream);
+
+/* Samples of the posterior of the displacements, p(eta | data row, template row) (csrc/posterior.hip; the definition:
+ * csrc/posterior_device.hpp and DESIGN.md section 4, "Trial ensembles: the nuisance posterior"): a Goodman-Weare
+ * stretch-move ensemble sampler (scale a = 2, red-blue split), every problem and every step in one launch.
+ * Problem p: data row t_p = d_t_of_problem[p], template row k_p = d_k_of_problem[p] (either NULL: p itself) and
+ * W = n_walkers walkers in J = n_params dimensions; H = W / 2.
+ *   log-density  lp(eta) = -Phi(eta) for _LLH and _POISSON_LLH, -Phi(eta) / 2 for _CHI2 and _MOD_CHI2, with Phi the
+ *       objective stated at pisa_hip_profiled_metric_matrix, formed as the solver forms it at a trial point: bins in
+ *       ascending order, a bin with a non-finite datum or expectation skipped, a compensated chain, then the prior
+ *       terms in ascending j.  lp = -inf where a responding finite bin has a mean that is not >= 1e-10, where some
+ *       eta_j lies outside [lower_j, upper_j] (the arguments of the bounded fit; NULL: no bound), or Phi is NaN.
+ *   numbers  Philox4x32-10 under the key of seed, as pisa_hip_fluctuate.  Walker w at step s reads the blocks with the
+ *       counters A = (0xC0000000 + w, s, stream_id, chain_id_p) and B = (0xD0000000 + w, s, stream_id, chain_id_p);
+ *       chain_id_p = d_chain_id[p] (NULL: p).  u_z and u_p: the first and second double of A on [0, 1) (53 bits of two
+ *       words each); u_a: the first double of B on the open interval, as the normal deviates take it.  s = first_step
+ *       + i is the GLOBAL step number.  No other block of the library has a first word of this form.
+ *   step  the walkers [0, H) move against the current state of [H, W), then [H, W) against the new state of [0, H).
+ *       A moving walker at x: z = ((u_z + 1)(u_z + 1)) / 2, the partner q = min((int)(u_p H), H - 1) of the other half
+ *       at c, the proposal y_j = c_j + z (x_j - c_j), every operation rounded on its own; accepted iff lp(y) is
+ *       neither NaN nor -inf and log(u_a) < (N - 1) log(z) + (lp(y) - lp(x)), N the number of coordinates that are
+ *       not pinned (lower_j < upper_j, or an infinite bound).
+ *   start  d_x0 [P][W][J].  d_problem_status[p]: _START_OUTSIDE if a walker starts at lp = -inf or NaN, _BAD_BOUNDS for
+ *       a bound pair that is not lower <= upper, -1 for a row index outside its array (d_status[0] becomes
+ *       PISA_HIP_ERR_INVALID); such a problem does not move, its outputs are NaN and its accept counts 0.
+ *   kept  step s iff s >= keep_from and (s - keep_from) % thin == 0; n_keep must be their number among the n_steps.
+ *   d_chain [P][n_keep][W][J], d_logp [P][n_keep][W], d_accepted [P][W] (int32: accepted proposals of this call),
+ *   d_x_end [P][W][J] (may be NULL): the state after the last step.
+ * The bits of problem p depend on its rows, its start, (seed, stream_id, chain_id_p) and the step numbers alone: not
+ * on P, the problem's place, the launch, or how the steps are split over calls -- a call of n steps continued from
+ * d_x_end with first_step + n equals one call of 2 n steps.
+ * d_status[1] (int32, zeroed by the caller): PISA_HIP_ERR_NEGATIVE for a negative datum or expectation in a row that
+ * is read.  PISA_HIP_ERR_INVALID before any device access: an unknown kind (the MC-uncertainty kinds have no form
+ * here), J outside [1, _MAX_PARAMS], W odd, < 2, < 2 J or > _MAX_WALKERS, thin < 1, a negative first_step or keep_from,
+ * first_step + n_steps > 2^32, a size outside [1, 2^31 - 1], a wrong n_keep, a chain of more than 2^40 bytes, a
+ * stride as in the bounded fit, a NULL pointer where one is required (d_chain and d_logp unless n_keep is 0),
+ * _MOD_CHI2 without d_sigma2, more problems than rows where an index array is NULL. */
+#define PISA_HIP_POSTERIOR_MAX_WALKERS 256
+int pisa_hip_posterior_sample(int32_t kind, const double *d_data, const double *d_expected, const double *d_sigma2,
+                              const double *d_response, int64_t response_stride_k, const double *d_inv_prior_sigma,
+                              const double *d_center, const double *d_lower, const double *d_upper,
+                              int64_t bound_stride_k, int32_t n_params, int64_t n_data, int64_t n_templates,
+                              int64_t n_bins, int64_t n_problems, const int32_t *d_t_of_problem,
+                              const int32_t *d_k_of_problem, const uint32_t *d_chain_id, int32_t n_walkers,
+                              const double *d_x0, uint64_t seed, uint32_t stream_id, int64_t first_step,
+                              int64_t n_steps, int64_t keep_from, int64_t thin, int64_t n_keep, double *d_chain,
+                              double *d_logp, int32_t *d_accepted, double *d_x_end, int32_t *d_problem_status,
+                              int32_t *d_status, void *stream);
 
 /* ------------------------------------------------------- raw device memory */
 /* Thin wrappers so hosts without torch (a cgo/ctypes binding of the

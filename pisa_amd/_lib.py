@@ -35,6 +35,10 @@ PROFILE_MAX_PARAMS = 8                              # PISA_HIP_PROFILE_MAX_PARAM
 PROFILE_NOT_CONVERGED, PROFILE_BOUNDARY, PROFILE_NOT_POSDEF, PROFILE_START_OUTSIDE = 1, 2, 4, 8
 PROFILE_BAD_BOUNDS = 16                             # (the bounded entry points alone)
 PROFILE_HELD = 32                                   # (pisa_hip_profiled_hesse alone)
+POSTERIOR_MAX_WALKERS = 256                         # PISA_HIP_POSTERIOR_MAX_WALKERS
+# the launch shape of pisa_hip_posterior_sample (csrc/posterior.hip): lanes of a workgroup, problems it holds at most,
+# doubles of its LDS stage
+POSTERIOR_THREADS, POSTERIOR_MAX_PROBLEMS, POSTERIOR_STAGE = 128, 32, 4096
 FLUCT_TRUTH_EXHAUSTED = 1                          # PISA_HIP_FLUCT_TRUTH_EXHAUSTED (pisa_hip_fluctuate_linear)
 
 ERR_NEGATIVE = -5
@@ -360,6 +364,8 @@ _SIGS = {
     "pisa_hip_fluctuate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pisa_hip_fluctuate_linear": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pisa_hip_fluctuate_linear_mvn": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pisa_hip_fluctuate_linear_at": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pisa_hip_posterior_sample": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pisa_hip_bin_scale": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_int32, C.c_double, C.c_int64, C.c_void_p, C.c_void_p]),
     "pisa_hip_bin_sqrt": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "pisa_hip_lookup_indices": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]),

@@ -71,9 +71,16 @@ and, for `generator="device"` with `nuisance="prior"`,
 and, for `covariance=True`, `pulls` and `nuisance="fitted"`,
     hesse(kind, data, expected, response, eta [T, J], k (an int or [T] ints), sigma2, inv_prior_sigma, center,
           lower=, upper=) -> dict(cov [T, J, J], sigma [T, J], status [T])
+and, for `posterior_sample`,
+    posterior(kind, data, expected, response, x0 [P, W, J], n_steps, seed, t_of, k_of ([P] ints or None), sigma2,
+              inv_prior_sigma, center, lower, upper, stream, chain_id ([P] ints or None), first_step, keep_from, thin)
+        -> dict(chain [P, n_keep, W, J], logp [P, n_keep, W], accepted [P, W], end [P, W, J], status [P])
+and, for `generator="device"` with `truths=`,
+    draw_linear_at(mu [B], response [J, B], sigma [B] or None, method, eta [n_trials, J], seed, stream, first_trial=0)
+        -> dict(data [n_trials, B], eta [n_trials, J], clipped)
 so that everything around the kernels can run with a numpy restatement (tests/ensemble_cases.py,
 tests/fluctuate_cases.py, tests/fluctuate_method_cases.py, tests/profile_cases.py, tests/truth_cases.py,
-tests/hesse_cases.py, tests/observed_cases.py).
+tests/hesse_cases.py, tests/observed_cases.py, tests/posterior_cases.py).
 
 `nuisance="prior"` (`pseudo_data`, `feldman_cousins`; needs `response=`) makes pseudo-experiments with the systematics
 fluctuated: every trial draws the truths of the response's parameters from their priors and its data from the
@@ -91,8 +98,17 @@ trial -- the generator of "prior" with every scale 0 and the shift eta_obs[k].  
 trial's truths from the fit's Gaussian N(eta_obs[k], cov_obs[k]) truncated to the response's box: the truths are
 CORRELATED, so the whole vector is drawn and rejected at once (`fl_truth_factor`, `fl_truth_mvn` of
 csrc/fluctuate_device.hpp; `kernels.fluctuate_linear_mvn`), and a coordinate the fit holds on a bound (a zero row and
-column of cov_obs[k]) stays on it.  A true posterior (anything but the fit's Gaussian) is not built, and
-`nuisance="posterior"` stays an unknown name.
+column of cov_obs[k]) stays on it.
+
+The true posterior of the displacements -- skewed at few counts, flat inside a box, free to move where the fit sits on
+a bound, none of which the fit's Gaussian can be -- is sampled by `posterior_sample`: a Goodman-Weare stretch-move
+ensemble sampler, one chain ensemble per grid point and every step of every point in ONE launch (csrc/posterior.hip,
+`kernels.posterior_sample`; DESIGN.md §4, "Trial ensembles: the nuisance posterior") -> a `PosteriorSample` with the
+samples, their integrated autocorrelation time (`autocorr_time`) and credible intervals.  Pseudo-experiments at such
+samples enter through `truths=` of `pseudo_data` and `feldman_cousins` (a `PosteriorSample`, or rows of displacements
+of the caller's own): trial number n is generated at row n of the true point's truths, the posterior-predictive
+ensemble.  `nuisance="posterior"` stays an unknown name: the posterior lives in `posterior_sample` and `truths=`, and
+the reference's full-model `MCMC_sampling` (analysis/bayesian_analysis.py: templates re-made per walker) is not this.
 """
 import math
 
@@ -102,7 +118,8 @@ from pisa_amd.core.map import FLUCTUATE_METHODS
 from pisa_amd.utils.comparisons import ALLCLOSE_KW
 
 __all__ = ["METRICS", "GENERATORS", "FLUCTUATE_METHODS", "DeviceSolver", "TemplateGrid", "NuisanceResponse", "grid_points", "pseudo_data",
-           "metric_matrix", "delta_metric", "pulls", "critical_values", "feldman_cousins", "accepted", "NUISANCE", "fit_observed"]
+           "metric_matrix", "delta_metric", "pulls", "critical_values", "feldman_cousins", "accepted", "NUISANCE", "fit_observed",
+           "posterior_sample", "PosteriorSample", "autocorr_time"]
 
 # kernels.METRIC_KIND, then kernels.ENSEMBLE_MC_KINDS: the metrics that account for finite MC statistics, which read
 # the templates' sumw2 and have no profiled form
@@ -216,6 +233,37 @@ class DeviceSolver:
         sigma = None if sigma is None else self._up(sigma).reshape(-1)
         return K.fluctuate_linear_mvn(self._up(mu).reshape(-1), self._up(response), n_trials, seed, mean, cov, lower,
                                       upper, method=method, sigma=sigma, stream=stream, first_trial=first_trial)
+
+    def draw_linear_at(self, mu, response, sigma, method, eta, seed, stream, first_trial=0):
+        """`draw_linear` at given truths: eta [n_trials, J], row t the truths of trial number first_trial + t; nothing
+        is drawn for them (`kernels.fluctuate_linear_at`) -> dict(data [n_trials, B], eta, clipped)"""
+        from pisa_amd import kernels as K
+
+        sigma = None if sigma is None else self._up(sigma).reshape(-1)
+        return K.fluctuate_linear_at(self._up(mu).reshape(-1), self._up(response), self._up(eta), seed, method=method,
+                                     sigma=sigma, stream=stream, first_trial=first_trial)
+
+    def posterior(self, kind, data, expected, response, x0, n_steps, seed, t_of=None, k_of=None, sigma2=None,
+                  inv_prior_sigma=None, center=None, lower=None, upper=None, stream=0, chain_id=None, first_step=0,
+                  keep_from=0, thin=1):
+        """dict(chain [P, n_keep, W, J], logp [P, n_keep, W], accepted [P, W], end [P, W, J], status [P]): the
+        stretch-move chains of P problems from the starts x0 [P, W, J] (`kernels.posterior_sample`); t_of, k_of and
+        chain_id: [P] ints or None"""
+        import torch
+
+        from pisa_amd import kernels as K
+
+        data, expected, response, x0, sigma2, ips, center, lower, upper = [self._up(a) for a in (
+            data, expected, response, x0, sigma2, inv_prior_sigma, center, lower, upper)]
+
+        def ints(a, dtype):
+            if a is None or isinstance(a, torch.Tensor):
+                return a
+            return torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64)).to(device=data.device, dtype=dtype)
+
+        return K.posterior_sample(kind, data, expected, response, x0, n_steps, seed, ints(t_of, torch.int32),
+                                  ints(k_of, torch.int32), sigma2, ips, center, lower, upper, stream,
+                                  ints(chain_id, torch.int64), first_step, keep_from, thin)
 
 
 def _rescaled(param, value):
@@ -879,8 +927,83 @@ def _observed_data(grid, k, n_trials, seed_or_rs, generator, solver, method, res
     return data, truth
 
 
+def _check_truths(response, grid, solver, generator, method, metric, nuisance, observed, what):
+    """`truths=` needs a response of this grid, a metric with a profiled form, a method whose mean may move per trial
+    and, for the device generator, a solver with `draw_linear_at`; it generates at GIVEN nuisance values, so the modes
+    that choose them (`nuisance=`, `observed=`) are refused beside it"""
+    if generator not in GENERATORS:
+        raise ValueError("ensemble: generator '%s' not among %s" % (generator, list(GENERATORS)))
+    if nuisance != "fixed" or observed is not None:
+        raise ValueError("%s: truths= gives every trial's nuisance values itself; leave nuisance at 'fixed' and "
+                         "observed= at None" % what)
+    if response is None:
+        raise ValueError("%s: truths= needs response=, the linear response the truths displace" % what)
+    if metric in _MC_METRICS:
+        raise ValueError("%s: truths= is not available for '%s' (response= has no form for the MC-uncertainty "
+                         "metrics)" % (what, metric))
+    if method == "scaled_poisson":
+        raise ValueError("%s: truths= has no scaled_poisson draws (the method's row rules compare a row's variance "
+                         "with its mean, which moves per trial)" % what)
+    if generator == "device" and not hasattr(solver, "draw_linear_at"):
+        raise ValueError("ensemble: generator='device' with truths= needs a solver with draw_linear_at(mu, response, "
+                         "sigma, method, eta, seed, stream, first_trial); %s has none" % type(solver).__name__)
+    shape = tuple(response.response.shape)
+    if shape[-1] != grid.n_bins or (len(shape) == 3 and shape[0] != len(grid)):
+        raise ValueError("%s: the response does not belong to this grid (%s against %d points, %d bins)"
+                         % (what, shape, len(grid), grid.n_bins))
+
+
+def _truth_rows(truths, k, n_j, first, n, what):
+    """rows [first, first + n) of the truths of point k: `truths` a `PosteriorSample`, a mapping from point index to
+    [n, J], or (`pseudo_data`) one [n, J] array"""
+    sample = truths if isinstance(truths, PosteriorSample) else None
+    if sample is not None:
+        if k not in sample.points:
+            raise ValueError("%s: the posterior sample holds the points %s, not point %d" % (what, sample.points, k))
+        rows = sample.eta[sample.points.index(k)]
+    elif hasattr(truths, "keys"):
+        if k not in truths:
+            raise ValueError("%s: truths= holds no rows for point %d" % (what, k))
+        rows = truths[k]
+    else:
+        rows = truths
+    rows = np.asarray(_host(rows), dtype=np.float64)
+    if rows.ndim != 2 or rows.shape[1] != n_j:
+        raise ValueError("%s: the truths of point %d are [n, %d] displacements, got %s" % (what, k, n_j, rows.shape))
+    if first + n > rows.shape[0]:
+        missing = first + n - rows.shape[0]
+        if sample is not None:
+            steps = -(-missing // sample.n_walkers) * sample.thin
+            raise ValueError("%s: %d trials at point %d and %d rows of truths: the sample needs %d steps more (%d rows "
+                             "at %d walkers, thin %d)" % (what, first + n, k, rows.shape[0], steps, missing,
+                                                          sample.n_walkers, sample.thin))
+        raise ValueError("%s: %d trials at point %d and %d rows of truths: %d rows more are needed"
+                         % (what, first + n, k, rows.shape[0], missing))
+    rows = np.ascontiguousarray(rows[first:first + n])
+    if np.isnan(rows).any():
+        raise ValueError("%s: the truths of point %d hold a NaN (a posterior sample whose chains did not run?)"
+                         % (what, k))
+    return rows
+
+
+def _truths_data(grid, k, rows, seed_or_rs, generator, solver, method, response, first_trial=0):
+    """data [n, B] at the truths `rows` [n, J] of the trials first_trial ... at point k: module docstring"""
+    R = _truth_priors(response, k)[0]
+    sigma = _sigma_row(grid, k, method)
+    if generator != "host":
+        return solver.draw_linear_at(grid.hist[k], R, sigma, method, rows, seed_or_rs, stream=k,
+                                     first_trial=first_trial)["data"]
+    rs = seed_or_rs
+    mu0 = np.asarray(grid.host("hist")[k], dtype=np.float64).ravel()
+    R = _host(R).astype(np.float64)
+    data = np.empty((rows.shape[0], mu0.size))
+    for t in range(data.shape[0]):
+        data[t] = _host_row(_linear_mean(mu0, R, rows[t]), sigma, method, rs)
+    return data
+
+
 def pseudo_data(grid, k, n_trials, random_state=None, generator="host", solver=None, method="poisson", response=None,
-                nuisance="fixed", return_truth=False, observed=None):
+                nuisance="fixed", return_truth=False, observed=None, truths=None):
     """[n_trials, B] pseudo-data of template k by `method` (one of `FLUCTUATE_METHODS`; every method but "poisson"
     reads sigma = sqrt(grid.sumw2[k]), and "scaled_poisson" applies the reference's row rules to it first: module
     docstring).  With another method than "poisson" the host generator is the loop of `Map.fluctuate(method,
@@ -912,8 +1035,28 @@ def pseudo_data(grid, k, n_trials, random_state=None, generator="host", solver=N
     generator="host": per attempt one rs.standard_normal() per live coordinate k in ascending k, x_j = eta_obs[k, j] +
     L[j, 0] z_0 + ... + L[j, j] z_j with the Cholesky factor L of cov_obs[k], until every coordinate is inside the
     box, then the method's own scipy calls.  return_truth=True returns (data, eta_true [n_trials, J]: the
-    displacements from the point's values the fit's eta estimates; None for "fixed")."""
+    displacements from the point's values the fit's eta estimates; None for "fixed").
+    truths= (with `response`; nuisance left at "fixed", no `observed`): a `PosteriorSample` of `posterior_sample` that
+    holds point k, or [n, J] displacements of the caller's own.  Trial number n is generated at row n of the truths:
+    by `method` from hist[k] + sum_j response[k, j] eta_n[j], a negative mean taken as 0.  generator="device":
+    `solver.draw_linear_at` (`kernels.fluctuate_linear_at`), stream k; generator="host": `_linear_mean` and the
+    method's own scipy calls on the one RandomState.  Fewer rows than trials, a NaN row, "scaled_poisson" and the
+    MC-uncertainty metrics are refused; return_truth=True returns the rows used.  With every row equal to
+    eta_obs[k] the data are those of nuisance="profiled"."""
     method = _check_method(method, grid)
+    if truths is not None:
+        solver_ = (DeviceSolver() if solver is None else solver) if generator != "host" else solver
+        _check_truths(response, grid, solver_, generator, method, grid.metric, nuisance, observed, "pseudo_data")
+        if not 0 <= int(k) < len(grid):
+            raise ValueError("pseudo_data: point %s outside the grid's %d points" % (k, len(grid)))
+        rows = _truth_rows(truths, int(k), len(response.names), 0, int(n_trials), "pseudo_data")
+        if generator == "host":
+            source = random_state if isinstance(random_state, np.random.RandomState) else np.random.RandomState(
+                random_state)
+        else:
+            source = _base_seed(random_state)
+        data = _truths_data(grid, int(k), rows, source, generator, solver_, method, response)
+        return (data, rows) if return_truth else data
     if nuisance != "fixed":
         solver_ = (DeviceSolver() if solver is None else solver) if generator != "host" else solver
         _check_nuisance(nuisance, response, grid, solver_, generator, method, grid.metric, "pseudo_data", observed)
@@ -1102,7 +1245,7 @@ def _base_seed(random_state):
 
 def feldman_cousins(grid, metric, n_trials, cl=(0.6827, 0.90), random_state=None, true_points=None, solver=None,
                     generator="host", chunk_bytes=CHUNK_BYTES, response=None, method="poisson",
-                    nuisance="fixed", observed=None):
+                    nuisance="fixed", observed=None, truths=None):
     """Critical values of the Feldman-Cousins ordering on the grid: for every true point k0 (default: all), n_trials
     pseudo-data maps of template k0, their `delta_metric` at k0 and `critical_values` -> crit [len(true_points),
     len(cl)].  seed: `random_state`, or one draw from it if it is a RandomState.
@@ -1122,14 +1265,22 @@ def feldman_cousins(grid, metric, n_trials, cl=(0.6827, 0.90), random_state=None
     at all points (`fit_observed`) and the pseudo-data of true point k0 are those of `pseudo_data(..., nuisance=...,
     observed=observed)` -- generated at the displacements fitted to the observed map given k0 (the profile
     construction), or at truths drawn from that fit's Gaussian --, in the chunks, seeds and streams of "prior"; info
-    gains eta_observed [len(true_points), J] and, for "fitted", cov_observed [len(true_points), J, J]."""
+    gains eta_observed [len(true_points), J] and, for "fitted", cov_observed [len(true_points), J, J].
+    truths= (needs `response`; nuisance left at "fixed", no `observed`): a `PosteriorSample` or a mapping from point
+    index to [n, J] displacements; trial number n of true point k0 is generated at row n of k0's truths
+    (`pseudo_data(..., truths=)`), the distances are profiled over the response as for "prior", and the device
+    generator draws in the same chunks through the solver's `draw_linear_at`: the result does not depend on the
+    chunks.  info gains truths_used [len(true_points)], the rows read per true point."""
     _check_metric(metric)
     if n_trials < 1:
         raise ValueError("feldman_cousins: n_trials >= 1")
     solver = DeviceSolver() if solver is None else solver
     method = _check_method(method, grid)
-    _check_nuisance(nuisance, response, grid, solver, generator, method, metric, "feldman_cousins", observed)
-    if nuisance == "fixed":
+    if truths is not None:
+        _check_truths(response, grid, solver, generator, method, metric, nuisance, observed, "feldman_cousins")
+    else:
+        _check_nuisance(nuisance, response, grid, solver, generator, method, metric, "feldman_cousins", observed)
+    if nuisance == "fixed" and truths is None:
         _check_generator(generator, solver, method)
     if response is not None:
         _check_response(response, grid, solver, "feldman_cousins", metric)
@@ -1153,9 +1304,21 @@ def feldman_cousins(grid, metric, n_trials, cl=(0.6827, 0.90), random_state=None
         eta_obs, cov_obs = _observed_truths(observed, grid, metric, response, solver, nuisance, list(points),
                                             "feldman_cousins")
     rows = max(1, int(chunk_bytes) // (8 * grid.n_bins))
+    if truths is not None:
+        for k0 in points:      # (every point's rows are there before the first draw)
+            _truth_rows(truths, k0, len(response.names), 0, n_trials, "feldman_cousins")
     for i, k0 in enumerate(points):
         flagged.append(0)
-        if nuisance != "fixed":
+        if truths is not None:
+            parts = []
+            source = np.random.RandomState([seed, k0]) if generator == "host" else seed
+            for first in range(0, n_trials, n_trials if generator == "host" else rows):
+                n = n_trials if generator == "host" else min(rows, n_trials - first)
+                at = _truth_rows(truths, k0, len(response.names), first, n, "feldman_cousins")
+                parts.append(distances(_truths_data(grid, k0, at, source, generator, solver, method, response, first),
+                                       k0))
+            delta = np.concatenate(parts)
+        elif nuisance != "fixed":
             parts = []
             source = np.random.RandomState([seed, k0]) if generator == "host" else seed
             for first in range(0, n_trials, n_trials if generator == "host" else rows):
@@ -1181,6 +1344,8 @@ def feldman_cousins(grid, metric, n_trials, cl=(0.6827, 0.90), random_state=None
     if response is None:
         return crit
     info = dict(flagged=np.array(flagged, dtype=np.int64))
+    if truths is not None:
+        info["truths_used"] = np.full(len(points), n_trials, dtype=np.int64)
     if nuisance in _OBSERVED:
         info["eta_observed"] = eta_obs[list(points)]
         if cov_obs is not None:
@@ -1202,3 +1367,189 @@ def accepted(data_map, grid, metric, crit, solver=None, response=None):
     m = _host(metric_matrix(rows, grid, metric, True, solver, response))[0]
     delta = m.max() - m if metric in _MAXIMISED else m - m.min()
     return delta <= crit
+
+
+# ------------------------------------------------------------------------------------- the nuisance posterior
+_START_STREAM = 0x40000000     # stream of the starts of point k: _START_STREAM + k (the data streams are the points')
+_TAU_LENGTHS = 50              # a tau estimate is reliable from this many tau of steps on
+
+
+def autocorr_time(series, c=5.0):
+    """The integrated autocorrelation time of a series [n] (or of every column of [n, J]) in its own steps, as emcee
+    defines it: the autocorrelation function by FFT, tau(M) = 1 + 2 sum_{t=1..M} rho(t), and Sokal's window, the
+    smallest M with M >= c tau(M) (c = 5).  A constant series gives NaN."""
+    x = np.asarray(series, dtype=np.float64)
+    if x.ndim == 2:
+        return np.array([autocorr_time(x[:, j], c) for j in range(x.shape[1])])
+    n = x.size
+    if n < 2 or not np.isfinite(x).all() or np.ptp(x) == 0.0:
+        return float("nan")
+    size = 1 << int(math.ceil(math.log2(2 * n)))
+    f = np.fft.rfft(x - x.mean(), n=size)
+    acf = np.fft.irfft(f * np.conjugate(f))[:n]
+    acf = acf / acf[0]
+    taus = 2.0 * np.cumsum(acf) - 1.0
+    m = np.arange(n) < c * taus
+    window = int(np.argmin(m)) if not m.all() else n - 1
+    return float(taus[window])
+
+
+class PosteriorSample:
+    """What `posterior_sample` returns: `points` (the grid points sampled, a list), `names`, and per point i
+    eta [P, n_keep * W, J] the displacements, all walkers of the first kept step first (the order of emcee's
+    flatchain); values = the parameters' values at the point + eta (None for a response without `values`); logp
+    [P, n_keep * W]; acceptance [P], the share of accepted proposals of the kept chain; tau [P, J] the integrated
+    autocorrelation time of the walker-mean series in steps; reliable [P]: the chain that tau was estimated on is at
+    least 50 tau long; status [P], the sampler's flags (a flagged point is NaN); thin, n_burn, seed, n_walkers."""
+
+    def __init__(self, points, names, eta, values, logp, acceptance, tau, reliable, status, thin, n_burn, seed,
+                 n_walkers):
+        self.points, self.names = list(points), tuple(names)
+        self.eta, self.values, self.logp = eta, values, logp
+        self.acceptance, self.tau, self.reliable, self.status = acceptance, tau, reliable, status
+        self.thin, self.n_burn, self.seed, self.n_walkers = int(thin), int(n_burn), int(seed), int(n_walkers)
+
+    def __len__(self):
+        return int(self.eta.shape[1])
+
+    def mean(self):
+        """[P, J]: the posterior means of the displacements"""
+        return self.eta.mean(axis=1)
+
+    def cov(self):
+        """[P, J, J]: the sample covariance of the displacements"""
+        d = self.eta - self.eta.mean(axis=1, keepdims=True)
+        return np.einsum("pni,pnj->pij", d, d) / max(self.eta.shape[1] - 1, 1)
+
+    def interval(self, cl=0.6827):
+        """(lower, upper) [P, J]: the equal-tailed credible interval of every displacement at the level cl"""
+        if not 0.0 < cl < 1.0:
+            raise ValueError("PosteriorSample.interval: 0 < cl < 1")
+        q = np.quantile(self.eta, [0.5 * (1.0 - cl), 0.5 * (1.0 + cl)], axis=1)
+        return q[0], q[1]
+
+
+def _start_scales(response, k, cov, lower, upper):
+    """the spread of the starts of point k per coordinate: sqrt(cov_jj) where that is > 0, else the prior's stddev,
+    else an eighth of a finite box; 0 for a pinned coordinate; never more than a quarter of a finite box, so that the
+    box holds at least half of the normal the starts are drawn from wherever its centre lies"""
+    n_j = len(response.names)
+    lo = np.full(n_j, -np.inf) if lower is None else lower
+    hi = np.full(n_j, np.inf) if upper is None else upper
+    ips = np.asarray(response.inv_prior_sigma, dtype=np.float64)
+    scale = np.zeros(n_j)
+    for j in range(n_j):
+        width = hi[j] - lo[j]
+        if width == 0.0:
+            continue
+        var = float(cov[j, j]) if cov is not None else float("nan")
+        if var > 0.0:
+            scale[j] = math.sqrt(var)
+        elif ips[j] > 0.0:
+            scale[j] = 1.0 / ips[j]
+        elif np.isfinite(width):
+            scale[j] = width / 8.0
+        else:
+            raise ValueError("posterior_sample: no scale for the starts of '%s' at point %d: the fit gives no variance, "
+                             "and the parameter has neither a prior nor a finite range" % (response.names[j], k))
+        if np.isfinite(width):
+            scale[j] = min(scale[j], width / 4.0)
+    return scale
+
+
+def posterior_sample(observed, grid, metric, response, points=None, n_keep=200, n_walkers=128, thin=None, n_burn=None,
+                     pilot_steps=2000, random_state=None, solver=None):
+    """Samples of p(eta | observed map, point k) for the points `points` of the grid (default: all): the posterior of
+    the response's displacements under the metric's likelihood -- ln p = -Phi (llh, poisson_llh) or -Phi / 2 (chi2,
+    mod_chi2) of the profiled fit's objective Phi, Gaussian priors included, flat inside the response's box and on
+    the domain where the linearised template is positive -- by the stretch-move ensemble sampler of csrc/posterior.hip,
+    every point a chain ensemble of `n_walkers` walkers, all of them in one launch (`solver.posterior`; DESIGN.md §4,
+    "Trial ensembles: the nuisance posterior") -> a `PosteriorSample` of n_keep * n_walkers rows per point.
+    Start: the observed map is fitted once at all points (`fit_observed(..., covariance=True)`; a point whose fit
+    carries a flag other than a held coordinate is refused), and the walkers of point k start at independent normals
+    about eta_obs[k] truncated to the box (`solver.draw_linear`, stream 0x40000000 + k, the data discarded) with the
+    spreads of `_start_scales`.  The chains of point k read the random numbers of (seed, stream 0, chain id k), so a
+    subset of points reproduces the full run's rows.
+    Lengths: with `thin` and `n_burn` given, n_burn steps are dropped and every thin-th of the next n_keep * thin kept.
+    Where either is None a pilot of `pilot_steps` steps is run first; it is (part of) the burn-in, the chain goes on
+    from its end (the sampler's continuation property), and thin = ceil(max tau) of the pilot's second half.  tau is
+    `autocorr_time` of the walker-mean series per parameter; where the steps an estimate rests on are fewer than 50
+    tau a warning is logged and `reliable` is False.  seed: `random_state`, or one draw from it if a RandomState."""
+    from pisa_amd.utils.log import logging
+
+    _check_metric(metric)
+    solver = DeviceSolver() if solver is None else solver
+    if response is None:
+        raise ValueError("posterior_sample: needs response=, the linear response whose parameters are sampled")
+    _check_response(response, grid, solver, "posterior_sample", metric)
+    for name in ("posterior", "draw_linear", "hesse"):
+        if not hasattr(solver, name):
+            raise ValueError("ensemble: posterior_sample needs a solver with %s; %s has none"
+                             % (name, type(solver).__name__))
+    points = list(range(len(grid))) if points is None else [int(k) for k in points]
+    for k in points:
+        if not 0 <= k < len(grid):
+            raise ValueError("posterior_sample: point %s outside the grid's %d points" % (k, len(grid)))
+    n_j, n_w, n_keep = len(response.names), int(n_walkers), int(n_keep)
+    if n_w % 2 or not max(2, 2 * n_j) <= n_w <= 256:
+        raise ValueError("posterior_sample: %d walkers; an even number from %d (twice the parameters) to 256"
+                         % (n_w, max(2, 2 * n_j)))
+    if n_keep < 1 or (thin is not None and int(thin) < 1) or (n_burn is not None and int(n_burn) < 0) or (
+            (thin is None or n_burn is None) and int(pilot_steps) < 4):
+        raise ValueError("posterior_sample: n_keep >= 1, thin >= 1, n_burn >= 0 and pilot_steps >= 4")
+    seed = _base_seed(random_state)
+    fit = fit_observed(observed, grid, metric, response, solver, covariance=True)
+    bad = [k for k in points if int(fit["status"][k]) & ~_PROFILE_HELD]
+    if bad:
+        raise ValueError("posterior_sample: the fit of the observed map carries a status flag at the points %s (status "
+                         "%s)" % (bad, [int(fit["status"][k]) for k in bad]))
+    x0 = np.empty((len(points), n_w, n_j))
+    for i, k in enumerate(points):
+        R, _, _, lower, upper = _truth_priors(response, k)
+        cov = fit["cov"][k] if not np.isnan(fit["cov"][k]).any() else None
+        scale = _start_scales(response, k, cov, lower, upper)
+        out = solver.draw_linear(grid.hist[k], R, None, "poisson", n_w, seed, stream=_START_STREAM + k, scale=scale,
+                                 shift=np.ascontiguousarray(fit["eta"][k], dtype=np.float64), lower=lower, upper=upper)
+        x0[i] = _host(out["eta"])
+    rows = _data_rows(observed)
+    kw = dict(t_of=np.zeros(len(points), dtype=np.int32), k_of=np.array(points, dtype=np.int32),
+              sigma2=grid.sigma2_for(metric), inv_prior_sigma=response.inv_prior_sigma, center=response.center,
+              stream=0, chain_id=np.array(points, dtype=np.int64), **response.bounds())
+
+    def tau_of(chain, step):
+        """[P, J] tau in steps of the walker-mean series of chain [P, n, W, J] whose rows are `step` steps apart, and
+        which estimates rest on at least 50 tau"""
+        tau = np.array([autocorr_time(chain[i].mean(axis=1)) for i in range(chain.shape[0])]).reshape(-1, n_j) * step
+        with np.errstate(invalid="ignore"):
+            ok = ~(chain.shape[1] * step < _TAU_LENGTHS * tau).any(axis=1)
+        return tau, ok
+
+    first = 0
+    reliable = np.ones(len(points), dtype=bool)
+    if thin is None or n_burn is None:
+        pilot = solver.posterior(metric, rows, grid.hist, response.response, x0, int(pilot_steps), seed,
+                                 first_step=0, keep_from=int(pilot_steps) // 2, thin=1, **kw)
+        tau_pilot, reliable = tau_of(_host(pilot["chain"]), 1)
+        if thin is None:
+            worst = np.nanmax(tau_pilot) if np.isfinite(tau_pilot).any() else 1.0
+            thin = max(1, int(math.ceil(worst)))
+        x0, first = _host(pilot["end"]), int(pilot_steps)
+        n_burn = max(first, int(n_burn or 0))
+    thin, n_burn = int(thin), int(n_burn)
+    n_steps = (n_burn - first) + n_keep * thin
+    out = solver.posterior(metric, rows, grid.hist, response.response, x0, n_steps, seed, first_step=first,
+                           keep_from=n_burn + thin - 1, thin=thin, **kw)
+    chain, logp, status = _host(out["chain"]), _host(out["logp"]), _host(out["status"])
+    tau, ok = tau_of(chain, thin)
+    reliable = reliable & ok
+    for i, k in enumerate(points):
+        if status[i]:
+            logging.warning("posterior_sample: the chains of point %d did not run (status %d)", k, int(status[i]))
+        elif not reliable[i]:
+            logging.warning("posterior_sample: point %d: tau = %s steps is estimated on fewer than %d tau; run longer",
+                            k, np.round(tau[i], 1), _TAU_LENGTHS)
+    eta = chain.reshape(len(points), n_keep * n_w, n_j)
+    values = None if response.values is None else np.asarray(response.values)[points][:, None, :] + eta
+    acceptance = _host(out["accepted"]).sum(axis=1) / float(n_w * n_steps)
+    return PosteriorSample(points, response.names, eta, values, logp.reshape(len(points), n_keep * n_w), acceptance,
+                           tau, reliable & (status == 0), status, thin, n_burn, seed, n_w)

@@ -22,6 +22,8 @@
 // N(mean, cov) inside the box by rejection of the whole vector (fl_truth_factor, fl_truth_mvn; DESIGN.md §4,
 // "pseudo-data at nuisances fitted to the observed data"; tests/observed_cases.py).  truth_mvn_kernel, one lane per
 // trial, takes the place of truth_kernel; linear_kernel runs unchanged on its truths.
+// pisa_hip_fluctuate_linear_at has no truth launch at all: the truths are an input [n_trials][J] on the device (rows
+// of a posterior sample of posterior.hip, for one), and linear_kernel runs unchanged on them.
 #include "common.hpp"
 #include "fluctuate_device.hpp"
 
@@ -180,6 +182,23 @@ PISA_API int pisa_hip_fluctuate_linear(const double *d_mu, const double *d_sigma
     return dispatch_int<FL_POISSON, FL_GAUSS, FL_GAUSS_POISSON>(method, [&](auto m) {
         return linear_launch<decltype(m)::value>(d_mu, d_sigma, d_response, n_params, n_bins, n_trials, seed,
                                                  stream_id, first_trial, d_out, d_eta_true, d_status, stream);
+    });
+}
+
+// the call above without the truth launch: the truths are the caller's, d_eta [n_trials][J] on the device
+PISA_API int pisa_hip_fluctuate_linear_at(const double *d_mu, const double *d_sigma, const double *d_response,
+                                          int32_t n_params, const double *d_eta, int32_t method, int64_t n_bins,
+                                          int64_t n_trials, uint64_t seed, uint32_t stream_id, uint32_t first_trial,
+                                          double *d_out, int32_t *d_status, void *stream) {
+    if (!d_mu || !d_response || !d_out || !d_eta || !d_status) return PISA_HIP_ERR_INVALID;
+    if (n_params < 1 || n_params > FLL_MAX_PARAMS) return PISA_HIP_ERR_INVALID;
+    if (n_bins < 1 || n_trials < 1 || n_bins > 0x7FFFFFFF || n_trials > 0x7FFFFFFF) return PISA_HIP_ERR_INVALID;
+    if ((int64_t)first_trial + n_trials > ((int64_t)1 << 32)) return PISA_HIP_ERR_INVALID;
+    if (method != FL_POISSON && method != FL_GAUSS && method != FL_GAUSS_POISSON) return PISA_HIP_ERR_INVALID;
+    if (method != FL_POISSON && !d_sigma) return PISA_HIP_ERR_INVALID;
+    return dispatch_int<FL_POISSON, FL_GAUSS, FL_GAUSS_POISSON>(method, [&](auto m) {
+        return linear_launch<decltype(m)::value>(d_mu, d_sigma, d_response, n_params, n_bins, n_trials, seed,
+                                                 stream_id, first_trial, d_out, d_eta, d_status, stream);
     });
 }
 

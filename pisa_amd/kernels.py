@@ -899,6 +899,37 @@ def fluctuate_linear_mvn(mu, response, n_trials, seed, mean, cov, lower=None, up
     return dict(data=out, eta=eta, clipped=clipped & 0xFFFFFFFF)
 
 
+def fluctuate_linear_at(mu, response, eta, seed, method="poisson", sigma=None, stream=0, first_trial=0):
+    """`fluctuate_linear` at truths the caller gives (`pisa_hip_fluctuate_linear_at`): eta [n_trials, J] float64 device
+    tensor, row t the truths of trial number first_trial + t (rows of a posterior sample of `posterior_sample`, for
+    one); nothing is drawn for them.  -> dict(data [n_trials, B], eta: the tensor that was read, clipped), with the
+    conventions of `fluctuate_linear`.  With every row equal to `shift` the data are those of `fluctuate_linear` with
+    every scale 0, bit for bit.  A NaN truth gives NaN data.  "scaled_poisson" is refused (ValueError)."""
+    name = fluctuate_method(method)
+    if name == "scaled_poisson":
+        raise ValueError("fluctuate_linear_at: no scaled_poisson draws from a mean that moves per trial (its row rules "
+                         "compare a row's variance with its mean)")
+    if response.dim() != 2 or response.dtype != F8 or mu.dim() != 1 or response.shape[1] != mu.shape[0] or (
+            response.device != mu.device):
+        raise ValueError("fluctuate_linear_at: response is float64 [n_params, n_bins] on mu's device")
+    n_j = response.shape[0]
+    if not 1 <= n_j <= _lib.PROFILE_MAX_PARAMS:
+        raise ValueError("fluctuate_linear_at: %d nuisance parameters, 1 to %d are taken"
+                         % (n_j, _lib.PROFILE_MAX_PARAMS))
+    if eta.dim() != 2 or eta.dtype != F8 or eta.shape[1] != n_j or eta.device != mu.device:
+        raise ValueError("fluctuate_linear_at: eta is float64 [n_trials, n_params] on mu's device")
+    mu, sigma, n_bins, n_trials, seed, stream, first_trial, out = _draw_args(
+        "fluctuate_linear_at", mu, sigma, name, eta.shape[0], seed, stream, first_trial, None)
+    response, eta = response.contiguous(), eta.contiguous()
+    status = torch.zeros(2, dtype=torch.int32, device=mu.device)
+    _lib.check(_lib.lib().pisa_hip_fluctuate_linear_at(
+        _ptr(mu), _ptr(sigma), _ptr(response), n_j, _ptr(eta), FLUCTUATE_METHOD[name], n_bins, n_trials, seed, stream,
+        first_trial, _ptr(out), _ptr(status), _stream()))
+    word, clipped = (int(x) for x in status.cpu().numpy())
+    _lib.check(word)
+    return dict(data=out, eta=eta, clipped=clipped & 0xFFFFFFFF)
+
+
 def _profile_args(what, kind, data, expected, response, sigma2, inv_prior_sigma, center, max_iter):
     if kind in ENSEMBLE_MC_KINDS:
         raise ValueError("%s: '%s' has no profiled form (its per-bin function is not convex in the response)"
@@ -1062,6 +1093,96 @@ def profiled_hesse(kind, data, expected, response, eta, k, sigma2=None, inv_prio
     _with_status(None, dev, launch)
     sigma = bin_sqrt(torch.diagonal(cov, dim1=1, dim2=2).contiguous())
     return dict(cov=cov, sigma=sigma, status=trial_status)
+
+
+def posterior_n_keep(first_step, n_steps, keep_from=0, thin=1):
+    """the number of kept steps of `posterior_sample`: the s of [first_step, first_step + n_steps) with s >= keep_from
+    and (s - keep_from) % thin == 0"""
+    first_step, n_steps, keep_from, thin = int(first_step), int(n_steps), int(keep_from), int(thin)
+    if thin < 1:
+        raise ValueError("posterior_sample: thin >= 1")
+    s0 = keep_from if first_step <= keep_from else keep_from + -(-(first_step - keep_from) // thin) * thin
+    return max(0, -(-(first_step + n_steps - s0) // thin))
+
+
+def posterior_layout(kind, n_params, n_walkers):
+    """how `pisa_hip_posterior_sample` places an ensemble (csrc/posterior.hip) -> dict(problems: the problems of one
+    workgroup; stage_bins: the most bins whose rows it keeps in LDS -- longer rows are streamed by every sweep).  The
+    results do not depend on either; tests pick their sizes by them."""
+    per = min(_lib.POSTERIOR_THREADS // (int(n_walkers) // 2), _lib.POSTERIOR_MAX_PROBLEMS)
+    rows = int(n_params) + 2 + (1 if kind == "mod_chi2" else 0)
+    return dict(problems=per, stage_bins=_lib.POSTERIOR_STAGE // (per * rows))
+
+
+def posterior_sample(kind, data, expected, response, x0, n_steps, seed, t_of=None, k_of=None, sigma2=None,
+                     inv_prior_sigma=None, center=None, lower=None, upper=None, stream=0, chain_id=None, first_step=0,
+                     keep_from=0, thin=1):
+    """Samples of the posterior of the linearised nuisance displacements, p(eta | data row, template row), by a
+    Goodman-Weare stretch-move ensemble sampler on the device (`pisa_hip_posterior_sample`; DESIGN.md §4, "Trial
+    ensembles: the nuisance posterior").  data [T, B], expected / sigma2 [K, B], response [K, J, B] or [J, B],
+    inv_prior_sigma [J], center [K, J], lower / upper [J] or [K, J]: the arguments of `profiled_metric_matrix`, and
+    ln p(eta) = -Phi(eta) (the llh kinds) or -Phi(eta) / 2 (the chi2 kinds) of its objective Phi, -inf outside the box
+    and outside the solver's domain.  x0 [P, W, J]: the starts of P problems of W walkers (W even, 2 J <= W <= 256);
+    problem p takes data row t_of[p] and template row k_of[p] (int32 device tensors [P]; None: p itself, or row 0
+    where there is one row only) and the random numbers of (seed, stream, chain_id[p]) (chain_id: int tensor [P];
+    None: p).  Steps first_step ... first_step + n_steps - 1 are taken; step s is kept iff s >= keep_from and
+    (s - keep_from) % thin == 0.
+    -> dict(chain [P, n_keep, W, J], logp [P, n_keep, W], accepted [P, W] int32, end [P, W, J], status [P] int32: 0,
+    `_lib.PROFILE_START_OUTSIDE` (a walker starts where ln p is -inf or NaN) or `_lib.PROFILE_BAD_BOUNDS`; a flagged
+    problem is NaN).  The bits of a problem depend on its rows, its start, (seed, stream, chain_id) and the step numbers
+    alone: a call continued from `end` with first_step advanced equals one longer call.  A negative datum or
+    expectation raises ValueError, a row index outside its array `_lib.PisaHipError`."""
+    what = "posterior_sample"
+    (data, expected, response, sigma2, ips, center, stride, n_t, n_k, n_bins, n_j) = _profile_args(
+        what, kind, data, expected, response, sigma2, inv_prior_sigma, center, 0)
+    b_stride = 0
+    if lower is not None or upper is not None:
+        lower, upper, b_stride = _bound_args(what, lower, upper, n_k, n_j)
+    dev = data.device
+    if x0.dim() != 3 or x0.dtype != F8 or x0.shape[2] != n_j or x0.device != dev:
+        raise ValueError("%s: x0 is float64 [n_problems, n_walkers, n_params] on the data's device" % what)
+    n_p, n_w = int(x0.shape[0]), int(x0.shape[1])
+    if n_w % 2 or not max(2, 2 * n_j) <= n_w <= _lib.POSTERIOR_MAX_WALKERS:
+        raise ValueError("%s: %d walkers; an even number from %d (twice the parameters) to %d"
+                         % (what, n_w, max(2, 2 * n_j), _lib.POSTERIOR_MAX_WALKERS))
+    x0 = x0.contiguous()
+    index = []
+    for name, idx, rows in (("t_of", t_of, n_t), ("k_of", k_of, n_k)):
+        if idx is None:
+            idx = torch.zeros(n_p, dtype=torch.int32, device=dev) if rows == 1 and n_p > 1 else None
+        elif idx.dtype != torch.int32 or tuple(idx.shape) != (n_p,) or idx.device != dev:
+            raise ValueError("%s: %s is an int32 tensor [n_problems] on the data's device" % (what, name))
+        index.append(None if idx is None else idx.contiguous())
+    if chain_id is not None:
+        if tuple(chain_id.shape) != (n_p,) or chain_id.device != dev or chain_id.is_floating_point():
+            raise ValueError("%s: chain_id is an integer tensor [n_problems] on the data's device" % what)
+        if n_p and (int(chain_id.min()) < 0 or int(chain_id.max()) >= 2 ** 32):
+            raise ValueError("%s: chain ids are in [0, 2^32)" % what)
+        # (the library reads 32-bit words: the low word of a little-endian int64 is the id)
+        chain_id = chain_id.to(torch.int64).contiguous().view(torch.int32)[::2].contiguous()
+    seed, stream = int(seed), int(stream)
+    first_step, n_steps, keep_from, thin = int(first_step), int(n_steps), int(keep_from), int(thin)
+    if not 0 <= seed < 2 ** 64 or not 0 <= stream < 2 ** 32:
+        raise ValueError("%s: the seed is in [0, 2^64) and stream in [0, 2^32)" % what)
+    if first_step < 0 or keep_from < 0 or n_steps < 1 or first_step + n_steps > 2 ** 32:
+        raise ValueError("%s: step numbers are in [0, 2^32), and at least one step is taken" % what)
+    n_keep = posterior_n_keep(first_step, n_steps, keep_from, thin)
+    chain = torch.empty((n_p, n_keep, n_w, n_j), dtype=F8, device=dev)
+    logp = torch.empty((n_p, n_keep, n_w), dtype=F8, device=dev)
+    accepted = torch.empty((n_p, n_w), dtype=torch.int32, device=dev)
+    end = torch.empty((n_p, n_w, n_j), dtype=F8, device=dev)
+    problem_status = torch.empty(n_p, dtype=torch.int32, device=dev)
+
+    def launch(status):
+        _lib.check(_lib.lib().pisa_hip_posterior_sample(
+            METRIC_KIND[kind], _ptr(data), _ptr(expected), _ptr(sigma2), _ptr(response), stride, _ptr(ips),
+            _ptr(center), _ptr(lower), _ptr(upper), b_stride, n_j, n_t, n_k, n_bins, n_p, _ptr(index[0]),
+            _ptr(index[1]), _ptr(chain_id), n_w, _ptr(x0), seed, stream, first_step, n_steps, keep_from, thin, n_keep,
+            _ptr(chain) if n_keep else None, _ptr(logp) if n_keep else None, _ptr(accepted), _ptr(end),
+            _ptr(problem_status), _ptr(status), _stream()))
+
+    _with_status(None, dev, launch)
+    return dict(chain=chain, logp=logp, accepted=accepted, end=end, status=problem_status)
 
 
 # --------------------------------------------------- generalized Poisson-gamma likelihood

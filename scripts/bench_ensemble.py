@@ -32,8 +32,13 @@
     and `kernels.fluctuate` of the same run, poisson and gauss+poisson; then one `feldman_cousins(generator="device")`
     with `nuisance="prior"`, "profiled" and "fitted" over the grid's points (wall time after a warm-up run).
 
+  * `--posterior` (alone: nothing else runs): the nuisance-posterior sampler `kernels.posterior_sample` at K = 64
+    points, W = 128 walkers, 128 bins, J = 4 parameters (llh, Gaussian priors, a box of +-1.5), 2000 steps of which
+    every 10th is kept, median of 5 launches, HIP events; the time per half step, the log-density sweeps per second
+    and the acceptance; then the same at W = 256 and at 4800 bins (rows streamed, not kept in LDS).
+
     python scripts/bench_ensemble.py [--reps 20] [--skip-e2e] [--skip-kernels] [--skip-draw] [--forms direct,product]
-                                     [--true-points N] [--generator host|device|both] [--e2e-reps 3] [--mc] [--truth] [--observed]
+                                     [--true-points N] [--generator host|device|both] [--e2e-reps 3] [--mc] [--truth] [--observed] [--posterior]
                                      [--metric llh] [--method poisson]
 """
 import argparse
@@ -311,6 +316,38 @@ def observed_lines(reps=5):
               flush=True)
 
 
+def posterior_lines(reps=5):
+    """one line per shape for `kernels.posterior_sample` (module docstring)"""
+    import torch
+
+    from pisa_amd import kernels as K
+
+    dev = K.device()
+    n_k, n_j, n_steps, thin = 64, 4, 2000, 10
+    for n_w, n_bins in ((128, 128), (256, 128), (128, 4800)):
+        E = _templates(n_k, n_bins)
+        x = np.linspace(0.0, 1.0, n_bins)
+        R = 0.1 * np.cos((np.arange(n_j)[None, :, None] + 1) * np.pi * x[None, None, :]) * E[:, None, :]
+        rs = np.random.RandomState(3)
+        D = rs.poisson(E[0]).astype(np.float64)[None, :]
+        x0 = 0.05 * rs.randn(n_k, n_w, n_j)
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)       # noqa: E731
+        args = ("llh", up(D), up(E), up(R), up(x0), n_steps, 7)
+        kw = dict(inv_prior_sigma=up(np.full(n_j, 2.0)), lower=up(np.full(n_j, -1.5)), upper=up(np.full(n_j, 1.5)),
+                  thin=thin, keep_from=thin - 1)
+        out = K.posterior_sample(*args, **kw)
+        assert not bool(out["status"].any())
+        t = _time(lambda: K.posterior_sample(*args, **kw), reps)
+        sweeps = n_k * n_w * n_steps
+        print(json.dumps(dict(kernel="posterior_sample", kind="llh", points=n_k, walkers=n_w, bins=n_bins, params=n_j,
+                              steps=n_steps, thin=thin, staged_in_lds=bool(n_bins <= K.posterior_layout("llh", n_j, n_w)[
+                                  "stage_bins"]), us_per_half_step=round(1e3 * t["ms_median"] / (2 * n_steps), 3),
+                              sweeps_per_s=round(sweeps / (1e-3 * t["ms_median"]), 1),
+                              ns_per_bin_and_sweep_of_a_wavefront=round(
+                                  1e6 * t["ms_median"] / (2 * n_steps * n_bins), 2),
+                              acceptance=round(float(out["accepted"].sum().item()) / sweeps, 3), **t)), flush=True)
+
+
 def mc_lines(reps=5):
     import torch
 
@@ -495,10 +532,15 @@ def main():
     ap.add_argument("--observed", action="store_true",
                     help="time fluctuate_linear_mvn against fluctuate_linear and feldman_cousins(nuisance='fitted') "
                          "against nuisance='prior', and nothing else")
+    ap.add_argument("--posterior", action="store_true",
+                    help="time the nuisance-posterior sampler (kernels.posterior_sample), and nothing else")
     args = ap.parse_args()
     import torch
 
     torch.cuda.set_device(0)
+    if args.posterior:
+        posterior_lines()
+        return
     if args.mc:
         mc_lines()
         return
