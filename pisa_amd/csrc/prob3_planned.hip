@@ -40,8 +40,9 @@ namespace pisa {
 //             A = sum_k phase_k Q_k from the record of the layer's density where it multiplies
 //             it (a pair belongs to one row: nothing is computed twice) -- the chain is
 //             multiplied from its middle outwards on both sides at once (see
-//             prob3_chain_kernel), wave 0 joins the waves' partial products (LDS), rotates to
-//             the flavour basis and stores P and the gather tables.
+//             prob3_chain_kernel), the row's first two waves join the waves' partial products
+//             (LDS), one side each, and the first rotates to the flavour basis and stores P and
+//             the gather tables.
 // The earlier split is kept as an option of the development library (PISA_HIP_PROB3_FUSED_AMP=0 at plan creation):
 //   stage AB  wave = (item of a few pairs of one density, sign, 64 energies): terms in registers,
 //             then the item's layer matrices -> amp[sign][pair][18][n_e]; stage C reads them.
@@ -157,9 +158,16 @@ __device__ __forceinline__ void mat_mul_fma(const mat3 &A, const mat3 &B, mat3 &
 // symmetric paths through the Earth these are the SAME matrix (plan: one pair per distinct
 // matrix of a row), so one load feeds two products,  L <- A . L  and  R <- R . A,  which are
 // independent of each other (instruction-level parallelism where the one-sided form has a
-// single dependent chain).  Wave g of the workgroup takes the g-th part of the steps; wave 0
-// joins  L_{G-1} .. L_0 . a_m . R_0 .. R_{G-1}.  Valid for any sequence (non-mirrored steps just
-// load two matrices); same matrices as the other forms, associated differently.
+// single dependent chain).  Wave g of the row takes the g-th part of the steps and leaves its L_g, R_g
+// in LDS; the parts are joined as  (L_{G-1} .. (L_1 . L_0)) . (a_m . ((R_0 . R_1) .. R_{G-1})).
+// Unpacked launch: wave 0, the leader, multiplies both sides behind the barrier.  Packed launch: the
+// two sides on two waves (chain_join_r, chain_join_l) -- the leader multiplies the R parts and a_m . R,
+// wave 1 of the row, which gets the leader's L_0 through LDS, the L parts; behind a SECOND barrier
+// the leader reads the finished L and closes with  L . (a_m . R): the products, operands and
+// association of the one-wave join, so the same bits (tests/test_gpu_prob3_join.py), with three
+// products fewer on the critical path of a four-wave row (EXPERIMENTS R16-1).  Valid for any
+// sequence (non-mirrored steps just load two matrices); same matrices as the other forms,
+// associated differently.
 // AMP = 0: layer matrices read from stage AB's `amp`.  AMP = 1 (no decay) / 2 (decay): formed here
 // from the stage-A records `terms` of the layer's density (a pair belongs to one row, so nothing
 // is computed twice, and the records -- 2 x n_unique x 26 x n_e doubles -- stay in the L2 where
@@ -168,7 +176,7 @@ __device__ __forceinline__ void mat_mul_fma(const mat3 &A, const mat3 &B, mat3 &
 // rows by their length -- one long row split over four waves, two medium rows over two waves each, or four short
 // rows with a wave each: what bounds this kernel is the dependent sequence of layer matrices per wave of the
 // longest rows (13 for a 24-layer row; a step is ~460 vector instructions, ~1 us where a SIMD is shared), and
-// four-wave workgroups for EVERY row do not fit the chip at once (230 VGPRs, 54 KB of LDS: two workgroups per CU).
+// four-wave workgroups for EVERY row do not fit the chip at once (244 VGPRs, 63 KB of LDS: two workgroups per CU).
 // A 200 x 100 PREM-12 grid has 19 rows of >= 14 layers and 81 shorter ones: 60 row blocks per energy tile.  Its
 // fourth tile has 8 live energies; there the rows of one class (same densities in the same order, same mirrored
 // steps: 12 classes) share a wave, eight rows side by side, 13 blocks instead of 60: 386 workgroups where 480
@@ -191,6 +199,79 @@ __device__ __forceinline__ void chain_tail(const Prob3Consts &c, const Prob3Side
                                            const double *s_part, int part_0, int lane, int Gr, int n_steps, int cnt, int mid,
                                            int e_major, int ie, int n_e, int n_cz, int jcz, int side, int n_points, int pt,
                                            double *__restrict__ out, double2 *__restrict__ pepmu);
+
+// A wave's partial product in LDS: [L | R][18][lane].  In the packed launch wave w owns slot (w + 3) & 3 -- the
+// partners of a leader at wave w are the next slots, and slot 3, wave 0's, has room for an L alone.
+constexpr int CHAIN_PART = 2 * 18 * 64;
+__device__ __forceinline__ void part_store(double *o, const mat3 &M) {
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+        for (int j = 0; j < 3; j++) {
+            o[(6 * i + 2 * j) * 64] = M.m[i][j].re;
+            o[(6 * i + 2 * j + 1) * 64] = M.m[i][j].im;
+        }
+}
+__device__ __forceinline__ void part_load(const double *o, mat3 &M) {
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+        for (int j = 0; j < 3; j++) M.m[i][j] = cmake(o[(6 * i + 2 * j) * 64], o[(6 * i + 2 * j + 1) * 64]);
+}
+
+// first step of part h of a row's n_steps steps over Gr waves (h = Gr: one past the last step)
+template <bool PACKED>
+__device__ __forceinline__ int chain_part_begin(int n_steps, int h, int Gr) {
+    if constexpr (PACKED) return 1 + ((n_steps * h) >> (Gr >> 1));   // Gr is 1, 2 or 4 (prob3_waves_of)
+    else return 1 + (int)(((int64_t)n_steps * h) / Gr);
+}
+
+// The join of a packed row over GR = 2 or 4 waves, one side per wave (between the kernel's two barriers), each in the
+// order of the one-wave join: the same products on the same operands.
+// R side, the leader at wave `wv`:  R <- R . R_h,  h = 1 .. GR-1.  It asks for all of its partners' parts at once and
+// multiplies them back to back.
+template <int GR>
+__device__ __forceinline__ void chain_join_r(mat3 &R, bool &have_r, const double *s_part, int wv, int lane, int n_steps) {
+    mat3 P[GR - 1];
+#pragma unroll
+    for (int h = 1; h < GR; h++) part_load(s_part + ((wv + h + 3) & 3) * CHAIN_PART + 18 * 64 + lane, P[h - 1]);
+#pragma unroll
+    for (int h = 1; h < GR; h++) {
+        if (chain_part_begin<true>(n_steps, h + 1, GR) <= chain_part_begin<true>(n_steps, h, GR)) continue;  // part h had no steps
+        if (have_r) { mat3 t; mat_mul_fma(R, P[h - 1], t); R = t; } else { R = P[h - 1]; have_r = true; }
+    }
+}
+// L side, the wave after the leader (it holds L_1):  L <- L_h . L,  h = 1 .. GR-1, from the L_0 the leader left in its
+// slot; the product goes to this wave's own slot, where the leader finds it behind the second barrier.  A part has an
+// L unless it had no step or its only step was the unpaired last one.  Where every part has one (any row of four
+// waves, most of two) this side too asks for its parts at once; else it takes them one at a time -- asking ahead under
+// the `have_l` selects takes 257 registers and with them one workgroup per CU (EXPERIMENTS R16-1).
+template <int GR>
+__device__ __forceinline__ void chain_join_l(const mat3 &L1, double *s_part, int wv, int lane, int n_steps, int cnt, int mid) {
+    mat3 L;
+    if (n_steps >= GR && mid + chain_part_begin<true>(n_steps, GR - 1, GR) < cnt) {
+        mat3 P[GR - 1];   // L_0, L_2 .. L_{GR-1}
+#pragma unroll
+        for (int h = 0; h < GR; h++)
+            if (h != 1) part_load(s_part + ((wv - 1 + h + 3) & 3) * CHAIN_PART + lane, P[h ? h - 1 : 0]);
+        mat_mul_fma(L1, P[0], L);
+#pragma unroll
+        for (int h = 2; h < GR; h++) { mat3 t; mat_mul_fma(P[h - 1], L, t); L = t; }
+        part_store(s_part + ((wv + 3) & 3) * CHAIN_PART + lane, L);
+        return;
+    }
+    bool have_l = false;
+#pragma unroll
+    for (int h = 0; h < GR; h++) {
+        const int h0 = chain_part_begin<true>(n_steps, h, GR);
+        if (chain_part_begin<true>(n_steps, h + 1, GR) <= h0 || mid + h0 >= cnt) continue;
+        mat3 Ph;
+        if (h != 1) part_load(s_part + ((wv - 1 + h + 3) & 3) * CHAIN_PART + lane, Ph);
+        const mat3 &Lh = h == 1 ? L1 : Ph;
+        if (have_l) { mat3 t; mat_mul_fma(Lh, L, t); L = t; } else { L = Lh; have_l = true; }
+    }
+    if (have_l) part_store(s_part + ((wv + 3) & 3) * CHAIN_PART + lane, L);
+}
 
 template <int G, int AMP, class CS = ConstsByValue>
 __global__ void __launch_bounds__(G ? 64 * G : 256)
@@ -220,7 +301,8 @@ prob3_chain_kernel(const CS cs, int n_e, const int32_t *__restrict__ row_start,
     if (!PACKED) n_tiles = gridDim.z;
     const int pt = by >> 1;     // parameter point (0 in the one-point form)
     const Prob3Consts &c = cs.at(pt);
-    __shared__ double s_part[(PACKED ? 3 : (G > 1 ? G - 1 : 1)) * 2 * 18 * 64];  // [partial][L|R][18][lane]
+    // [partial][L|R][18][lane]; packed: a slot per wave, the fourth (wave 0's) an L alone -- 63 KB, two workgroups per CU
+    __shared__ double s_part[PACKED ? 3 * CHAIN_PART + 18 * 64 : (G > 1 ? G - 1 : 1) * CHAIN_PART];
     const int lane = threadIdx.x & 63;
     // wave index: uniform within a wave, which the compiler cannot see -- without this the loop
     // bounds derived from it are 'divergent' and every index look-up becomes a vector load
@@ -269,8 +351,8 @@ prob3_chain_kernel(const CS cs, int n_e, const int32_t *__restrict__ row_start,
     const int cnt = PACKED ? cnt_blk : (jcz >= 0 ? row_cnt[jcz] : 0);
     const int mid = cnt >> 1;
     const int n_steps = mid;  // steps s = 1..mid (out-going side may be one shorter)
-    const int s0 = 1 + (int)(((int64_t)n_steps * g) / Gr);
-    const int s1 = 1 + (int)(((int64_t)n_steps * (g + 1)) / Gr);
+    const int s0 = PACKED ? chain_part_begin<true>(n_steps, g, Gr) : 1 + (int)(((int64_t)n_steps * g) / Gr);
+    const int s1 = PACKED ? chain_part_begin<true>(n_steps, g + 1, Gr) : 1 + (int)(((int64_t)n_steps * (g + 1)) / Gr);
     const int64_t ns = (int64_t)n_tiles * 64;
     // 1/E once per lane: L/E as a product (one rounding more than the quotient, 1e-16 on a phase)
     const double inv_e = (AMP != 0 && live) ? 1.0 / energy[ie] : 1.0;
@@ -324,7 +406,7 @@ prob3_chain_kernel(const CS cs, int n_e, const int32_t *__restrict__ row_start,
     CSTAMP(2);
     if (g > 0 && live) {
         double *o = s_part + (size_t)part_w * 2 * 18 * 64 + lane;
-        if (have_l) {
+        if (have_l && !(PACKED && g == 1)) {
 #pragma unroll
             for (int i = 0; i < 3; i++)
 #pragma unroll
@@ -343,14 +425,45 @@ prob3_chain_kernel(const CS cs, int n_e, const int32_t *__restrict__ row_start,
                 }
         }
     }
+    // packed: the leader of a row of several waves hands its L_0 to the wave that joins the L side
+    if (PACKED && g == 0 && Gr > 1 && live && have_l) part_store(s_part + ((wv + 3) & 3) * CHAIN_PART + lane, L);
     // the leader forms the middle layer's matrix while it waits for its partners
     mat3 T;
     if (g == 0 && live && cnt > 0) load_pair(k0 + mid, T);
     __syncthreads();
     CSTAMP(3);
-    if (g != 0 || !live) return;
-    chain_tail<G, AMP>(c, S, L, R, T, have_l, have_r, s_part, part_0, lane, Gr, n_steps, cnt, mid, e_major, ie, n_e, n_cz, jl, side, n_points, pt,
-                       out, pepmu);
+    if constexpr (!PACKED) {
+        if (g != 0 || !live) return;
+        chain_tail<G, AMP>(c, S, L, R, T, have_l, have_r, s_part, part_0, lane, Gr, n_steps, cnt, mid, e_major, ie, n_e, n_cz, jl, side, n_points,
+                           pt, out, pepmu);
+    } else {
+        // The join on two waves: the leader multiplies the R parts and T . R while the next wave of the row multiplies
+        // the L parts; every wave of the workgroup meets at the second barrier (idle waves and the partners that have
+        // nothing to join pass straight through), and the leader closes with L . (T . R).
+        if (live && cnt > 0) {
+            if (g == 0) {
+                if (Gr == 4) chain_join_r<4>(R, have_r, s_part, wv, lane, n_steps);
+                else if (Gr == 2) chain_join_r<2>(R, have_r, s_part, wv, lane, n_steps);
+                if (have_r) { mat3 t; MM(T, R, t); T = t; }
+                if (Gr == 1 && have_l) { mat3 t; MM(L, T, t); T = t; }
+            } else if (g == 1) {
+                if (Gr == 4) chain_join_l<4>(L, s_part, wv, lane, n_steps, cnt, mid);
+                else chain_join_l<2>(L, s_part, wv, lane, n_steps, cnt, mid);
+            }
+        }
+        __syncthreads();
+        if (g != 0 || !live) return;
+        // some part has an L as soon as step 1 has an out-going layer
+        if (Gr > 1 && n_steps > 0 && mid + 1 < cnt) {
+            mat3 t;
+            part_load(s_part + ((wv + 1 + 3) & 3) * CHAIN_PART + lane, L);
+            MM(L, T, t);
+            T = t;
+        }
+        // joined already: the tail with one wave and no part of its own closes the chain
+        chain_tail<G, AMP>(c, S, L, R, T, false, false, s_part, 0, lane, 1, n_steps, cnt, mid, e_major, ie, n_e, n_cz, jl, side, n_points, pt, out,
+                           pepmu);
+    }
 }
 
 // the leader's part of the chain kernel: joins the partial products of its partner waves, closes the chain with the
