@@ -1361,6 +1361,33 @@ int pisa_hip_profiled_metric_matrix_best_bounded(int32_t kind, const double *d_d
                                                  double *d_eta_best, double *d_eta_at, int32_t *d_trial_status,
                                                  int32_t *d_status, void *stream);
 
+/* The wide form of the four entry points above: the same fit for up to 32 displacements (csrc/profile_wide.hip;
+ * DESIGN.md section 4, "Profiled trial ensembles: more than 8 parameters").  The definition, every argument and every
+ * output are those of pisa_hip_profiled_metric_matrix_bounded and pisa_hip_profiled_metric_matrix_best_bounded, with
+ * n_params in [1, _WIDE_MAX_PARAMS].  d_lower and d_upper both NULL: the unbounded fit of
+ * pisa_hip_profiled_metric_matrix / _best, bit for bit its definition; otherwise the bounded one, _BAD_BOUNDS
+ * included.  One wavefront fits one pair, with every sum formed as the same chain in the same order: for
+ * n_params <= 8 the outputs are bit for bit those of the entry points they stand in for.
+ * PISA_HIP_ERR_INVALID before any device access: as there, with n_params outside [1, 32], and more than 2^26 pairs for
+ * the full output or trials for the reduced one.  The join buffer of the reduced form is this pair's own. */
+#define PISA_HIP_PROFILE_WIDE_MAX_PARAMS 32
+int pisa_hip_profiled_metric_matrix_wide(int32_t kind, const double *d_data, const double *d_expected,
+                                         const double *d_sigma2, const double *d_response, int64_t response_stride_k,
+                                         const double *d_inv_prior_sigma, const double *d_center,
+                                         const double *d_lower, const double *d_upper, int64_t bound_stride_k,
+                                         int32_t n_params, int32_t max_iter, int64_t n_trials, int64_t n_templates,
+                                         int64_t n_bins, double *d_value, double *d_eta, int32_t *d_n_iter,
+                                         int32_t *d_pair_status, int32_t *d_status, void *stream);
+int pisa_hip_profiled_metric_matrix_best_wide(int32_t kind, const double *d_data, const double *d_expected,
+                                              const double *d_sigma2, const double *d_response,
+                                              int64_t response_stride_k, const double *d_inv_prior_sigma,
+                                              const double *d_center, const double *d_lower, const double *d_upper,
+                                              int64_t bound_stride_k, const double *d_offset, int32_t k0,
+                                              int32_t n_params, int32_t max_iter, int64_t n_trials,
+                                              int64_t n_templates, int64_t n_bins, double *d_best, int32_t *d_arg,
+                                              double *d_at, double *d_eta_best, double *d_eta_at,
+                                              int32_t *d_trial_status, int32_t *d_status, void *stream);
+
 /* The covariance of the fitted displacements (csrc/profile_hesse.hip; DESIGN.md section 4, "Profiled trial ensembles:
  * covariance and pulls"): for trial t, its template k_t = d_k_of_trial[t] (the d_arg of the reduced fit; NULL: k0 for
  * every trial) and the point d_eta[t] ([n_trials][J]; normally d_eta_best or d_eta_at of that fit), one sweep over the

@@ -33,8 +33,8 @@ value over the grid's points.  A free parameter that is NOT a dimension of the g
 where a `NuisanceResponse` is passed (`response=`): the template of point k is linearised in those parameters around
 the point, mu = hist[k] + sum_j response[k, j] eta_j with the binwise gradients of `DistributionMaker._fisher_templates`
 (`NuisanceResponse.from_maker`), and the displacements eta are fitted by the damped Newton iteration of
-csrc/profile.hip (`kernels.profiled_metric_matrix`, at most 8 parameters, Gaussian priors included; DESIGN.md §4,
-"Profiled trial ensembles") -- T x K small convex fits in one launch, no minimiser on the host.  The fit is exact for
+csrc/profile.hip (`kernels.profiled_metric_matrix`, at most 8 parameters, or 32 in the wide form a response asks for
+with `wide=True`; Gaussian priors included; DESIGN.md §4, "Profiled trial ensembles") -- T x K small convex fits in one launch, no minimiser on the host.  The fit is exact for
 a parameter the template is linear in (aeff_scale) and a first-order profile otherwise.  A response with bounds
 (`NuisanceResponse(..., lower=, upper=)`, `from_maker(..., bounded=True)`: the parameters' ranges as displacements
 from the point's values) fits every eta inside them, as a host minimiser working in the rescaled box [0, 1] would
@@ -59,6 +59,11 @@ and, for a `response` that has bounds, the same two methods with the keywords
     lower=, upper=  ([J] or [K, J] host arrays of displacements, -inf / +inf for no bound)
 which the drivers pass ONLY for such a response: a solver that knows nothing of bounds keeps working with responses
 that have none, and a bounded response on it is refused,
+and, for a wide `response` (`NuisanceResponse(..., wide=True)`: up to 32 parameters), the same two methods with
+    wide=True
+(csrc/profile_wide.hip, `kernels.profiled_metric_matrix_wide`: one wavefront per pair, the bits of the narrow fit up to 8
+parameters), passed ONLY for such a response in the same way; what reads a kernel that stays limited to 8 parameters --
+`hesse`, `posterior`, `draw_linear`, `draw_linear_mvn`, `draw_linear_at` -- is refused for a response with more,
 and, for `generator="device"` with `nuisance="prior"`,
     draw_linear(mu [B], response [J, B], sigma [B] or None, method, n_trials, seed, stream, scale, shift, lower, upper
                 ([J] host arrays; lower / upper may be None), first_trial=0)
@@ -167,22 +172,24 @@ class DeviceSolver:
         return self._run(K.metric_matrix_best, kind, (data, expected, sigma2, offset), k0=int(k0))
 
     def profiled_matrix(self, kind, data, expected, response, sigma2=None, inv_prior_sigma=None, center=None,
-                        max_iter=32, lower=None, upper=None):
+                        max_iter=32, lower=None, upper=None, wide=False):
+        """wide=True: the wide form (`kernels.profiled_metric_matrix_wide`, up to 32 parameters), whatever J"""
         from pisa_amd import kernels as K
 
         data, expected, response, sigma2, ips, center, lower, upper = [self._up(a) for a in (
             data, expected, response, sigma2, inv_prior_sigma, center, lower, upper)]
-        return K.profiled_metric_matrix(kind, data, expected, response, sigma2, ips, center, max_iter=max_iter,
-                                        lower=lower, upper=upper)
+        fn = K.profiled_metric_matrix_wide if wide else K.profiled_metric_matrix
+        return fn(kind, data, expected, response, sigma2, ips, center, max_iter=max_iter, lower=lower, upper=upper)
 
     def profiled_best(self, kind, data, expected, response, sigma2=None, inv_prior_sigma=None, center=None,
-                      offset=None, k0=0, max_iter=32, lower=None, upper=None):
+                      offset=None, k0=0, max_iter=32, lower=None, upper=None, wide=False):
         from pisa_amd import kernels as K
 
         data, expected, response, sigma2, ips, center, offset, lower, upper = [self._up(a) for a in (
             data, expected, response, sigma2, inv_prior_sigma, center, offset, lower, upper)]
-        return K.profiled_metric_matrix_best(kind, data, expected, response, sigma2, ips, center, offset, int(k0),
-                                             max_iter=max_iter, lower=lower, upper=upper)
+        fn = K.profiled_metric_matrix_best_wide if wide else K.profiled_metric_matrix_best
+        return fn(kind, data, expected, response, sigma2, ips, center, offset, int(k0), max_iter=max_iter, lower=lower,
+                  upper=upper)
 
     def hesse(self, kind, data, expected, response, eta, k, sigma2=None, inv_prior_sigma=None, center=None, lower=None,
               upper=None):
@@ -415,24 +422,30 @@ class TemplateGrid:
 
 
 class NuisanceResponse:
-    """The linear response of the templates of a grid to J <= 8 nuisance parameters that are not dimensions of the
-    grid: `names` [J]; `response` [K, J, B] (or [J, B], shared by all points) the change of the template per unit of
+    """The linear response of the templates of a grid to J <= 8 (`wide=True`: J <= 32) nuisance parameters that are not
+    dimensions of the grid: `names` [J]; `response` [K, J, B] (or [J, B], shared by all points) the change of the template per unit of
     the parameter (its magnitude in the parameter's units); `inv_prior_sigma` [J] = 1 / stddev of a Gaussian prior,
     0 without one; `center` [K, J] the parameter's value at point k minus its prior mean; `prior_at_point` [K] the
     named parameters' share of `priors_penalty` at point k, which the drivers take out of `grid.penalty` (the fit
     adds the prior at the FITTED value: no prior is counted twice); `values` [K, J] the parameters' values at the
     points, to which a fitted displacement eta is added; `lower` / `upper` [J] or [K, J] host arrays (either may be
     None): the box lower <= eta <= upper every displacement is fitted in, -inf / +inf for no bound (a NaN, or lower >
-    upper, raises ValueError).  Arrays of whatever kind the solver takes."""
+    upper, raises ValueError).  Arrays of whatever kind the solver takes.  `wide=True` takes 1 to 32 parameters and has
+    the drivers fit them with the wide form of the solver (`wide=True` of `profiled_matrix` / `profiled_best`;
+    csrc/profile_wide.hip), whatever J; what goes through a kernel limited to 8 parameters (covariances, pulls,
+    nuisance="fitted", `posterior_sample`, the device generator's nuisance draws) is then refused above 8."""
 
     def __init__(self, names, response, inv_prior_sigma=None, center=None, prior_at_point=None, values=None,
-                 max_iter=32, lower=None, upper=None):
+                 max_iter=32, lower=None, upper=None, wide=False):
         self.names = tuple(names)
+        self.wide = bool(wide)
         self.response = response
         n_j = len(self.names)
         if len(response.shape) not in (2, 3) or int(response.shape[-2]) != n_j:
             raise ValueError("NuisanceResponse: response is [K, %d, B] or [%d, B] for %d names" % (n_j, n_j, n_j))
-        if not 1 <= n_j <= 8:
+        if self.wide and not 1 <= n_j <= WIDE_MAX_PARAMS:
+            raise ValueError("NuisanceResponse: 1 to %d parameters with wide=True, got %d" % (WIDE_MAX_PARAMS, n_j))
+        if not self.wide and not 1 <= n_j <= MAX_PARAMS:
             raise ValueError("NuisanceResponse: 1 to 8 parameters, got %d" % n_j)
         self.inv_prior_sigma = np.zeros(n_j) if inv_prior_sigma is None else np.asarray(inv_prior_sigma, np.float64)
         self.center = None if center is None else np.asarray(center, dtype=np.float64)
@@ -470,13 +483,18 @@ class NuisanceResponse:
         """the keywords a driver passes to the solver's profiled methods: none for a response without bounds"""
         return dict(lower=self.lower, upper=self.upper) if self.bounded else {}
 
+    def fit_keywords(self):
+        """the keywords a driver passes to `profiled_matrix` and `profiled_best`: the bounds of a response that has
+        some, wide=True for a wide response, nothing otherwise"""
+        return dict(self.bounds(), wide=True) if self.wide else self.bounds()
+
     def offset(self, grid):
         """grid.penalty without the named parameters' share, or None if that is zero everywhere"""
         off = grid.penalty if self.prior_at_point is None else grid.penalty - self.prior_at_point
         return off if np.any(off != 0.0) else None
 
     @classmethod
-    def from_maker(cls, hypo_maker, grid, names, test_vals, max_iter=32, bounded=False):
+    def from_maker(cls, hypo_maker, grid, names, test_vals, max_iter=32, bounded=False, wide=False):
         """The response of `grid`'s templates to the free parameters `names` of `hypo_maker`: at every point of
         `grid.points` the gradients (T_hi - T_lo) / (hi - lo) of `hypo_maker._fisher_templates` (one call per
         parameter, every other parameter at the point's own value; one sweep of the events each where the pipeline
@@ -485,10 +503,15 @@ class NuisanceResponse:
         the mean are read from a Gaussian prior; a uniform prior (or none) gives 0; any other kind raises
         ValueError.  bounded=True: every displacement is fitted inside the parameter's `range`, lower[k, j] =
         range_j[0] - values[k, j] and upper[k, j] = range_j[1] - values[k, j] in the parameter's units (-inf / +inf
-        for a parameter without a range).  On return the free parameters hold the values they had at entry."""
+        for a parameter without a range).  wide=True: as in the constructor, up to 32 names.  On return the free
+        parameters hold the values they had at entry."""
         from pisa_amd import kernels as K
 
         names = list(names)
+        most = WIDE_MAX_PARAMS if wide else MAX_PARAMS
+        if not 1 <= len(names) <= most:      # (before any template is made)
+            raise ValueError("NuisanceResponse: 1 to %d parameters%s, got %d"
+                             % (most, " with wide=True" if wide else "", len(names)))
         free = hypo_maker.params.free
         for name in names:
             if name not in free.names:
@@ -545,7 +568,7 @@ class NuisanceResponse:
                 if prm._range is not None:
                     lower[:, j] = float(prm._range[0].m_as(prm._units)) - values[:, j]
                     upper[:, j] = float(prm._range[1].m_as(prm._units)) - values[:, j]
-        return cls(names, K.to_device(resp), ips, center, at_point, values, max_iter, lower, upper)
+        return cls(names, K.to_device(resp), ips, center, at_point, values, max_iter, lower, upper, wide)
 
 
 def _takes_bounds(method):
@@ -554,6 +577,20 @@ def _takes_bounds(method):
     params = inspect.signature(method).parameters
     return ("lower" in params and "upper" in params) or any(
         p.kind is inspect.Parameter.VAR_KEYWORD for p in params.values())
+
+
+def _takes_wide(method):
+    import inspect
+
+    params = inspect.signature(method).parameters
+    return "wide" in params or any(p.kind is inspect.Parameter.VAR_KEYWORD for p in params.values())
+
+
+def _check_narrow(response, what, needs):
+    """what goes through a kernel that fits, draws or samples at most 8 parameters"""
+    if response is not None and len(response.names) > MAX_PARAMS:
+        raise ValueError("%s: %s is limited to %d nuisance parameters; this response has %d (the wide form fits up to "
+                         "%d, and fits alone)" % (what, needs, MAX_PARAMS, len(response.names), WIDE_MAX_PARAMS))
 
 
 def _check_response(response, grid, solver, what, metric=None):
@@ -566,6 +603,10 @@ def _check_response(response, grid, solver, what, metric=None):
     if response.bounded and not (_takes_bounds(solver.profiled_matrix) and _takes_bounds(solver.profiled_best)):
         raise ValueError("ensemble: a response with bounds needs a solver whose profiled_matrix and profiled_best "
                          "take lower= and upper=; those of %s do not" % type(solver).__name__)
+    if getattr(response, "wide", False) and not (_takes_wide(solver.profiled_matrix)
+                                                 and _takes_wide(solver.profiled_best)):
+        raise ValueError("ensemble: a wide response needs a solver whose profiled_matrix and profiled_best take "
+                         "wide=; those of %s do not" % type(solver).__name__)
     shape = tuple(response.response.shape)
     if shape[-1] != grid.n_bins or (len(shape) == 3 and shape[0] != len(grid)):
         raise ValueError("%s: the response does not belong to this grid (%s against %d points, %d bins)"
@@ -577,6 +618,8 @@ def _check_response(response, grid, solver, what, metric=None):
 
 
 GENERATORS = ("host", "device")
+MAX_PARAMS = 8                 # _lib.PROFILE_MAX_PARAMS: the narrow fit, the covariance, the draws and the sampler
+WIDE_MAX_PARAMS = 32           # _lib.PROFILE_WIDE_MAX_PARAMS: the wide fit
 CHUNK_BYTES = 1 << 30          # pseudo-data of the device generator alive at a time
 
 
@@ -683,6 +726,10 @@ def _check_nuisance(nuisance, response, grid, solver, generator, method, metric,
     if metric in _MC_METRICS:
         raise ValueError("%s: nuisance='%s' is not available for '%s' (response= has no form for the "
                          "MC-uncertainty metrics)" % (what, nuisance, metric))
+    if nuisance == "fitted":
+        _check_narrow(response, what, "nuisance='fitted' (the covariance of the observed fit)")
+    if generator == "device":
+        _check_narrow(response, what, "generator='device' with nuisance='%s' (the device draws of the truths)" % nuisance)
     if method == "scaled_poisson":
         raise ValueError("%s: nuisance='%s' has no scaled_poisson draws (the method's row rules compare a row's "
                          "variance with its mean, which moves per trial)" % (what, nuisance))
@@ -845,13 +892,14 @@ def fit_observed(observed, grid, metric, response, solver=None, covariance=False
         raise ValueError("fit_observed: needs response=, the linear response whose parameters are fitted")
     _check_response(response, grid, solver, "fit_observed", metric)
     if covariance:
+        _check_narrow(response, "fit_observed", "covariance=True")
         _check_hesse(solver)
     rows = _data_rows(observed)
     if int(rows.shape[0]) != 1 or int(rows.shape[1]) != grid.n_bins:
         raise ValueError("fit_observed: one observed map of %d bins, got %s" % (grid.n_bins, tuple(rows.shape)))
     args = (grid.sigma2_for(metric), response.inv_prior_sigma, response.center)
     out = solver.profiled_matrix(metric, rows, grid.hist, response.response, *args, response.max_iter,
-                                 **response.bounds())
+                                 **response.fit_keywords())
     fit = dict(eta=_host(out["eta"])[0], status=_host(out["status"])[0], value=_host(out["value"])[0])
     if covariance:
         n_k = len(grid)
@@ -944,6 +992,8 @@ def _check_truths(response, grid, solver, generator, method, metric, nuisance, o
     if method == "scaled_poisson":
         raise ValueError("%s: truths= has no scaled_poisson draws (the method's row rules compare a row's variance "
                          "with its mean, which moves per trial)" % what)
+    if generator == "device":
+        _check_narrow(response, what, "generator='device' with truths= (the device draws at given truths)")
     if generator == "device" and not hasattr(solver, "draw_linear_at"):
         raise ValueError("ensemble: generator='device' with truths= needs a solver with draw_linear_at(mu, response, "
                          "sigma, method, eta, seed, stream, first_trial); %s has none" % type(solver).__name__)
@@ -1131,7 +1181,7 @@ def metric_matrix(data, grid, metric, with_penalty=True, solver=None, response=N
         _check_response(response, grid, solver, "metric_matrix", metric)
         m = solver.profiled_matrix(metric, _data_rows(data), grid.hist, response.response, grid.sigma2_for(metric),
                                    response.inv_prior_sigma, response.center, response.max_iter,
-                                   **response.bounds())["value"]
+                                   **response.fit_keywords())["value"]
         penalty = response.offset(grid)
     if with_penalty and penalty is not None:
         if hasattr(m, "cpu"):
@@ -1169,10 +1219,11 @@ def delta_metric(data, grid, metric, k0, solver=None, response=None, return_info
         return best - at if metric in _MAXIMISED else at - best
     _check_response(response, grid, solver, "delta_metric", metric)
     if covariance:
+        _check_narrow(response, "delta_metric", "covariance=True")
         _check_hesse(solver)
     out = solver.profiled_best(metric, _data_rows(data), grid.hist, response.response, grid.sigma2_for(metric),
                                response.inv_prior_sigma, response.center, response.offset(grid), int(k0),
-                               response.max_iter, **response.bounds())
+                               response.max_iter, **response.fit_keywords())
     best, at = _host(out["best"]), _host(out["at"])
     delta = best - at if metric in _MAXIMISED else at - best
     if not return_info:
@@ -1205,6 +1256,7 @@ def pulls(data, grid, metric, k0, response, truth, solver=None):
     and the counts large: the closure check of a profiled ensemble.  NaN where sigma is 0 (a coordinate held on a
     bound) or NaN (a flagged fit)."""
     solver = DeviceSolver() if solver is None else solver
+    _check_narrow(response, "pulls", "the covariance of the fit")
     _check_hesse(solver)
     rows = _data_rows(data)
     truth = _host(truth)
@@ -1482,6 +1534,7 @@ def posterior_sample(observed, grid, metric, response, points=None, n_keep=200, 
     if response is None:
         raise ValueError("posterior_sample: needs response=, the linear response whose parameters are sampled")
     _check_response(response, grid, solver, "posterior_sample", metric)
+    _check_narrow(response, "posterior_sample", "the sampler")
     for name in ("posterior", "draw_linear", "hesse"):
         if not hasattr(solver, name):
             raise ValueError("ensemble: posterior_sample needs a solver with %s; %s has none"

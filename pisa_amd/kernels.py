@@ -930,7 +930,8 @@ def fluctuate_linear_at(mu, response, eta, seed, method="poisson", sigma=None, s
     return dict(data=out, eta=eta, clipped=clipped & 0xFFFFFFFF)
 
 
-def _profile_args(what, kind, data, expected, response, sigma2, inv_prior_sigma, center, max_iter):
+def _profile_args(what, kind, data, expected, response, sigma2, inv_prior_sigma, center, max_iter,
+                  most=_lib.PROFILE_MAX_PARAMS):
     if kind in ENSEMBLE_MC_KINDS:
         raise ValueError("%s: '%s' has no profiled form (its per-bin function is not convex in the response)"
                          % (what, kind))
@@ -945,8 +946,8 @@ def _profile_args(what, kind, data, expected, response, sigma2, inv_prior_sigma,
         raise ValueError("%s: response is float64 [n_templates, n_params, n_bins], or [n_params, n_bins] shared by "
                          "all templates" % what)
     n_j = response.shape[-2]
-    if not 1 <= n_j <= _lib.PROFILE_MAX_PARAMS:
-        raise ValueError("%s: %d nuisance parameters, 1 to %d are fitted" % (what, n_j, _lib.PROFILE_MAX_PARAMS))
+    if not 1 <= n_j <= most:
+        raise ValueError("%s: %d nuisance parameters, 1 to %d are fitted" % (what, n_j, most))
     if inv_prior_sigma is not None and (inv_prior_sigma.shape != (n_j,) or inv_prior_sigma.dtype != F8):
         raise ValueError("%s: inv_prior_sigma is float64 [n_params]" % what)
     if center is not None and (center.shape != (n_k, n_j) or center.dtype != F8):
@@ -1048,6 +1049,65 @@ def profiled_metric_matrix_best(kind, data, expected, response, sigma2=None, inv
             METRIC_KIND[kind], _ptr(data), _ptr(expected), _ptr(sigma2), _ptr(response), stride, _ptr(ips),
             _ptr(center), _ptr(offset), int(k0), n_j, int(max_iter), n_t, n_k, n_bins, _ptr(best), _ptr(arg),
             _ptr(at), _ptr(eta_best), _ptr(eta_at), _ptr(trial_status), _ptr(status), _stream()))
+
+    _with_status(status, dev, launch)
+    return dict(best=best, arg=arg, at=at, eta_best=eta_best, eta_at=eta_at, status=trial_status)
+
+
+def profiled_metric_matrix_wide(kind, data, expected, response, sigma2=None, inv_prior_sigma=None, center=None,
+                                max_iter=32, want_eta=True, status=None, lower=None, upper=None):
+    """`profiled_metric_matrix` in the wide form (`pisa_hip_profiled_metric_matrix_wide`, DESIGN.md §4, "Profiled
+    trial ensembles: more than 8 parameters"): the same fit, arguments and outputs with 1 to
+    `_lib.PROFILE_WIDE_MAX_PARAMS` = 32 nuisance parameters, one wavefront per (trial, template) pair.  With both
+    bounds None it is the unbounded fit, otherwise the bounded one; up to 8 parameters the outputs are bit for bit those
+    of `profiled_metric_matrix`."""
+    what = "profiled_metric_matrix_wide"
+    (data, expected, response, sigma2, ips, center, stride, n_t, n_k, n_bins, n_j) = _profile_args(
+        what, kind, data, expected, response, sigma2, inv_prior_sigma, center, max_iter, _lib.PROFILE_WIDE_MAX_PARAMS)
+    b_stride = 0
+    if lower is not None or upper is not None:
+        lower, upper, b_stride = _bound_args(what, lower, upper, n_k, n_j)
+    dev = data.device
+    value = torch.empty((n_t, n_k), dtype=F8, device=dev)
+    eta = torch.empty((n_t, n_k, n_j), dtype=F8, device=dev) if want_eta else None
+    n_iter = torch.empty((n_t, n_k), dtype=torch.int32, device=dev)
+    pair_status = torch.empty((n_t, n_k), dtype=torch.int32, device=dev)
+
+    def launch(status):
+        _lib.check(_lib.lib().pisa_hip_profiled_metric_matrix_wide(
+            METRIC_KIND[kind], _ptr(data), _ptr(expected), _ptr(sigma2), _ptr(response), stride, _ptr(ips),
+            _ptr(center), _ptr(lower), _ptr(upper), b_stride, n_j, int(max_iter), n_t, n_k, n_bins, _ptr(value),
+            _ptr(eta), _ptr(n_iter), _ptr(pair_status), _ptr(status), _stream()))
+
+    _with_status(status, dev, launch)
+    return dict(value=value, eta=eta, n_iter=n_iter, status=pair_status)
+
+
+def profiled_metric_matrix_best_wide(kind, data, expected, response, sigma2=None, inv_prior_sigma=None, center=None,
+                                     offset=None, k0=0, max_iter=32, status=None, lower=None, upper=None):
+    """`profiled_metric_matrix_best` in the wide form (`pisa_hip_profiled_metric_matrix_best_wide`): the reduction of
+    `profiled_metric_matrix_wide` per trial, bit for bit, with 1 to 32 nuisance parameters"""
+    what = "profiled_metric_matrix_best_wide"
+    (data, expected, response, sigma2, ips, center, stride, n_t, n_k, n_bins, n_j) = _profile_args(
+        what, kind, data, expected, response, sigma2, inv_prior_sigma, center, max_iter, _lib.PROFILE_WIDE_MAX_PARAMS)
+    b_stride = 0
+    if lower is not None or upper is not None:
+        lower, upper, b_stride = _bound_args(what, lower, upper, n_k, n_j)
+    dev = data.device
+    offset = _offset_arg(what, offset, n_k)
+    best = torch.empty(n_t, dtype=F8, device=dev)
+    arg = torch.empty(n_t, dtype=torch.int32, device=dev)
+    at = torch.empty(n_t, dtype=F8, device=dev)
+    eta_best = torch.empty((n_t, n_j), dtype=F8, device=dev)
+    eta_at = torch.empty((n_t, n_j), dtype=F8, device=dev)
+    trial_status = torch.empty(n_t, dtype=torch.int32, device=dev)
+
+    def launch(status):
+        _lib.check(_lib.lib().pisa_hip_profiled_metric_matrix_best_wide(
+            METRIC_KIND[kind], _ptr(data), _ptr(expected), _ptr(sigma2), _ptr(response), stride, _ptr(ips),
+            _ptr(center), _ptr(lower), _ptr(upper), b_stride, _ptr(offset), int(k0), n_j, int(max_iter), n_t, n_k,
+            n_bins, _ptr(best), _ptr(arg), _ptr(at), _ptr(eta_best), _ptr(eta_at), _ptr(trial_status), _ptr(status),
+            _stream()))
 
     _with_status(status, dev, launch)
     return dict(best=best, arg=arg, at=at, eta_best=eta_best, eta_at=eta_at, status=trial_status)

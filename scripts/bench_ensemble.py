@@ -191,6 +191,44 @@ def profiled_lines(n_params, reps, bounded=None):
         del d, e, r
 
 
+def profiled_wide_lines(n_params, reps):
+    """the protocol of `profiled_lines` with the wide form (`profiled_metric_matrix_best_wide`, one wavefront per pair,
+    J up to 32) at (T, K, B) = (1e4, 1e2, 128); iteration counts from the wide full output on the first trials.  With
+    J <= 8 the narrow form is timed in the same run: the price of the mapping."""
+    import torch
+
+    from pisa_amd import kernels as K
+
+    dev = K.device()
+    J = int(n_params)
+    n_t, n_k, n_b = 10 ** 4, 10 ** 2, 128
+    e_host = _templates(n_k, n_b)
+    rs = np.random.RandomState(1)
+    x = (np.arange(n_b) + 0.5) / n_b
+    r_host = 0.05 * np.cos((np.arange(J)[:, None] + 1) * np.pi * x[None, :])[None] * e_host[:, None, :]
+    mu = e_host + np.einsum("kjb,kj->kb", r_host, 0.5 * rs.randn(n_k, J))
+    d = torch.from_numpy(rs.poisson(np.maximum(mu, 1.0)[rs.randint(0, n_k, n_t)]).astype(np.float64)).to(dev)
+    e, r = torch.from_numpy(e_host).to(dev), torch.from_numpy(r_host).to(dev)
+    s2 = 0.1 * e
+    ips = torch.ones(J, dtype=torch.float64, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    n_head = 256
+    for kind in ("llh", "poisson_llh", "chi2", "mod_chi2"):
+        sig = s2 if kind == "mod_chi2" else None
+        head = K.profiled_metric_matrix_wide(kind, d[:n_head], e, r, sig, ips, want_eta=False, status=status)
+        it = head["n_iter"].double()
+        res = _time(lambda: K.profiled_metric_matrix_best_wide(kind, d, e, r, sig, ips, k0=n_k // 2, status=status), reps)
+        line = dict(workload="profiled_kernel_wide", T=n_t, K=n_k, B=n_b, J=J, kind=kind, output="reduced", **res,
+                    iter_mean=round(float(it.mean().item()), 3), iter_max=int(it.max().item()),
+                    flagged_of_head=int((head["status"] != 0).sum().item()), head_pairs=int(it.numel()),
+                    ms_per_sweep=round(res["ms_median"] / (float(it.mean().item()) + 2.0), 3))
+        if J <= 8:
+            narrow = _time(lambda: K.profiled_metric_matrix_best(kind, d, e, r, sig, ips, k0=n_k // 2, status=status), reps)
+            line.update(ms_narrow=narrow["ms_median"], ratio_to_narrow=round(res["ms_median"] / narrow["ms_median"], 2))
+        print(json.dumps(line), flush=True)
+    assert int(status.item()) == 0
+
+
 def truth_lines(reps=5):
     """one line per method for `fluctuate_linear` against `fluctuate`, one per kind for `profiled_hesse` against
     `profiled_metric_matrix_best`, at (T, K, B, J) = (1e4, 1e2, 128, 8); the inputs of `profiled_lines`"""
@@ -520,7 +558,11 @@ def main():
     ap.add_argument("--metric", default="llh", help="the metric of the end-to-end run")
     ap.add_argument("--method", default="poisson", help="the fluctuation method of the end-to-end run")
     ap.add_argument("--profiled", type=int, default=0, metavar="J",
-                    help="also time the profiled reduced form with J fitted nuisance parameters (1 to 8)")
+                    help="also time the profiled reduced form with J fitted nuisance parameters (1 to 8; with --wide: "
+                         "1 to 32)")
+    ap.add_argument("--wide", action="store_true",
+                    help="with --profiled: time the wide form (one wavefront per pair) at (1e4, 1e2, 128), and for "
+                         "J <= 8 the narrow form beside it")
     ap.add_argument("--bounded", type=float, default=None, metavar="H",
                     help="with --profiled: also time the bounded reduced form, every displacement inside -H ... +H "
                          "prior sigmas")
@@ -552,7 +594,9 @@ def main():
         return
     if not args.skip_kernels:
         kernel_lines(args.reps, tuple(args.forms.split(",")))
-    if args.profiled:
+    if args.profiled and args.wide:
+        profiled_wide_lines(args.profiled, args.reps)
+    elif args.profiled:
         profiled_lines(args.profiled, args.reps, args.bounded)
     if not args.skip_draw:
         draw_lines(args.reps)
