@@ -46,11 +46,10 @@ PISA_PF_HD void ps_begin(PsSweep &sw) {
     sw.inside = true;
 }
 
-// one bin at eta: the value of `pf_bin`, operation for operation
+// one bin at eta: the value of `pf_bin` (`pf_phi`; its derivatives are dropped)
 template <int KIND, int J>
 PISA_PF_HD void ps_bin(PsSweep &sw, const double *eta, double d, double e, double s2, const double *r) {
-    const bool finite = (d == d) && (e == e) && !isinf(d) && !isinf(e);
-    if (!finite) return;
+    if (!pf_finite(d, e)) return;
     bool responds;
     double reach;
     const double mu = pf_mu<J>(e, r, eta, responds, reach);
@@ -59,14 +58,8 @@ PISA_PF_HD void ps_bin(PsSweep &sw, const double *eta, double d, double e, doubl
         return;
     }
     const double m = mu < PF_SMALL_POS ? PF_SMALL_POS : mu;
-    double phi;
-    if (PfKind<KIND>::is_llh) {
-        phi = m - d * log(m);
-    } else {
-        const double v = KIND == PF_MOD_CHI2 ? s2 + m : m;
-        const double rr = d - m, a = rr / v;
-        phi = rr * a;
-    }
+    double phi, p1, p2;
+    pf_phi<KIND>(d, m, s2, phi, p1, p2);   // (the derivatives are not used)
     pf_two_sum(sw.phi_s, sw.phi_c, phi);
 }
 
@@ -74,14 +67,11 @@ PISA_PF_HD void ps_bin(PsSweep &sw, const double *eta, double d, double e, doubl
 template <int KIND, int J>
 PISA_PF_HD double ps_end(const PsSweep &sw, const double *eta, const double *ips, const double *c, const double *lo,
                          const double *hi) {
-    constexpr double w = PfKind<KIND>::w;
-    double Phi = sw.phi_s + sw.phi_c;
+    double Phi = sw.phi_s + sw.phi_c, p;
     bool in_box = true;
 #pragma unroll
     for (int j = 0; j < J; j++) {
-        const double p = ips[j] * (eta[j] + c[j]);
-        const double pp = w * (p * p);
-        Phi += pp;
+        Phi += pf_prior<KIND>(ips[j], eta[j], c[j], p);
         if (!(eta[j] >= lo[j] && eta[j] <= hi[j])) in_box = false;
     }
     if (!sw.inside || !in_box || Phi != Phi) return -INFINITY;

@@ -22,11 +22,10 @@ PISA_API int pisa_hip_profiled_metric_matrix_bounded(int32_t kind, const double 
                                                      int64_t n_bins, double *d_value, double *d_eta,
                                                      int32_t *d_n_iter, int32_t *d_pair_status, int32_t *d_status,
                                                      void *stream) {
-    PfArgs a = {};
-    a.D = d_data, a.E = d_expected, a.S2 = d_sigma2, a.R = d_response, a.ips = d_inv_prior_sigma, a.center = d_center;
-    a.lower = d_lower, a.upper = d_upper, a.b_stride_k = bound_stride_k;
-    a.value = d_value, a.eta = d_eta, a.n_iter = d_n_iter, a.pair_status = d_pair_status, a.status = d_status;
-    return pf_run<false, true>(kind, response_stride_k, n_params, max_iter, n_trials, n_templates, n_bins, a, stream);
+    const PfArgs in = pf_args_in(d_data, d_expected, d_sigma2, d_response, response_stride_k, d_inv_prior_sigma,
+                                 d_center, d_status, d_lower, d_upper, bound_stride_k);
+    const PfArgs a = pf_args_full(in, d_value, d_eta, d_n_iter, d_pair_status);
+    return pf_run<false, true>(kind, n_params, max_iter, n_trials, n_templates, n_bins, a, stream);
 }
 
 PISA_API int pisa_hip_profiled_metric_matrix_best_bounded(int32_t kind, const double *d_data, const double *d_expected,
@@ -39,11 +38,8 @@ PISA_API int pisa_hip_profiled_metric_matrix_best_bounded(int32_t kind, const do
                                                           int64_t n_bins, double *d_best, int32_t *d_arg, double *d_at,
                                                           double *d_eta_best, double *d_eta_at,
                                                           int32_t *d_trial_status, int32_t *d_status, void *stream) {
-    PfArgs a = {};
-    a.D = d_data, a.E = d_expected, a.S2 = d_sigma2, a.R = d_response, a.ips = d_inv_prior_sigma, a.center = d_center;
-    a.lower = d_lower, a.upper = d_upper, a.b_stride_k = bound_stride_k;
-    a.offset = d_offset, a.k0 = k0;
-    a.best = d_best, a.arg = d_arg, a.at = d_at, a.eta_best = d_eta_best, a.eta_at = d_eta_at;
-    a.trial_status = d_trial_status, a.status = d_status;
-    return pf_run<true, true>(kind, response_stride_k, n_params, max_iter, n_trials, n_templates, n_bins, a, stream);
+    const PfArgs in = pf_args_in(d_data, d_expected, d_sigma2, d_response, response_stride_k, d_inv_prior_sigma,
+                                 d_center, d_status, d_lower, d_upper, bound_stride_k);
+    const PfArgs a = pf_args_best(in, d_offset, k0, d_best, d_arg, d_at, d_eta_best, d_eta_at, d_trial_status);
+    return pf_run<true, true>(kind, n_params, max_iter, n_trials, n_templates, n_bins, a, stream);
 }

@@ -14,6 +14,12 @@
 // The bounded form (`pf_init_bounded`, `pf_decide_bounded`; profile_bounded.hip) is the same state machine with a
 // projected step: eta_hat minimises Phi over lo_j <= eta_j <= hi_j ("Profiled trial ensembles: bounds";
 // restated in tests/profile_bounded_cases.py).
+// This file is the home of Phi for every form of the fit.  The wide form (profile_wide_device.hpp), the covariance
+// (`pf_hesse_*` below) and the posterior sampler (posterior_device.hpp) take from here the finite test (`pf_finite`),
+// phi / phi' / phi'' of a bin (`pf_phi`), its term of `scale` (`pf_scale_term`), the prior term (`pf_prior`,
+// `pf_prior_join`) and the bound set (`pf_bound_set`, which `pf_bind` applies).  `pf_bin` and `pf_decide_any`, the two
+// functions the 128 narrow kernels spend their registers in, keep the per-bin arithmetic and the prior lines written
+// out: calling the helpers there changes the register allocation of those kernels (profiles/r17_profile_shared/).
 // No HIP type or call: the same source compiles for the host with a plain C++ compiler; tests/test_host_profiled.py
 // and tests/test_host_profiled_bounded.py run it there, under the sanitizers, against the numpy restatements.
 #pragma once
@@ -168,7 +174,34 @@ PISA_PF_HD double pf_mu(double e, const double *r, const double *eta, bool &resp
     return mu;
 }
 
+// a bin with a non-finite datum or expectation takes no part in any sum (the direct form drops it)
+PISA_PF_HD bool pf_finite(double d, double e) { return (d == d) && (e == e) && !isinf(d) && !isinf(e); }
+
+// phi, phi', phi'' of one admitted bin at m: the per-bin arithmetic of Phi for every form but `pf_bin` below
+template <int KIND>
+PISA_PF_HD void pf_phi(double d, double m, double s2, double &phi, double &p1, double &p2) {
+    if (PfKind<KIND>::is_llh) {
+        const double q = d / m;
+        phi = m - d * log(m);
+        p1 = 1.0 - q;
+        p2 = q / m;
+    } else {
+        const double v = KIND == PF_MOD_CHI2 ? s2 + m : m;
+        const double rr = d - m, a = rr / v;
+        const double u = (KIND == PF_MOD_CHI2 ? d + s2 : d) / v;
+        phi = rr * a;
+        p1 = -(a * (2.0 + a));
+        p2 = 2.0 * (u * u) / v;
+    }
+}
+
+// the bin's term of `scale` (mu is a rounded sum: Phi sees it through phi')
+PISA_PF_HD double pf_scale_term(double phi, double p1, double reach) { return (fabs(phi) + 1.0) + fabs(p1) * reach; }
+
 // one bin of a sweep at eta_t.  A bin with a non-finite datum or expectation takes no part (the direct form drops it).
+// OWN COPY of `pf_finite`, `pf_phi` and `pf_scale_term`, operation for operation: with the calls, 7 of the 64 unbounded
+// narrow kernels change their count of spilled SGPRs (the inliner orders the blocks of `log` differently).  A change
+// of Phi is made in `pf_phi` AND here; tests/test_gpu_profiled_wide.py holds the two together bit for bit.
 template <int KIND, int J>
 PISA_PF_HD void pf_bin(PfState<J> &st, double d, double e, double s2, const double *r) {
     const bool finite = (d == d) && (e == e) && !isinf(d) && !isinf(e);
@@ -273,8 +306,9 @@ PISA_PF_HD void pf_trial_bounded(PfState<J> &st, const double *lo, const double 
 // A pinned coordinate (lo == hi) is no variable and belongs to the set whatever its gradient: at an exact fit the
 // gradient is 0 in every coordinate, and a pinned one set free there would bring back the singular Hessian it was
 // pinned to avoid.
+// the bound set as a mask (bit j: coordinate j), from the marks of `pf_hold` and the gradient
 template <int J>
-PISA_PF_HD void pf_bind(PfState<J> &st) {
+PISA_PF_HD uint32_t pf_bound_set(const PfState<J> &st) {
     const uint32_t on = st.on_bound;   // (of the trial point that has just become eta)
     uint32_t bound = 0;
 #pragma unroll
@@ -283,6 +317,13 @@ PISA_PF_HD void pf_bind(PfState<J> &st) {
         const bool at_lo = on >> j & 1u, at_hi = on >> (8 + j) & 1u;
         if ((at_lo && at_hi) || (at_lo && gj > 0.0) || (at_hi && gj < 0.0)) bound |= 1u << j;
     }
+    return bound;
+}
+
+// the bound set leaves the system
+template <int J>
+PISA_PF_HD void pf_bind(PfState<J> &st) {
+    const uint32_t bound = pf_bound_set<J>(st);
 #pragma unroll
     for (int i = 0; i < J; i++) {
         if (bound >> i & 1u) st.g[i] = 0.0;
@@ -292,9 +333,24 @@ PISA_PF_HD void pf_bind(PfState<J> &st) {
     }
 }
 
+// The prior term of one coordinate at x: p = ips (x + c), returns its share w p^2 of Phi.  `pf_prior_join` adds the
+// term's share to the gradient entry and to the diagonal entry of the Hessian.
+template <int KIND>
+PISA_PF_HD double pf_prior(double ips, double x, double c, double &p) {
+    p = ips * (x + c);
+    return PfKind<KIND>::w * (p * p);
+}
+
+template <int KIND>
+PISA_PF_HD void pf_prior_join(double ips, double p, double &g, double &h) {
+    g += (2.0 * PfKind<KIND>::w) * (ips * p);
+    h += (2.0 * PfKind<KIND>::w) * (ips * ips);
+}
+
 // after a sweep at eta_t: the priors join, the trial point is accepted or the step halved; on acceptance the next
 // step is formed.  Sets `done` when the pair has its final eta.  BOUNDED: every trial point and the last step are
 // held inside [lo, hi] and the step is that of the free block (`pf_bind`); nothing else differs.
+// OWN COPY of `pf_prior` and `pf_prior_join` in its first loop (see `pf_bin`: the narrow kernels' registers).
 template <int KIND, int J, bool BOUNDED>
 PISA_PF_HD void pf_decide_any(PfState<J> &st, const double *ips, const double *c, const double *lo, const double *hi,
                               int32_t max_iter) {
@@ -388,20 +444,6 @@ PISA_PF_HD int32_t pf_status(const PfState<J> &st) {
 // (profile_hesse.hip; DESIGN.md §4, "Profiled trial ensembles: covariance and pulls"; restated in tests/hesse_cases.py)
 constexpr int PF_HELD = 32;                // PISA_HIP_PROFILE_HELD: a coordinate of the bound set has zero rows and columns
 
-// the bound set `pf_bind` takes out of the system, as a mask (bit j: coordinate j), from the same marks and gradient
-template <int J>
-PISA_PF_HD uint32_t pf_bound_set(const PfState<J> &st) {
-    const uint32_t on = st.on_bound;
-    uint32_t bound = 0;
-#pragma unroll
-    for (int j = 0; j < J; j++) {
-        const double gj = st.g[j];
-        const bool at_lo = on >> j & 1u, at_hi = on >> (8 + j) & 1u;
-        if ((at_lo && at_hi) || (at_lo && gj > 0.0) || (at_hi && gj < 0.0)) bound |= 1u << j;
-    }
-    return bound;
-}
-
 // inv (packed lower triangle) = (L L^T)^-1 from the factor L of `pf_factor`: column k is the solution of
 // L L^T x = e_k by forward and back substitution, of which the entries i >= k are kept (the forward solution is 0
 // above k, and the back substitution of entry i reads the entries below it alone).
@@ -457,12 +499,11 @@ PISA_PF_HD bool pf_hesse_begin(PfState<J> &st, const double *eta, const double *
 // written then --, or PF_HELD where the bound set is not empty, else 0.
 template <int KIND, int J>
 PISA_PF_HD int32_t pf_hesse_end(PfState<J> &st, const double *ips, const double *c, double *cov) {
-    constexpr double w = PfKind<KIND>::w;
 #pragma unroll
     for (int j = 0; j < J; j++) {
-        const double p = ips[j] * (st.eta_t[j] + c[j]);
-        st.g[j] += (2.0 * w) * (ips[j] * p);
-        st.H[pf_at(j, j)] += (2.0 * w) * (ips[j] * ips[j]);
+        double p;
+        pf_prior<KIND>(ips[j], st.eta_t[j], c[j], p);
+        pf_prior_join<KIND>(ips[j], p, st.g[j], st.H[pf_at(j, j)]);
     }
     if (!st.inside) return PF_START_OUTSIDE;
     const uint32_t held = pf_bound_set<J>(st);
@@ -494,8 +535,7 @@ PISA_PF_HD void pf_value_begin(PfValue &v) {
 // one bin of ens_direct_kernel on the template row mu(eta)
 template <int KIND, int J>
 PISA_PF_HD void pf_value_bin(PfValue &v, const double *eta, double d, double e, double s2, const double *r) {
-    const bool finite = (d == d) && (e == e) && !isinf(d) && !isinf(e);
-    if (!finite) return;
+    if (!pf_finite(d, e)) return;
     if (d < 0.0 || e < 0.0) v.negative = true;
     bool responds;
     double reach;
@@ -512,13 +552,12 @@ PISA_PF_HD void pf_value_bin(PfValue &v, const double *eta, double d, double e, 
 // the direct form's entry, then the prior terms in ascending j through the same compensated addition
 template <int KIND, int J>
 PISA_PF_HD double pf_value_end(const PfValue &v, const double *eta, const double *ips, const double *c) {
-    constexpr double w = PfKind<KIND>::w;
     double acc = v.sum + v.comp, comp = 0.0;
     if (KIND == PF_CHI2 && !v.differs) acc = 0.0;
 #pragma unroll
     for (int j = 0; j < J; j++) {
-        const double p = ips[j] * (eta[j] + c[j]);
-        const double pp = w * (p * p);
+        double p;
+        const double pp = pf_prior<KIND>(ips[j], eta[j], c[j], p);
         pf_two_sum(acc, comp, PfKind<KIND>::is_llh ? -pp : pp);
     }
     return acc + comp;

@@ -9,10 +9,8 @@
 // lane (k_t is the fit's `arg`, or one k0 for all), so nothing is staged through LDS: a lane reads its own data row,
 // its template's row and responses straight from memory.  That is one sweep against the fit's five or so times K
 // templates: the simple form is the right one here.  The bits of row t depend on row t of D, row k_t of E / S2 / R /
-// center / bounds and eta[t] alone.
-#include "common.hpp"
-#include "ensemble_device.hpp"
-#include "profile_device.hpp"
+// center / bounds and eta[t] alone.  The entry point's checks are `pf_check` of profile_kernel.hpp, the fit's own.
+#include "profile_kernel.hpp"   // (the checks of the launch layer: `pf_check`)
 
 namespace pisa {
 
@@ -115,14 +113,10 @@ PISA_API int pisa_hip_profiled_hesse(int32_t kind, const double *d_data, const d
                                      int64_t n_trials, int64_t n_templates, int64_t n_bins,
                                      const int32_t *d_k_of_trial, int32_t k0, const double *d_eta, double *d_cov,
                                      int32_t *d_trial_status, int32_t *d_status, void *stream) {
-    if (kind < PISA_HIP_METRIC_LLH || kind > PISA_HIP_METRIC_MOD_CHI2) return PISA_HIP_ERR_INVALID;
-    if (n_params < 1 || n_params > PISA_HIP_PROFILE_MAX_PARAMS) return PISA_HIP_ERR_INVALID;
-    if (!ens_check_sizes(n_trials, n_templates, n_bins)) return PISA_HIP_ERR_INVALID;
-    if (!d_data || !d_expected || !d_response || !d_status || !d_eta || !d_cov || !d_trial_status)
+    if (!pf_check(kind, n_params, PISA_HIP_PROFILE_MAX_PARAMS, n_trials, n_templates, n_bins, d_data, d_expected,
+                  d_sigma2, d_response, d_status, response_stride_k, d_lower || d_upper, bound_stride_k))
         return PISA_HIP_ERR_INVALID;
-    if (kind == PISA_HIP_METRIC_MOD_CHI2 && !d_sigma2) return PISA_HIP_ERR_INVALID;
-    if (response_stride_k != 0 && response_stride_k < (int64_t)n_params * n_bins) return PISA_HIP_ERR_INVALID;
-    if ((d_lower || d_upper) && bound_stride_k != 0 && bound_stride_k < (int64_t)n_params) return PISA_HIP_ERR_INVALID;
+    if (!d_eta || !d_cov || !d_trial_status) return PISA_HIP_ERR_INVALID;
     if (!d_k_of_trial && (k0 < 0 || k0 >= n_templates)) return PISA_HIP_ERR_INVALID;
     const int64_t blocks = (n_trials + PH_LANES - 1) / PH_LANES;
     if (blocks > PH_MAX_BLOCKS) return PISA_HIP_ERR_INVALID;

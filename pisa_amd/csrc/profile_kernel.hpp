@@ -1,7 +1,10 @@
 // profile_kernel.hpp -- the kernels and the launch layer of the profiled trial ensembles, shared by profile.hip (the
 // unbounded entry points) and profile_bounded.hip (eta fitted inside a box per template): one kernel template with a
 // BOUNDED flag, instantiated by the file that includes this header for the forms its entry points reach.  What the
-// kernel computes, its mapping and its placement rule are described at the top of profile.hip.
+// kernel computes, its mapping and its placement rule are described at the top of profile.hip.  The launch layer at the
+// end of the file -- the checks (`pf_check`), the filling of `PfArgs` (`pf_args_*`), the split of the reduced form
+// (`pf_plan_split`) and the run with its join (`pf_run_any`) -- serves profile_wide.hip's kernels as well, and
+// profile_hesse.hip takes the checks from it.
 //
 // BOUNDED.  The bounds lo / hi of template k ([J] doubles each) are wavefront-uniform: they are staged beside the
 // prior weights and the centres in LDS (2 J more doubles, in the bounded instantiations only) and read where they are
@@ -244,74 +247,124 @@ profile_join_kernel(const PfArgs a, int J) {
     for (int j = 0; j < J; j++) a.eta_best[t * J + j] = a.ws_eta[o * J + j];
 }
 
-// join buffer of the split reduced form: one per file that includes this header, so the bounded and the unbounded
-// entry points share no memory
-static DeviceScratch g_pf_work;
+// join buffer of the split reduced form: one per file that includes this header, so the bounded, the unbounded and
+// the wide entry points share no memory
+[[maybe_unused]] static DeviceScratch g_pf_work;   // (profile_hesse.hip has no reduced form)
 
-template <int KIND, int J, bool REDUCE, bool BOUNDED>
-static int pf_launch(const PfArgs &a, unsigned blocks, hipStream_t stream) {
-    const dim3 grid(blocks, REDUCE ? (unsigned)a.n_split : 1u);
-    hipLaunchKernelGGL((profile_kernel<KIND, J, REDUCE, BOUNDED>), grid, dim3(PF_LANES), 0, stream, a);
-    PISA_CHECK_LAUNCH("profile_kernel");
-    if (REDUCE && a.n_split > 1) {
-        const unsigned jb = (unsigned)((a.T + 255) / 256);
-        hipLaunchKernelGGL((profile_join_kernel<PfKind<KIND>::is_llh>), dim3(jb), dim3(256), 0, stream, a, J);
-        PISA_CHECK_LAUNCH("profile_join_kernel");
-    }
+// ------------------------------------------------------------------------------------------------ the launch layer
+// (of profile.hip, profile_bounded.hip and profile_wide.hip; profile_hesse.hip takes `pf_check`)
+
+// What the narrow, bounded, wide and hesse entry points check alike: the kind, 1 <= n_params <= most, the sizes, the
+// required inputs, sigma2 for mod_chi2, and both strides: the response of template k begins k * stride doubles in, 0
+// (shared by all templates) or whole [J][B] blocks; its bounds (`boxed`) likewise, 0 or whole [J] blocks.
+inline bool pf_check(int32_t kind, int32_t n_params, int32_t most, int64_t T, int64_t K, int64_t B, const double *D,
+                     const double *E, const double *S2, const double *R, const int32_t *status, int64_t r_stride_k,
+                     bool boxed, int64_t b_stride_k) {
+    return kind >= PISA_HIP_METRIC_LLH && kind <= PISA_HIP_METRIC_MOD_CHI2 && n_params >= 1 && n_params <= most &&
+           ens_check_sizes(T, K, B) && D && E && R && status && (kind != PISA_HIP_METRIC_MOD_CHI2 || S2) &&
+           (r_stride_k == 0 || r_stride_k >= (int64_t)n_params * B) &&
+           (!boxed || b_stride_k == 0 || b_stride_k >= (int64_t)n_params);
+}
+
+// the arguments of an entry point as the kernels take them: the inputs (bounds: null where the form has none) ...
+inline PfArgs pf_args_in(const double *D, const double *E, const double *S2, const double *R, int64_t r_stride_k,
+                         const double *ips, const double *center, int32_t *status, const double *lower = nullptr,
+                         const double *upper = nullptr, int64_t b_stride_k = 0) {
+    PfArgs a = {};
+    a.D = D, a.E = E, a.S2 = S2, a.R = R, a.r_stride_k = r_stride_k, a.ips = ips, a.center = center;
+    a.lower = lower, a.upper = upper, a.b_stride_k = b_stride_k, a.status = status;
+    return a;
+}
+
+// ... with the full output ...
+inline PfArgs pf_args_full(PfArgs a, double *value, double *eta, int32_t *n_iter, int32_t *pair_status) {
+    a.value = value, a.eta = eta, a.n_iter = n_iter, a.pair_status = pair_status;
+    return a;
+}
+
+// ... or the reduced one
+inline PfArgs pf_args_best(PfArgs a, const double *offset, int32_t k0, double *best, int32_t *arg, double *at,
+                           double *eta_best, double *eta_at, int32_t *trial_status) {
+    a.offset = offset, a.k0 = k0;
+    a.best = best, a.arg = arg, a.at = at, a.eta_best = eta_best, a.eta_at = eta_at, a.trial_status = trial_status;
+    return a;
+}
+
+// The split of the reduced form: with fewer row units (strips of the narrow form, trials of the wide one) than `fill`
+// workgroups the templates of a unit go to several workgroups, in contiguous ranges that all hold a template; the
+// ranges' results go through `work`.
+inline int pf_plan_split(PfArgs &a, int64_t units, int64_t fill, int n_params, DeviceScratch &work) {
+    const int64_t K = a.K, T = a.T;
+    if (units >= fill || K <= 1) return PISA_HIP_OK;
+    int64_t want = (fill + units - 1) / units;
+    if (want > K) want = K;
+    if (want > PF_MAX_SPLIT) want = PF_MAX_SPLIT;
+    const int64_t chunk = (K + want - 1) / want;
+    const int64_t n_split = (K + chunk - 1) / chunk;
+    if (n_split <= 1) return PISA_HIP_OK;
+    const int64_t per = n_split * T;               // doubles: best, eta [J], and arg + flags as one more; + T
+    double *w;
+    const int rc = work.reserve(per * (2 + n_params) + T, &w);
+    if (rc != PISA_HIP_OK) return rc;
+    a.n_split = (int)n_split;
+    a.k_chunk = (int)chunk;
+    a.ws_best = w;
+    a.ws_eta = w + per;
+    a.ws_arg = reinterpret_cast<int32_t *>(w + per * (1 + n_params));
+    a.ws_st = a.ws_arg + per;
+    a.ws_st_at = a.ws_st + per;
     return PISA_HIP_OK;
 }
 
-template <bool REDUCE, bool BOUNDED>
-static int pf_run(int32_t kind, int64_t response_stride_k, int32_t n_params, int32_t max_iter, int64_t T, int64_t K,
-                  int64_t B, PfArgs a, void *stream) {
-    if (kind < PISA_HIP_METRIC_LLH || kind > PISA_HIP_METRIC_MOD_CHI2) return PISA_HIP_ERR_INVALID;
-    if (n_params < 1 || n_params > PISA_HIP_PROFILE_MAX_PARAMS) return PISA_HIP_ERR_INVALID;
+// One run of a matrix entry point, narrow or wide: the checks, the sizes, the split, the launch of the form's kernel
+// (`launch(kind constant, a, grid, stream)`, which returns after PISA_CHECK_LAUNCH) and the join of a split run.
+// `rows`: the trials of one row unit of the form (a strip of 64, or 1); full output: a workgroup per (unit, template).
+template <bool REDUCE, class L>
+static int pf_run_any(int32_t kind, int32_t n_params, int32_t most, int32_t max_iter, int64_t T, int64_t K, int64_t B,
+                      int rows, int64_t fill, bool boxed, PfArgs a, void *stream, L launch) {
+    if (!pf_check(kind, n_params, most, T, K, B, a.D, a.E, a.S2, a.R, a.status, a.r_stride_k, boxed, a.b_stride_k))
+        return PISA_HIP_ERR_INVALID;
     if (max_iter < 0 || max_iter > PF_MAX_ITER) return PISA_HIP_ERR_INVALID;
-    if (!ens_check_sizes(T, K, B)) return PISA_HIP_ERR_INVALID;
-    if (!a.D || !a.E || !a.R || !a.status) return PISA_HIP_ERR_INVALID;
-    if (kind == PISA_HIP_METRIC_MOD_CHI2 && !a.S2) return PISA_HIP_ERR_INVALID;
-    // the response of template k begins k * stride doubles in: 0 (shared by all templates) or whole [J][B] blocks
-    if (response_stride_k != 0 && response_stride_k < (int64_t)n_params * B) return PISA_HIP_ERR_INVALID;
-    // the bounds of template k likewise: 0 (one [J] block for all templates) or whole [J] blocks
-    if (BOUNDED && a.b_stride_k != 0 && a.b_stride_k < (int64_t)n_params) return PISA_HIP_ERR_INVALID;
     if (!ens_check_outputs<REDUCE>(a.value, a.best, a.arg, a.at, a.k0, K)) return PISA_HIP_ERR_INVALID;
     if (REDUCE ? (!a.eta_best || !a.eta_at || !a.trial_status) : !a.pair_status) return PISA_HIP_ERR_INVALID;
-    const int64_t strips = (T + PF_LANES - 1) / PF_LANES;
-    const int64_t blocks = REDUCE ? strips : strips * K;   // full: one workgroup per (strip, template)
+    const int64_t units = (T + rows - 1) / rows;
+    const int64_t blocks = REDUCE ? units : units * K;
     // (a grid holds at most 2^32 threads: 2^26 workgroups of 64 lanes)
     if (blocks > PF_MAX_BLOCKS) return PISA_HIP_ERR_INVALID;
-    a.r_stride_k = response_stride_k;
     a.B = B;
     a.T = (int)T;
     a.K = (int)K;
     a.max_iter = max_iter;
     a.n_split = 1;
     a.k_chunk = (int)K;
-    if (REDUCE && strips < PF_FILL_BLOCKS && K > 1) {
-        // too few strips to fill the device: the templates of a strip go to several workgroups
-        int64_t want = (PF_FILL_BLOCKS + strips - 1) / strips;
-        if (want > K) want = K;
-        if (want > PF_MAX_SPLIT) want = PF_MAX_SPLIT;
-        const int64_t chunk = (K + want - 1) / want;
-        const int64_t n_split = (K + chunk - 1) / chunk;   // (every range holds a template)
-        if (n_split > 1) {
-            const int64_t per = n_split * T;               // doubles: best, eta [J], and arg + flags as one more; + T
-            double *w;
-            const int rc = g_pf_work.reserve(per * (2 + n_params) + T, &w);
-            if (rc != PISA_HIP_OK) return rc;
-            a.n_split = (int)n_split;
-            a.k_chunk = (int)chunk;
-            a.ws_best = w;
-            a.ws_eta = w + per;
-            a.ws_arg = reinterpret_cast<int32_t *>(w + per * (1 + n_params));
-            a.ws_st = a.ws_arg + per;
-            a.ws_st_at = a.ws_st + per;
-        }
+    if (REDUCE) {
+        const int rc = pf_plan_split(a, units, fill, n_params, g_pf_work);
+        if (rc != PISA_HIP_OK) return rc;
     }
     hipStream_t st = as_stream(stream);
+    const dim3 grid((unsigned)blocks, (unsigned)a.n_split);
     return dispatch_int<PF_LLH, PF_POISSON_LLH, PF_CHI2, PF_MOD_CHI2>(kind, [&](auto c) {
+        const int rc = launch(c, a, grid, st);
+        if (rc != PISA_HIP_OK || a.n_split == 1) return rc;
+        const unsigned jb = (unsigned)((a.T + 255) / 256);
+        hipLaunchKernelGGL((profile_join_kernel<PfKind<decltype(c)::value>::is_llh>), dim3(jb), dim3(256), 0, st, a,
+                           n_params);
+        PISA_CHECK_LAUNCH("profile_join_kernel");
+        return PISA_HIP_OK;
+    });
+}
+
+// the narrow form: a row unit is a strip of 64 trials, J a template parameter
+template <bool REDUCE, bool BOUNDED>
+static int pf_run(int32_t kind, int32_t n_params, int32_t max_iter, int64_t T, int64_t K, int64_t B, const PfArgs &a,
+                  void *stream) {
+    return pf_run_any<REDUCE>(kind, n_params, PISA_HIP_PROFILE_MAX_PARAMS, max_iter, T, K, B, PF_LANES, PF_FILL_BLOCKS,
+                              BOUNDED, a, stream, [&](auto c, const PfArgs &aa, dim3 grid, hipStream_t st) {
         return dispatch_int<1, 2, 3, 4, 5, 6, 7, 8>(n_params, [&](auto j) {
-            return pf_launch<decltype(c)::value, decltype(j)::value, REDUCE, BOUNDED>(a, (unsigned)blocks, st);
+            hipLaunchKernelGGL((profile_kernel<decltype(c)::value, decltype(j)::value, REDUCE, BOUNDED>), grid,
+                               dim3(PF_LANES), 0, st, aa);
+            PISA_CHECK_LAUNCH("profile_kernel");
+            return PISA_HIP_OK;
         });
     });
 }

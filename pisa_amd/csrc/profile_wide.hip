@@ -14,7 +14,8 @@
 // J and `bounded` are run-time values (the LDS of the response chunk is sized by J at the launch); the kind and the
 // output form are template parameters: 8 kernels.  Full output: grid.x = t K + k.  Reduced output: grid.x = t, the
 // workgroup walks its range of templates in ascending order (grid.y ranges where the trials are too few to fill the
-// device) and profile_join_kernel of profile_kernel.hpp joins the ranges through this file's own buffer.
+// device) and profile_join_kernel of profile_kernel.hpp joins the ranges through this file's own buffer.  The checks,
+// the split and the launch with its join are `pf_run_any` of profile_kernel.hpp, with a trial as the row unit.
 #include "profile_kernel.hpp"
 #include "profile_wide_device.hpp"
 
@@ -145,68 +146,18 @@ profile_wide_kernel(const PfArgs a, const int J, const int bounded) {
     if (negative) a.status[0] = PISA_HIP_ERR_NEGATIVE;   // (every writer stores the same word)
 }
 
-template <int KIND, bool REDUCE>
-static int pfw_launch(const PfArgs &a, int J, int bounded, unsigned blocks, hipStream_t stream) {
-    const dim3 grid(blocks, REDUCE ? (unsigned)a.n_split : 1u);
-    const size_t lds = sizeof(PfwShared) + (size_t)pfw_chunk_doubles(J) * sizeof(double);
-    hipLaunchKernelGGL((profile_wide_kernel<KIND, REDUCE>), grid, dim3(PFW_LANES), lds, stream, a, J, bounded);
-    PISA_CHECK_LAUNCH("profile_wide_kernel");
-    if (REDUCE && a.n_split > 1) {
-        const unsigned jb = (unsigned)((a.T + 255) / 256);
-        hipLaunchKernelGGL((profile_join_kernel<PfKind<KIND>::is_llh>), dim3(jb), dim3(256), 0, stream, a, J);
-        PISA_CHECK_LAUNCH("profile_join_kernel");
-    }
-    return PISA_HIP_OK;
-}
-
+// a row unit is one trial; J and `bounded` are run-time values, the response chunk's LDS is sized by J here
 template <bool REDUCE>
-static int pfw_run(int32_t kind, int64_t response_stride_k, int32_t n_params, int32_t max_iter, int64_t T, int64_t K,
-                   int64_t B, PfArgs a, void *stream) {
-    if (kind < PISA_HIP_METRIC_LLH || kind > PISA_HIP_METRIC_MOD_CHI2) return PISA_HIP_ERR_INVALID;
-    if (n_params < 1 || n_params > PISA_HIP_PROFILE_WIDE_MAX_PARAMS) return PISA_HIP_ERR_INVALID;
-    if (max_iter < 0 || max_iter > PF_MAX_ITER) return PISA_HIP_ERR_INVALID;
-    if (!ens_check_sizes(T, K, B)) return PISA_HIP_ERR_INVALID;
-    if (!a.D || !a.E || !a.R || !a.status) return PISA_HIP_ERR_INVALID;
-    if (kind == PISA_HIP_METRIC_MOD_CHI2 && !a.S2) return PISA_HIP_ERR_INVALID;
-    if (response_stride_k != 0 && response_stride_k < (int64_t)n_params * B) return PISA_HIP_ERR_INVALID;
+static int pfw_run(int32_t kind, int32_t n_params, int32_t max_iter, int64_t T, int64_t K, int64_t B, const PfArgs &a,
+                   void *stream) {
     const int bounded = a.lower || a.upper;
-    if (bounded && a.b_stride_k != 0 && a.b_stride_k < (int64_t)n_params) return PISA_HIP_ERR_INVALID;
-    if (!ens_check_outputs<REDUCE>(a.value, a.best, a.arg, a.at, a.k0, K)) return PISA_HIP_ERR_INVALID;
-    if (REDUCE ? (!a.eta_best || !a.eta_at || !a.trial_status) : !a.pair_status) return PISA_HIP_ERR_INVALID;
-    const int64_t blocks = REDUCE ? T : T * K;   // full: one workgroup per pair
-    // (a grid holds at most 2^32 threads: 2^26 workgroups of 64 lanes)
-    if (blocks > PF_MAX_BLOCKS) return PISA_HIP_ERR_INVALID;
-    a.r_stride_k = response_stride_k;
-    a.B = B;
-    a.T = (int)T;
-    a.K = (int)K;
-    a.max_iter = max_iter;
-    a.n_split = 1;
-    a.k_chunk = (int)K;
-    if (REDUCE && T < PFW_FILL_BLOCKS && K > 1) {
-        // too few trials to fill the device: the templates of a trial go to several workgroups
-        int64_t want = (PFW_FILL_BLOCKS + T - 1) / T;
-        if (want > K) want = K;
-        if (want > PF_MAX_SPLIT) want = PF_MAX_SPLIT;
-        const int64_t chunk = (K + want - 1) / want;
-        const int64_t n_split = (K + chunk - 1) / chunk;   // (every range holds a template)
-        if (n_split > 1) {
-            const int64_t per = n_split * T;               // doubles: best, eta [J], and arg + flags as one more; + T
-            double *w;
-            const int rc = g_pf_work.reserve(per * (2 + n_params) + T, &w);
-            if (rc != PISA_HIP_OK) return rc;
-            a.n_split = (int)n_split;
-            a.k_chunk = (int)chunk;
-            a.ws_best = w;
-            a.ws_eta = w + per;
-            a.ws_arg = reinterpret_cast<int32_t *>(w + per * (1 + n_params));
-            a.ws_st = a.ws_arg + per;
-            a.ws_st_at = a.ws_st + per;
-        }
-    }
-    hipStream_t st = as_stream(stream);
-    return dispatch_int<PF_LLH, PF_POISSON_LLH, PF_CHI2, PF_MOD_CHI2>(kind, [&](auto c) {
-        return pfw_launch<decltype(c)::value, REDUCE>(a, n_params, bounded, (unsigned)blocks, st);
+    return pf_run_any<REDUCE>(kind, n_params, PISA_HIP_PROFILE_WIDE_MAX_PARAMS, max_iter, T, K, B, 1, PFW_FILL_BLOCKS,
+                              bounded, a, stream, [&](auto c, const PfArgs &aa, dim3 grid, hipStream_t st) {
+        const size_t lds = sizeof(PfwShared) + (size_t)pfw_chunk_doubles(n_params) * sizeof(double);
+        hipLaunchKernelGGL((profile_wide_kernel<decltype(c)::value, REDUCE>), grid, dim3(PFW_LANES), lds, st, aa,
+                           n_params, bounded);
+        PISA_CHECK_LAUNCH("profile_wide_kernel");
+        return PISA_HIP_OK;
     });
 }
 
@@ -220,11 +171,10 @@ PISA_API int pisa_hip_profiled_metric_matrix_wide(int32_t kind, const double *d_
                                                   int64_t n_trials, int64_t n_templates, int64_t n_bins,
                                                   double *d_value, double *d_eta, int32_t *d_n_iter,
                                                   int32_t *d_pair_status, int32_t *d_status, void *stream) {
-    PfArgs a = {};
-    a.D = d_data, a.E = d_expected, a.S2 = d_sigma2, a.R = d_response, a.ips = d_inv_prior_sigma, a.center = d_center;
-    a.lower = d_lower, a.upper = d_upper, a.b_stride_k = bound_stride_k;
-    a.value = d_value, a.eta = d_eta, a.n_iter = d_n_iter, a.pair_status = d_pair_status, a.status = d_status;
-    return pfw_run<false>(kind, response_stride_k, n_params, max_iter, n_trials, n_templates, n_bins, a, stream);
+    const PfArgs in = pf_args_in(d_data, d_expected, d_sigma2, d_response, response_stride_k, d_inv_prior_sigma,
+                                 d_center, d_status, d_lower, d_upper, bound_stride_k);
+    const PfArgs a = pf_args_full(in, d_value, d_eta, d_n_iter, d_pair_status);
+    return pfw_run<false>(kind, n_params, max_iter, n_trials, n_templates, n_bins, a, stream);
 }
 
 PISA_API int pisa_hip_profiled_metric_matrix_best_wide(int32_t kind, const double *d_data, const double *d_expected,
@@ -237,11 +187,8 @@ PISA_API int pisa_hip_profiled_metric_matrix_best_wide(int32_t kind, const doubl
                                                        int64_t n_bins, double *d_best, int32_t *d_arg, double *d_at,
                                                        double *d_eta_best, double *d_eta_at, int32_t *d_trial_status,
                                                        int32_t *d_status, void *stream) {
-    PfArgs a = {};
-    a.D = d_data, a.E = d_expected, a.S2 = d_sigma2, a.R = d_response, a.ips = d_inv_prior_sigma, a.center = d_center;
-    a.lower = d_lower, a.upper = d_upper, a.b_stride_k = bound_stride_k;
-    a.offset = d_offset, a.k0 = k0;
-    a.best = d_best, a.arg = d_arg, a.at = d_at, a.eta_best = d_eta_best, a.eta_at = d_eta_at;
-    a.trial_status = d_trial_status, a.status = d_status;
-    return pfw_run<true>(kind, response_stride_k, n_params, max_iter, n_trials, n_templates, n_bins, a, stream);
+    const PfArgs in = pf_args_in(d_data, d_expected, d_sigma2, d_response, response_stride_k, d_inv_prior_sigma,
+                                 d_center, d_status, d_lower, d_upper, bound_stride_k);
+    const PfArgs a = pf_args_best(in, d_offset, k0, d_best, d_arg, d_at, d_eta_best, d_eta_at, d_trial_status);
+    return pfw_run<true>(kind, n_params, max_iter, n_trials, n_templates, n_bins, a, stream);
 }

@@ -8,7 +8,11 @@
 // the bins in ascending order, the entries of the Cholesky factor and of both substitutions in ascending m.  Here a
 // chain is owned by one lane, which walks it in that order; the per-bin quantities (mu, phi, phi', phi'') come from
 // lanes that own bins and are handed over through shared memory.  No floating-point value is ever reduced across
-// lanes, and no operation is fused or reordered: at J <= 8 the results are the bits of profile_device.hpp.
+// lanes, and no operation is fused or reordered: at J <= 8 the results are the bits of profile_device.hpp.  The finite
+// test, phi / phi' / phi'', the bin's term of `scale` and the prior term are that file's own functions (`pf_finite`,
+// `pf_phi`, `pf_scale_term`, `pf_prior`, `pf_prior_join`); what stands here is the wide form's own: the mapping of
+// chains to lanes, mu over the staged chunk, the cooperative factor and solve, the judgement of a trial point on the
+// scalar lane between their phases, and the executor.
 //
 // Form.  Every cooperative phase is a function of (shared state, lane): it reads what earlier phases wrote and writes
 // locations no other lane reads or writes in the same phase.  A driver (`pfw_*` taking an executor X) strings the
@@ -120,8 +124,7 @@ PISA_PF_HD void pfw_bins(PfwShared &S, const double *R, int lane, int nb) {
     if (lane >= nb) return;
     const int J = S.J;
     const double d = S.cD[lane], e = S.cE[lane], s2 = S.cS2[lane];
-    const bool finite = (d == d) && (e == e) && !isinf(d) && !isinf(e);
-    if (!finite) {
+    if (!pf_finite(d, e)) {
         S.use[lane] = PFW_SKIP;
         return;
     }
@@ -140,24 +143,12 @@ PISA_PF_HD void pfw_bins(PfwShared &S, const double *R, int lane, int nb) {
     }
     const double m = mu < PF_SMALL_POS ? PF_SMALL_POS : mu;
     double phi, p1, p2;
-    if (PfKind<KIND>::is_llh) {
-        const double q = d / m;
-        phi = m - d * log(m);
-        p1 = 1.0 - q;
-        p2 = q / m;
-    } else {
-        const double v = KIND == PF_MOD_CHI2 ? s2 + m : m;
-        const double rr = d - m, a = rr / v;
-        const double u = (KIND == PF_MOD_CHI2 ? d + s2 : d) / v;
-        phi = rr * a;
-        p1 = -(a * (2.0 + a));
-        p2 = 2.0 * (u * u) / v;
-    }
+    pf_phi<KIND>(d, m, s2, phi, p1, p2);
     S.use[lane] = PFW_USE;
     S.phi[lane] = phi;
     S.p1[lane] = p1;
     S.p2[lane] = p2;
-    S.sc[lane] = (fabs(phi) + 1.0) + fabs(p1) * reach;
+    S.sc[lane] = pf_scale_term(phi, p1, reach);
 }
 
 // the number of tiles of the lower triangle, and tile q's block row and column
@@ -323,21 +314,20 @@ PISA_PF_HD void pfw_solve(PfwShared &S, X &x) {
 // `pf_decide_any` after a sweep at eta_t.  Sets S.done when the pair has its final eta.
 template <int KIND, class X>
 PISA_PF_HD void pfw_decide(PfwShared &S, X &x, int32_t max_iter) {
-    constexpr double w = PfKind<KIND>::w;
     const int J = S.J;
     // the priors join: g and the diagonal of H per coordinate, Phi and `scale` as chains in ascending j; the scalar
     // lane then judges the trial point
     x.each([&](int lane) {
         if (lane < J) {
-            const double p = S.ips[lane] * (S.eta_t[lane] + S.cen[lane]);
-            S.g[lane] += (2.0 * w) * (S.ips[lane] * p);
-            S.H[pf_at(lane, lane)] += (2.0 * w) * (S.ips[lane] * S.ips[lane]);
+            double p;
+            pf_prior<KIND>(S.ips[lane], S.eta_t[lane], S.cen[lane], p);
+            pf_prior_join<KIND>(S.ips[lane], p, S.g[lane], S.H[pf_at(lane, lane)]);
         }
         if (lane != PFW_SCALAR) return;
         double phi_t = S.phi_s + S.phi_c, scale = S.scale;
         for (int j = 0; j < J; j++) {
-            const double p = S.ips[j] * (S.eta_t[j] + S.cen[j]);
-            const double pp = w * (p * p);
+            double p;
+            const double pp = pf_prior<KIND>(S.ips[j], S.eta_t[j], S.cen[j], p);
             phi_t += pp;
             scale += pp;
         }
@@ -448,9 +438,8 @@ PISA_PF_HD void pfw_value_bins(PfwShared &S, const double *R, int lane, int nb) 
     if (lane >= nb) return;
     const int J = S.J;
     const double d = S.cD[lane], e = S.cE[lane], s2 = S.cS2[lane];
-    const bool finite = (d == d) && (e == e) && !isinf(d) && !isinf(e);
     int mark = PFW_SKIP;
-    if (finite) {
+    if (pf_finite(d, e)) {
         if (d < 0.0 || e < 0.0) mark |= PFW_NEGATIVE;
         double lam = e;
         for (int j = 0; j < J; j++) {
@@ -489,12 +478,11 @@ PISA_PF_HD void pfw_value_chain(PfwShared &S, int lane, int nb) {
 template <int KIND>
 PISA_PF_HD void pfw_value_end(PfwShared &S, int lane) {
     if (lane != PFW_SCALAR) return;
-    constexpr double w = PfKind<KIND>::w;
     double acc = S.v_sum + S.v_comp, comp = 0.0;
     if (KIND == PF_CHI2 && !S.differs) acc = 0.0;
     for (int j = 0; j < S.J; j++) {
-        const double p = S.ips[j] * (S.eta[j] + S.cen[j]);
-        const double pp = w * (p * p);
+        double p;
+        const double pp = pf_prior<KIND>(S.ips[j], S.eta[j], S.cen[j], p);
         pf_two_sum(acc, comp, PfKind<KIND>::is_llh ? -pp : pp);
     }
     S.value = acc + comp;

@@ -975,6 +975,69 @@ def _bound_args(what, lower, upper, n_k, n_j):
     return out[0], out[1], n_j if per_template else 0
 
 
+def _profiled_call(what, wide, kind, data, expected, response, sigma2, inv_prior_sigma, center, max_iter, lower, upper):
+    """the checked inputs of a profiled matrix call -> (the entry points' suffix, the arguments they begin with: [kind
+    ... center, (the bounds)], n_params, [max_iter, T, K, B], the tensors behind the pointers, data first).  The narrow
+    form without bounds goes to the unbounded entry points, with bounds to the `_bounded` ones; the wide entry points
+    take the bounds always (NULL: none)."""
+    (data, expected, response, sigma2, ips, center, stride, n_t, n_k, n_bins, n_j) = _profile_args(
+        what, kind, data, expected, response, sigma2, inv_prior_sigma, center, max_iter,
+        _lib.PROFILE_WIDE_MAX_PARAMS if wide else _lib.PROFILE_MAX_PARAMS)
+    bounded = lower is not None or upper is not None
+    head = [METRIC_KIND[kind], _ptr(data), _ptr(expected), _ptr(sigma2), _ptr(response), stride, _ptr(ips),
+            _ptr(center)]
+    if bounded:
+        lower, upper, b_stride = _bound_args(what, lower, upper, n_k, n_j)
+        head += [_ptr(lower), _ptr(upper), b_stride]
+    elif wide:
+        head += [None, None, 0]
+    keep = (data, expected, response, sigma2, ips, center, lower, upper)     # (alive until the launch)
+    return "_wide" if wide else "_bounded" if bounded else "", head, n_j, [int(max_iter), n_t, n_k, n_bins], keep
+
+
+def _profiled_full(what, wide, kind, data, expected, response, sigma2, inv_prior_sigma, center, max_iter, want_eta,
+                   status, lower, upper):
+    """the body of `profiled_metric_matrix` and `profiled_metric_matrix_wide`"""
+    suffix, head, n_j, sizes, keep = _profiled_call(what, wide, kind, data, expected, response, sigma2, inv_prior_sigma,
+                                                    center, max_iter, lower, upper)
+    n_t, n_k, dev = sizes[1], sizes[2], keep[0].device
+    value = torch.empty((n_t, n_k), dtype=F8, device=dev)
+    eta = torch.empty((n_t, n_k, n_j), dtype=F8, device=dev) if want_eta else None
+    n_iter = torch.empty((n_t, n_k), dtype=torch.int32, device=dev)
+    pair_status = torch.empty((n_t, n_k), dtype=torch.int32, device=dev)
+    entry = getattr(_lib.lib(), "pisa_hip_profiled_metric_matrix" + suffix)
+
+    def launch(status):
+        _lib.check(entry(*head, n_j, *sizes, _ptr(value), _ptr(eta), _ptr(n_iter), _ptr(pair_status), _ptr(status),
+                         _stream()))
+
+    _with_status(status, dev, launch)
+    return dict(value=value, eta=eta, n_iter=n_iter, status=pair_status)
+
+
+def _profiled_best(what, wide, kind, data, expected, response, sigma2, inv_prior_sigma, center, offset, k0, max_iter,
+                   status, lower, upper):
+    """the body of `profiled_metric_matrix_best` and `profiled_metric_matrix_best_wide`"""
+    suffix, head, n_j, sizes, keep = _profiled_call(what, wide, kind, data, expected, response, sigma2, inv_prior_sigma,
+                                                    center, max_iter, lower, upper)
+    n_t, n_k, dev = sizes[1], sizes[2], keep[0].device
+    offset = _offset_arg(what, offset, n_k)
+    best = torch.empty(n_t, dtype=F8, device=dev)
+    arg = torch.empty(n_t, dtype=torch.int32, device=dev)
+    at = torch.empty(n_t, dtype=F8, device=dev)
+    eta_best = torch.empty((n_t, n_j), dtype=F8, device=dev)
+    eta_at = torch.empty((n_t, n_j), dtype=F8, device=dev)
+    trial_status = torch.empty(n_t, dtype=torch.int32, device=dev)
+    entry = getattr(_lib.lib(), "pisa_hip_profiled_metric_matrix_best" + suffix)
+
+    def launch(status):
+        _lib.check(entry(*head, _ptr(offset), int(k0), n_j, *sizes, _ptr(best), _ptr(arg), _ptr(at), _ptr(eta_best),
+                         _ptr(eta_at), _ptr(trial_status), _ptr(status), _stream()))
+
+    _with_status(status, dev, launch)
+    return dict(best=best, arg=arg, at=at, eta_best=eta_best, eta_at=eta_at, status=trial_status)
+
+
 def profiled_metric_matrix(kind, data, expected, response, sigma2=None, inv_prior_sigma=None, center=None,
                            max_iter=32, want_eta=True, status=None, lower=None, upper=None):
     """`metric_matrix` with linearised nuisance parameters fitted per (trial, template) pair
@@ -989,31 +1052,8 @@ def profiled_metric_matrix(kind, data, expected, response, sigma2=None, inv_prio
     lower == upper pins a parameter).  A fitted coordinate on a bound equals the bound; a template with lower > upper
     or a NaN bound gives pairs flagged `_lib.PROFILE_BAD_BOUNDS` that stay at eta = 0.  With both None the call is
     what it was before the arguments existed."""
-    (data, expected, response, sigma2, ips, center, stride, n_t, n_k, n_bins, n_j) = _profile_args(
-        "profiled_metric_matrix", kind, data, expected, response, sigma2, inv_prior_sigma, center, max_iter)
-    bounded = lower is not None or upper is not None
-    if bounded:
-        lower, upper, b_stride = _bound_args("profiled_metric_matrix", lower, upper, n_k, n_j)
-    dev = data.device
-    value = torch.empty((n_t, n_k), dtype=F8, device=dev)
-    eta = torch.empty((n_t, n_k, n_j), dtype=F8, device=dev) if want_eta else None
-    n_iter = torch.empty((n_t, n_k), dtype=torch.int32, device=dev)
-    pair_status = torch.empty((n_t, n_k), dtype=torch.int32, device=dev)
-
-    def launch(status):
-        if bounded:
-            _lib.check(_lib.lib().pisa_hip_profiled_metric_matrix_bounded(
-                METRIC_KIND[kind], _ptr(data), _ptr(expected), _ptr(sigma2), _ptr(response), stride, _ptr(ips),
-                _ptr(center), _ptr(lower), _ptr(upper), b_stride, n_j, int(max_iter), n_t, n_k, n_bins, _ptr(value),
-                _ptr(eta), _ptr(n_iter), _ptr(pair_status), _ptr(status), _stream()))
-            return
-        _lib.check(_lib.lib().pisa_hip_profiled_metric_matrix(
-            METRIC_KIND[kind], _ptr(data), _ptr(expected), _ptr(sigma2), _ptr(response), stride, _ptr(ips),
-            _ptr(center), n_j, int(max_iter), n_t, n_k, n_bins, _ptr(value), _ptr(eta), _ptr(n_iter),
-            _ptr(pair_status), _ptr(status), _stream()))
-
-    _with_status(status, dev, launch)
-    return dict(value=value, eta=eta, n_iter=n_iter, status=pair_status)
+    return _profiled_full("profiled_metric_matrix", False, kind, data, expected, response, sigma2, inv_prior_sigma,
+                          center, max_iter, want_eta, status, lower, upper)
 
 
 def profiled_metric_matrix_best(kind, data, expected, response, sigma2=None, inv_prior_sigma=None, center=None,
@@ -1023,35 +1063,8 @@ def profiled_metric_matrix_best(kind, data, expected, response, sigma2=None, inv
     [T, J]: the fitted displacements at both columns, status [T] int32: the flags of the pair at arg OR those of
     the pair at k0), bit for bit the reduction of the full output.  lower / upper: as in `profiled_metric_matrix`
     (`pisa_hip_profiled_metric_matrix_best_bounded`)"""
-    (data, expected, response, sigma2, ips, center, stride, n_t, n_k, n_bins, n_j) = _profile_args(
-        "profiled_metric_matrix_best", kind, data, expected, response, sigma2, inv_prior_sigma, center, max_iter)
-    bounded = lower is not None or upper is not None
-    if bounded:
-        lower, upper, b_stride = _bound_args("profiled_metric_matrix_best", lower, upper, n_k, n_j)
-    dev = data.device
-    offset = _offset_arg("profiled_metric_matrix_best", offset, n_k)
-    best = torch.empty(n_t, dtype=F8, device=dev)
-    arg = torch.empty(n_t, dtype=torch.int32, device=dev)
-    at = torch.empty(n_t, dtype=F8, device=dev)
-    eta_best = torch.empty((n_t, n_j), dtype=F8, device=dev)
-    eta_at = torch.empty((n_t, n_j), dtype=F8, device=dev)
-    trial_status = torch.empty(n_t, dtype=torch.int32, device=dev)
-
-    def launch(status):
-        if bounded:
-            _lib.check(_lib.lib().pisa_hip_profiled_metric_matrix_best_bounded(
-                METRIC_KIND[kind], _ptr(data), _ptr(expected), _ptr(sigma2), _ptr(response), stride, _ptr(ips),
-                _ptr(center), _ptr(lower), _ptr(upper), b_stride, _ptr(offset), int(k0), n_j, int(max_iter), n_t, n_k,
-                n_bins, _ptr(best), _ptr(arg), _ptr(at), _ptr(eta_best), _ptr(eta_at), _ptr(trial_status),
-                _ptr(status), _stream()))
-            return
-        _lib.check(_lib.lib().pisa_hip_profiled_metric_matrix_best(
-            METRIC_KIND[kind], _ptr(data), _ptr(expected), _ptr(sigma2), _ptr(response), stride, _ptr(ips),
-            _ptr(center), _ptr(offset), int(k0), n_j, int(max_iter), n_t, n_k, n_bins, _ptr(best), _ptr(arg),
-            _ptr(at), _ptr(eta_best), _ptr(eta_at), _ptr(trial_status), _ptr(status), _stream()))
-
-    _with_status(status, dev, launch)
-    return dict(best=best, arg=arg, at=at, eta_best=eta_best, eta_at=eta_at, status=trial_status)
+    return _profiled_best("profiled_metric_matrix_best", False, kind, data, expected, response, sigma2, inv_prior_sigma,
+                          center, offset, k0, max_iter, status, lower, upper)
 
 
 def profiled_metric_matrix_wide(kind, data, expected, response, sigma2=None, inv_prior_sigma=None, center=None,
@@ -1061,56 +1074,16 @@ def profiled_metric_matrix_wide(kind, data, expected, response, sigma2=None, inv
     `_lib.PROFILE_WIDE_MAX_PARAMS` = 32 nuisance parameters, one wavefront per (trial, template) pair.  With both
     bounds None it is the unbounded fit, otherwise the bounded one; up to 8 parameters the outputs are bit for bit those
     of `profiled_metric_matrix`."""
-    what = "profiled_metric_matrix_wide"
-    (data, expected, response, sigma2, ips, center, stride, n_t, n_k, n_bins, n_j) = _profile_args(
-        what, kind, data, expected, response, sigma2, inv_prior_sigma, center, max_iter, _lib.PROFILE_WIDE_MAX_PARAMS)
-    b_stride = 0
-    if lower is not None or upper is not None:
-        lower, upper, b_stride = _bound_args(what, lower, upper, n_k, n_j)
-    dev = data.device
-    value = torch.empty((n_t, n_k), dtype=F8, device=dev)
-    eta = torch.empty((n_t, n_k, n_j), dtype=F8, device=dev) if want_eta else None
-    n_iter = torch.empty((n_t, n_k), dtype=torch.int32, device=dev)
-    pair_status = torch.empty((n_t, n_k), dtype=torch.int32, device=dev)
-
-    def launch(status):
-        _lib.check(_lib.lib().pisa_hip_profiled_metric_matrix_wide(
-            METRIC_KIND[kind], _ptr(data), _ptr(expected), _ptr(sigma2), _ptr(response), stride, _ptr(ips),
-            _ptr(center), _ptr(lower), _ptr(upper), b_stride, n_j, int(max_iter), n_t, n_k, n_bins, _ptr(value),
-            _ptr(eta), _ptr(n_iter), _ptr(pair_status), _ptr(status), _stream()))
-
-    _with_status(status, dev, launch)
-    return dict(value=value, eta=eta, n_iter=n_iter, status=pair_status)
+    return _profiled_full("profiled_metric_matrix_wide", True, kind, data, expected, response, sigma2, inv_prior_sigma,
+                          center, max_iter, want_eta, status, lower, upper)
 
 
 def profiled_metric_matrix_best_wide(kind, data, expected, response, sigma2=None, inv_prior_sigma=None, center=None,
                                      offset=None, k0=0, max_iter=32, status=None, lower=None, upper=None):
     """`profiled_metric_matrix_best` in the wide form (`pisa_hip_profiled_metric_matrix_best_wide`): the reduction of
     `profiled_metric_matrix_wide` per trial, bit for bit, with 1 to 32 nuisance parameters"""
-    what = "profiled_metric_matrix_best_wide"
-    (data, expected, response, sigma2, ips, center, stride, n_t, n_k, n_bins, n_j) = _profile_args(
-        what, kind, data, expected, response, sigma2, inv_prior_sigma, center, max_iter, _lib.PROFILE_WIDE_MAX_PARAMS)
-    b_stride = 0
-    if lower is not None or upper is not None:
-        lower, upper, b_stride = _bound_args(what, lower, upper, n_k, n_j)
-    dev = data.device
-    offset = _offset_arg(what, offset, n_k)
-    best = torch.empty(n_t, dtype=F8, device=dev)
-    arg = torch.empty(n_t, dtype=torch.int32, device=dev)
-    at = torch.empty(n_t, dtype=F8, device=dev)
-    eta_best = torch.empty((n_t, n_j), dtype=F8, device=dev)
-    eta_at = torch.empty((n_t, n_j), dtype=F8, device=dev)
-    trial_status = torch.empty(n_t, dtype=torch.int32, device=dev)
-
-    def launch(status):
-        _lib.check(_lib.lib().pisa_hip_profiled_metric_matrix_best_wide(
-            METRIC_KIND[kind], _ptr(data), _ptr(expected), _ptr(sigma2), _ptr(response), stride, _ptr(ips),
-            _ptr(center), _ptr(lower), _ptr(upper), b_stride, _ptr(offset), int(k0), n_j, int(max_iter), n_t, n_k,
-            n_bins, _ptr(best), _ptr(arg), _ptr(at), _ptr(eta_best), _ptr(eta_at), _ptr(trial_status), _ptr(status),
-            _stream()))
-
-    _with_status(status, dev, launch)
-    return dict(best=best, arg=arg, at=at, eta_best=eta_best, eta_at=eta_at, status=trial_status)
+    return _profiled_best("profiled_metric_matrix_best_wide", True, kind, data, expected, response, sigma2,
+                          inv_prior_sigma, center, offset, k0, max_iter, status, lower, upper)
 
 
 def profiled_hesse(kind, data, expected, response, eta, k, sigma2=None, inv_prior_sigma=None, center=None, lower=None,
