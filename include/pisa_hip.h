@@ -1388,6 +1388,42 @@ int pisa_hip_profiled_metric_matrix_best_wide(int32_t kind, const double *d_data
                                               double *d_at, double *d_eta_best, double *d_eta_at,
                                               int32_t *d_trial_status, int32_t *d_status, void *stream);
 
+/* The wide pair with the form of the nuisance response as an argument (csrc/profile_loglinear.hip; DESIGN.md section
+ * 4, "Profiled trial ensembles: the log-linear response").  form = _RESPONSE_LINEAR is the call of the _wide entry
+ * point, bit for bit.  form = _RESPONSE_LOGLINEAR reads d_response as rho and fits
+ *     mu_b(eta) = E[k][b] exp( rho[k][0][b] eta_0 + ... + rho[k][J-1][b] eta_(J-1) )
+ * (the exponent from 0 in ascending j, every product rounded; exp and the product with E rounded once each).  A bin
+ * with E == 0 or every rho == 0 does not respond: mu_b = E[k][b] exactly.  A responding bin whose mu is not finite or
+ * below 1e-10 puts the trial point outside the domain, and the damping halves the step as for a linear bin below
+ * 1e-10: an overflowing exp is a rejected trial point.  Gradient and Hessian are the exact ones of this model,
+ *     g_j = sum_b (phi' mu) rho_jb,    H_ij = sum_b (phi'' mu^2 + phi' mu) rho_ib rho_jb,
+ * and everything else -- priors, bounds, the Newton state machine, the stop rule, the status flags, the reported
+ * metric on mu(eta_hat), the reduced output and its join (through a buffer of this pair's own), placement, d_status
+ * -- is what the _wide pair states.  PISA_HIP_ERR_INVALID before any device access: as there, and for a form that is
+ * neither of the two. */
+#define PISA_HIP_RESPONSE_LINEAR 0
+#define PISA_HIP_RESPONSE_LOGLINEAR 1
+int pisa_hip_profiled_metric_matrix_wide_form(int32_t kind, int32_t form, const double *d_data,
+                                              const double *d_expected, const double *d_sigma2,
+                                              const double *d_response, int64_t response_stride_k,
+                                              const double *d_inv_prior_sigma, const double *d_center,
+                                              const double *d_lower, const double *d_upper, int64_t bound_stride_k,
+                                              int32_t n_params, int32_t max_iter, int64_t n_trials,
+                                              int64_t n_templates, int64_t n_bins, double *d_value, double *d_eta,
+                                              int32_t *d_n_iter, int32_t *d_pair_status, int32_t *d_status,
+                                              void *stream);
+int pisa_hip_profiled_metric_matrix_best_wide_form(int32_t kind, int32_t form, const double *d_data,
+                                                   const double *d_expected, const double *d_sigma2,
+                                                   const double *d_response, int64_t response_stride_k,
+                                                   const double *d_inv_prior_sigma, const double *d_center,
+                                                   const double *d_lower, const double *d_upper,
+                                                   int64_t bound_stride_k, const double *d_offset, int32_t k0,
+                                                   int32_t n_params, int32_t max_iter, int64_t n_trials,
+                                                   int64_t n_templates, int64_t n_bins, double *d_best,
+                                                   int32_t *d_arg, double *d_at, double *d_eta_best,
+                                                   double *d_eta_at, int32_t *d_trial_status, int32_t *d_status,
+                                                   void *stream);
+
 /* The covariance of the fitted displacements (csrc/profile_hesse.hip; DESIGN.md section 4, "Profiled trial ensembles:
  * covariance and pulls"): for trial t, its template k_t = d_k_of_trial[t] (the d_arg of the reduced fit; NULL: k0 for
  * every trial) and the point d_eta[t] ([n_trials][J]; normally d_eta_best or d_eta_at of that fit), one sweep over the

@@ -64,6 +64,12 @@ and, for a wide `response` (`NuisanceResponse(..., wide=True)`: up to 32 paramet
 (csrc/profile_wide.hip, `kernels.profiled_metric_matrix_wide`: one wavefront per pair, the bits of the narrow fit up to 8
 parameters), passed ONLY for such a response in the same way; what reads a kernel that stays limited to 8 parameters --
 `hesse`, `posterior`, `draw_linear`, `draw_linear_mvn`, `draw_linear_at` -- is refused for a response with more,
+and, for a log-linear `response` (`NuisanceResponse(..., form="loglinear")`: templates hist * exp(rho . eta), 1 to 32
+parameters, always fitted by the wide form), the same two methods with
+    form="loglinear"
+(csrc/profile_loglinear.hip, `kernels.profiled_metric_matrix_wide(..., form=)`), passed ONLY for such a response; the
+host generator forms its means by the response's form, and what reads a linear kernel -- `hesse`, `posterior`,
+`draw_linear`, `draw_linear_mvn`, `draw_linear_at` -- is refused for it by a ValueError that says "log-linear",
 and, for `generator="device"` with `nuisance="prior"`,
     draw_linear(mu [B], response [J, B], sigma [B] or None, method, n_trials, seed, stream, scale, shift, lower, upper
                 ([J] host arrays; lower / upper may be None), first_trial=0)
@@ -172,21 +178,29 @@ class DeviceSolver:
         return self._run(K.metric_matrix_best, kind, (data, expected, sigma2, offset), k0=int(k0))
 
     def profiled_matrix(self, kind, data, expected, response, sigma2=None, inv_prior_sigma=None, center=None,
-                        max_iter=32, lower=None, upper=None, wide=False):
-        """wide=True: the wide form (`kernels.profiled_metric_matrix_wide`, up to 32 parameters), whatever J"""
+                        max_iter=32, lower=None, upper=None, wide=False, form="linear"):
+        """wide=True: the wide form (`kernels.profiled_metric_matrix_wide`, up to 32 parameters), whatever J.
+        form: "linear", or "loglinear" (`response` holds rho, the template is expected * exp(rho . eta)); any other
+        form than "linear" runs the wide kernels"""
         from pisa_amd import kernels as K
 
         data, expected, response, sigma2, ips, center, lower, upper = [self._up(a) for a in (
             data, expected, response, sigma2, inv_prior_sigma, center, lower, upper)]
+        if form != "linear":
+            return K.profiled_metric_matrix_wide(kind, data, expected, response, sigma2, ips, center,
+                                                 max_iter=max_iter, lower=lower, upper=upper, form=form)
         fn = K.profiled_metric_matrix_wide if wide else K.profiled_metric_matrix
         return fn(kind, data, expected, response, sigma2, ips, center, max_iter=max_iter, lower=lower, upper=upper)
 
     def profiled_best(self, kind, data, expected, response, sigma2=None, inv_prior_sigma=None, center=None,
-                      offset=None, k0=0, max_iter=32, lower=None, upper=None, wide=False):
+                      offset=None, k0=0, max_iter=32, lower=None, upper=None, wide=False, form="linear"):
         from pisa_amd import kernels as K
 
         data, expected, response, sigma2, ips, center, offset, lower, upper = [self._up(a) for a in (
             data, expected, response, sigma2, inv_prior_sigma, center, offset, lower, upper)]
+        if form != "linear":
+            return K.profiled_metric_matrix_best_wide(kind, data, expected, response, sigma2, ips, center, offset,
+                                                      int(k0), max_iter=max_iter, lower=lower, upper=upper, form=form)
         fn = K.profiled_metric_matrix_best_wide if wide else K.profiled_metric_matrix_best
         return fn(kind, data, expected, response, sigma2, ips, center, offset, int(k0), max_iter=max_iter, lower=lower,
                   upper=upper)
@@ -433,12 +447,21 @@ class NuisanceResponse:
     upper, raises ValueError).  Arrays of whatever kind the solver takes.  `wide=True` takes 1 to 32 parameters and has
     the drivers fit them with the wide form of the solver (`wide=True` of `profiled_matrix` / `profiled_best`;
     csrc/profile_wide.hip), whatever J; what goes through a kernel limited to 8 parameters (covariances, pulls,
-    nuisance="fitted", `posterior_sample`, the device generator's nuisance draws) is then refused above 8."""
+    nuisance="fitted", `posterior_sample`, the device generator's nuisance draws) is then refused above 8.
+    `form="loglinear"`: the multiplicative response mu_kb(eta) = hist_kb exp(sum_j rho_kjb eta_j), with rho held in
+    `response` ([K, J, B] or [J, B]); the template stays positive and keeps the cross terms of a product of factors
+    (csrc/profile_loglinear.hip; DESIGN.md §4, "Profiled trial ensembles: the log-linear response").  A log-linear
+    response is wide whatever `wide=` says: it takes 1 to 32 names and is fitted by the wide form of the solver, which
+    gets form="loglinear".  What reads a kernel that is linear -- covariances, pulls, nuisance="fitted",
+    `posterior_sample`, the device generator with drawn or given truths -- is refused for it, whatever J."""
 
     def __init__(self, names, response, inv_prior_sigma=None, center=None, prior_at_point=None, values=None,
-                 max_iter=32, lower=None, upper=None, wide=False):
+                 max_iter=32, lower=None, upper=None, wide=False, form="linear"):
+        if form not in FORMS:
+            raise ValueError("NuisanceResponse: form '%s' is not one of %s" % (form, list(FORMS)))
         self.names = tuple(names)
-        self.wide = bool(wide)
+        self.form = form
+        self.wide = bool(wide) or form != "linear"
         self.response = response
         n_j = len(self.names)
         if len(response.shape) not in (2, 3) or int(response.shape[-2]) != n_j:
@@ -485,8 +508,9 @@ class NuisanceResponse:
 
     def fit_keywords(self):
         """the keywords a driver passes to `profiled_matrix` and `profiled_best`: the bounds of a response that has
-        some, wide=True for a wide response, nothing otherwise"""
-        return dict(self.bounds(), wide=True) if self.wide else self.bounds()
+        some, wide=True for a wide response, form= for a response that is not linear, nothing otherwise"""
+        kw = dict(self.bounds(), wide=True) if self.wide else self.bounds()
+        return dict(kw, form=self.form) if self.form != "linear" else kw
 
     def offset(self, grid):
         """grid.penalty without the named parameters' share, or None if that is zero everywhere"""
@@ -494,7 +518,7 @@ class NuisanceResponse:
         return off if np.any(off != 0.0) else None
 
     @classmethod
-    def from_maker(cls, hypo_maker, grid, names, test_vals, max_iter=32, bounded=False, wide=False):
+    def from_maker(cls, hypo_maker, grid, names, test_vals, max_iter=32, bounded=False, wide=False, form="linear"):
         """The response of `grid`'s templates to the free parameters `names` of `hypo_maker`: at every point of
         `grid.points` the gradients (T_hi - T_lo) / (hi - lo) of `hypo_maker._fisher_templates` (one call per
         parameter, every other parameter at the point's own value; one sweep of the events each where the pipeline
@@ -503,11 +527,16 @@ class NuisanceResponse:
         the mean are read from a Gaussian prior; a uniform prior (or none) gives 0; any other kind raises
         ValueError.  bounded=True: every displacement is fitted inside the parameter's `range`, lower[k, j] =
         range_j[0] - values[k, j] and upper[k, j] = range_j[1] - values[k, j] in the parameter's units (-inf / +inf
-        for a parameter without a range).  wide=True: as in the constructor, up to 32 names.  On return the free
+        for a parameter without a range).  wide=True: as in the constructor, up to 32 names.  form="loglinear": the
+        response holds rho[k, j, b] = grad[k, j, b] / hist[k, b] where the point's own template hist[k, b] > 0 and 0
+        elsewhere (the same gradients, read as logarithmic derivatives), and is wide.  On return the free
         parameters hold the values they had at entry."""
         from pisa_amd import kernels as K
 
+        if form not in FORMS:
+            raise ValueError("NuisanceResponse: form '%s' is not one of %s" % (form, list(FORMS)))
         names = list(names)
+        wide = bool(wide) or form != "linear"
         most = WIDE_MAX_PARAMS if wide else MAX_PARAMS
         if not 1 <= len(names) <= most:      # (before any template is made)
             raise ValueError("NuisanceResponse: 1 to %d parameters%s, got %d"
@@ -560,6 +589,11 @@ class NuisanceResponse:
         finally:
             hypo_maker.set_free_params(saved)
         center = np.where(ips[None, :] > 0, values - means[None, :], 0.0)
+        if form == "loglinear":
+            hist = np.asarray(grid.host("hist"), dtype=np.float64).reshape(n, 1, grid.n_bins)
+            with np.errstate(invalid="ignore"):
+                has = hist > 0.0
+            resp = np.where(has, resp / np.where(has, hist, 1.0), 0.0)
         lower = upper = None
         if bounded:
             lower, upper = np.full(values.shape, -np.inf), np.full(values.shape, np.inf)
@@ -568,7 +602,7 @@ class NuisanceResponse:
                 if prm._range is not None:
                     lower[:, j] = float(prm._range[0].m_as(prm._units)) - values[:, j]
                     upper[:, j] = float(prm._range[1].m_as(prm._units)) - values[:, j]
-        return cls(names, K.to_device(resp), ips, center, at_point, values, max_iter, lower, upper, wide)
+        return cls(names, K.to_device(resp), ips, center, at_point, values, max_iter, lower, upper, wide, form)
 
 
 def _takes_bounds(method):
@@ -584,6 +618,20 @@ def _takes_wide(method):
 
     params = inspect.signature(method).parameters
     return "wide" in params or any(p.kind is inspect.Parameter.VAR_KEYWORD for p in params.values())
+
+
+def _takes_form(method):
+    import inspect
+
+    params = inspect.signature(method).parameters
+    return "form" in params or any(p.kind is inspect.Parameter.VAR_KEYWORD for p in params.values())
+
+
+def _check_linear(response, what, needs):
+    """what reads a kernel whose template is linear in the displacements"""
+    if response is not None and getattr(response, "form", "linear") != "linear":
+        raise ValueError("%s: %s is not available for a log-linear response (it reads a kernel that is linear in the "
+                         "displacements; the fits alone take the form)" % (what, needs))
 
 
 def _check_narrow(response, what, needs):
@@ -607,6 +655,10 @@ def _check_response(response, grid, solver, what, metric=None):
                                                  and _takes_wide(solver.profiled_best)):
         raise ValueError("ensemble: a wide response needs a solver whose profiled_matrix and profiled_best take "
                          "wide=; those of %s do not" % type(solver).__name__)
+    if getattr(response, "form", "linear") != "linear" and not (_takes_form(solver.profiled_matrix)
+                                                                and _takes_form(solver.profiled_best)):
+        raise ValueError("ensemble: a log-linear response needs a solver whose profiled_matrix and profiled_best take "
+                         "form=; those of %s do not" % type(solver).__name__)
     shape = tuple(response.response.shape)
     if shape[-1] != grid.n_bins or (len(shape) == 3 and shape[0] != len(grid)):
         raise ValueError("%s: the response does not belong to this grid (%s against %d points, %d bins)"
@@ -618,6 +670,7 @@ def _check_response(response, grid, solver, what, metric=None):
 
 
 GENERATORS = ("host", "device")
+FORMS = ("linear", "loglinear")  # kernels.RESPONSE_FORM: how the templates respond to the displacements
 MAX_PARAMS = 8                 # _lib.PROFILE_MAX_PARAMS: the narrow fit, the covariance, the draws and the sampler
 WIDE_MAX_PARAMS = 32           # _lib.PROFILE_WIDE_MAX_PARAMS: the wide fit
 CHUNK_BYTES = 1 << 30          # pseudo-data of the device generator alive at a time
@@ -727,8 +780,10 @@ def _check_nuisance(nuisance, response, grid, solver, generator, method, metric,
         raise ValueError("%s: nuisance='%s' is not available for '%s' (response= has no form for the "
                          "MC-uncertainty metrics)" % (what, nuisance, metric))
     if nuisance == "fitted":
+        _check_linear(response, what, "nuisance='fitted' (the covariance of the observed fit)")
         _check_narrow(response, what, "nuisance='fitted' (the covariance of the observed fit)")
     if generator == "device":
+        _check_linear(response, what, "generator='device' with nuisance='%s' (the device draws of the truths)" % nuisance)
         _check_narrow(response, what, "generator='device' with nuisance='%s' (the device draws of the truths)" % nuisance)
     if method == "scaled_poisson":
         raise ValueError("%s: nuisance='%s' has no scaled_poisson draws (the method's row rules compare a row's "
@@ -788,6 +843,25 @@ def _linear_mean(mu0, R, eta):
         return np.where(mu < 0.0, 0.0, mu)
 
 
+def _loglinear_mean(mu0, rho, eta):
+    """mu0 exp(rho[0] eta_0 + ...) with the exponent formed from 0 in ascending j, every step rounded (the template the
+    log-linear fit works with); a bin with mu0 == 0 or every rho == 0 keeps mu0 exactly; a negative mean becomes 0, a
+    NaN stays"""
+    mu0 = np.array(mu0, dtype=np.float64)
+    s = np.zeros(mu0.shape)
+    for j in range(rho.shape[0]):
+        s = s + rho[j] * eta[j]
+    with np.errstate(invalid="ignore", over="ignore"):
+        responds = (mu0 != 0.0) & np.any(rho != 0.0, axis=0)
+        mu = np.where(responds, mu0 * np.exp(np.where(responds, s, 0.0)), mu0)
+        return np.where(mu < 0.0, 0.0, mu)
+
+
+def _mean_of(response):
+    """the host generator's mean of a trial by the response's form"""
+    return _loglinear_mean if getattr(response, "form", "linear") == "loglinear" else _linear_mean
+
+
 def _prior_data(grid, k, n_trials, seed_or_rs, generator, solver, method, response, first_trial=0):
     """(data [n_trials, B], eta_true [n_trials, J]) of `nuisance="prior"` at point k: module docstring"""
     R, scale, shift, lower, upper = _truth_priors(response, k)
@@ -808,9 +882,10 @@ def _prior_data(grid, k, n_trials, seed_or_rs, generator, solver, method, respon
     mu0 = np.asarray(grid.host("hist")[k], dtype=np.float64).ravel()
     R = _host(R).astype(np.float64)
     data, truth = np.empty((max(n_trials, 0), mu0.size)), np.empty((max(n_trials, 0), scale.size))
+    mean = _mean_of(response)
     for t in range(data.shape[0]):
         truth[t] = _host_truths(scale, shift, lower, upper, rs)
-        data[t] = _host_row(_linear_mean(mu0, R, truth[t]), sigma, method, rs)
+        data[t] = _host_row(mean(mu0, R, truth[t]), sigma, method, rs)
     return data, truth
 
 
@@ -892,6 +967,7 @@ def fit_observed(observed, grid, metric, response, solver=None, covariance=False
         raise ValueError("fit_observed: needs response=, the linear response whose parameters are fitted")
     _check_response(response, grid, solver, "fit_observed", metric)
     if covariance:
+        _check_linear(response, "fit_observed", "covariance=True")
         _check_narrow(response, "fit_observed", "covariance=True")
         _check_hesse(solver)
     rows = _data_rows(observed)
@@ -969,9 +1045,10 @@ def _observed_data(grid, k, n_trials, seed_or_rs, generator, solver, method, res
     mu0 = np.asarray(grid.host("hist")[k], dtype=np.float64).ravel()
     R = _host(R).astype(np.float64)
     data, truth = np.empty((max(n_trials, 0), mu0.size)), np.empty((max(n_trials, 0), eta.size))
+    mean = _mean_of(response)
     for t in range(data.shape[0]):
         truth[t] = eta if L is None else _host_truths_mvn(eta, L, lower, upper, rs)
-        data[t] = _host_row(_linear_mean(mu0, R, truth[t]), sigma, method, rs)
+        data[t] = _host_row(mean(mu0, R, truth[t]), sigma, method, rs)
     return data, truth
 
 
@@ -993,6 +1070,7 @@ def _check_truths(response, grid, solver, generator, method, metric, nuisance, o
         raise ValueError("%s: truths= has no scaled_poisson draws (the method's row rules compare a row's variance "
                          "with its mean, which moves per trial)" % what)
     if generator == "device":
+        _check_linear(response, what, "generator='device' with truths= (the device draws at given truths)")
         _check_narrow(response, what, "generator='device' with truths= (the device draws at given truths)")
     if generator == "device" and not hasattr(solver, "draw_linear_at"):
         raise ValueError("ensemble: generator='device' with truths= needs a solver with draw_linear_at(mu, response, "
@@ -1047,8 +1125,9 @@ def _truths_data(grid, k, rows, seed_or_rs, generator, solver, method, response,
     mu0 = np.asarray(grid.host("hist")[k], dtype=np.float64).ravel()
     R = _host(R).astype(np.float64)
     data = np.empty((rows.shape[0], mu0.size))
+    mean = _mean_of(response)
     for t in range(data.shape[0]):
-        data[t] = _host_row(_linear_mean(mu0, R, rows[t]), sigma, method, rs)
+        data[t] = _host_row(mean(mu0, R, rows[t]), sigma, method, rs)
     return data
 
 
@@ -1219,6 +1298,7 @@ def delta_metric(data, grid, metric, k0, solver=None, response=None, return_info
         return best - at if metric in _MAXIMISED else at - best
     _check_response(response, grid, solver, "delta_metric", metric)
     if covariance:
+        _check_linear(response, "delta_metric", "covariance=True")
         _check_narrow(response, "delta_metric", "covariance=True")
         _check_hesse(solver)
     out = solver.profiled_best(metric, _data_rows(data), grid.hist, response.response, grid.sigma2_for(metric),
@@ -1256,6 +1336,7 @@ def pulls(data, grid, metric, k0, response, truth, solver=None):
     and the counts large: the closure check of a profiled ensemble.  NaN where sigma is 0 (a coordinate held on a
     bound) or NaN (a flagged fit)."""
     solver = DeviceSolver() if solver is None else solver
+    _check_linear(response, "pulls", "the covariance of the fit")
     _check_narrow(response, "pulls", "the covariance of the fit")
     _check_hesse(solver)
     rows = _data_rows(data)
@@ -1534,6 +1615,7 @@ def posterior_sample(observed, grid, metric, response, points=None, n_keep=200, 
     if response is None:
         raise ValueError("posterior_sample: needs response=, the linear response whose parameters are sampled")
     _check_response(response, grid, solver, "posterior_sample", metric)
+    _check_linear(response, "posterior_sample", "the sampler")
     _check_narrow(response, "posterior_sample", "the sampler")
     for name in ("posterior", "draw_linear", "hesse"):
         if not hasattr(solver, name):

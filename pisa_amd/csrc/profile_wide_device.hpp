@@ -14,11 +14,16 @@
 // chains to lanes, mu over the staged chunk, the cooperative factor and solve, the judgement of a trial point on the
 // scalar lane between their phases, and the executor.
 //
+// The form of the response (`PFW_LINEAR`, `PFW_LOGLINEAR`) is a template parameter of the two phases whose lanes own
+// bins, `pfw_bins` and `pfw_value_bins`, and of nothing else: the log-linear form mu_b = E_b exp(sum_j rho_jb eta_j)
+// ("Profiled trial ensembles: the log-linear response") hands the chains another p1, p2 per bin and is
+// the same solver from there on.  With the form linear both phases are the code they were before the parameter existed.
+//
 // Form.  Every cooperative phase is a function of (shared state, lane): it reads what earlier phases wrote and writes
 // locations no other lane reads or writes in the same phase.  A driver (`pfw_*` taking an executor X) strings the
 // phases together; `x.each(f)` runs f(lane) on every lane and then makes the writes visible: the kernel
-// (profile_wide.hip) calls f on its own lane and meets the barrier, a host program loops over the lanes.  All control
-// flow of a driver depends on shared values read after such a barrier, so it is uniform over the lanes.
+// (profile_wide_kernel.hpp) calls f on its own lane and meets the barrier, a host program loops over the lanes.  All
+// control flow of a driver depends on shared values read after such a barrier, so it is uniform over the lanes.
 // No HIP type or call: tests/test_host_profiled_wide.py compiles this file with a plain C++ compiler and runs it
 // under the sanitizers against the numpy restatements.
 #pragma once
@@ -59,6 +64,8 @@ struct PfwShared {
 };
 
 constexpr int PFW_ACT_DONE = 0, PFW_ACT_HALVE = 1, PFW_ACT_ACCEPT = 2;
+
+constexpr int PFW_LINEAR = 0, PFW_LOGLINEAR = 1;   // PISA_HIP_RESPONSE_*: the form of the response
 
 // the response of coordinate j at bin cc of the chunk (`R`: the pfw_chunk_doubles(J) doubles behind the state)
 PISA_PF_HD double pfw_r(const double *R, int j, int cc) { return R[j * PFW_LD + cc]; }
@@ -117,10 +124,66 @@ PISA_PF_HD void pfw_sweep_begin(PfwShared &S, int lane) {
     }
 }
 
+// The log-linear template of bin cc of the chunk at `eta`: the exponent s from 0 in ascending j with every product
+// rounded, then mu = e * exp(s), `exp` and the product rounded once each.  `a`: the sum of |rho_jb eta_j|, formed the
+// same way.  A bin responds if e != 0 and some rho_jb != 0; one that does not keeps mu = e exactly (no exp, no product).
+PISA_PF_HD double pfw_mu_loglinear(const double *R, const double *eta, int J, int cc, double e, bool &responds,
+                                   double &a) {
+    double s = 0.0;
+    bool any = false;
+    a = 0.0;
+    for (int j = 0; j < J; j++) {
+        const double r = pfw_r(R, j, cc);
+        const double t = r * eta[j];
+        s = s + t;
+        a += fabs(t);
+        if (r != 0.0) any = true;
+    }
+    responds = any && e != 0.0;
+    if (!responds) return e;
+    const double x = exp(s);
+    return e * x;
+}
+
+// `pfw_bins` of the log-linear form.  With u = d mu / d eta_j = mu rho_j the bin's share of g_j is (phi' mu) rho_j and
+// of H_ij (phi'' mu^2 + phi' mu) rho_i rho_j: the rank-one shape `pfw_chains` takes, with other p1, p2.  A responding
+// bin whose mu is not finite (an overflowing exp) or below PF_SMALL_POS is outside the domain; a bin that does not
+// respond is a constant of Phi and hands the chains zeros.
+template <int KIND>
+PISA_PF_HD void pfw_bins_loglinear(PfwShared &S, const double *R, int lane, int nb) {
+    if (lane >= nb) return;
+    const double d = S.cD[lane], e = S.cE[lane], s2 = S.cS2[lane];
+    if (!pf_finite(d, e)) {
+        S.use[lane] = PFW_SKIP;
+        return;
+    }
+    bool responds;
+    double a;
+    const double mu = pfw_mu_loglinear(R, S.eta_t, S.J, lane, e, responds, a);
+    if (responds && (!(mu >= PF_SMALL_POS) || isinf(mu))) {
+        S.use[lane] = PFW_OUTSIDE;
+        return;
+    }
+    const double m = mu < PF_SMALL_POS ? PF_SMALL_POS : mu;
+    double phi, f1, f2;
+    pf_phi<KIND>(d, m, s2, phi, f1, f2);
+    const double p1 = f1 * m;
+    const double p2 = (f2 * m) * m + p1;
+    S.use[lane] = PFW_USE;
+    S.phi[lane] = phi;
+    S.p1[lane] = responds ? p1 : 0.0;
+    S.p2[lane] = responds ? p2 : 0.0;
+    S.sc[lane] = pf_scale_term(phi, f1, m * (2.0 + a));
+}
+
 // Lanes own bins: the part of `pf_bin` that is the bin's own (mu in ascending j with every product rounded, then
 // phi, phi', phi'' and the bin's term of `scale`), for bin `lane` of a chunk of nb bins.
-template <int KIND>
+template <int KIND, int FORM = PFW_LINEAR>
 PISA_PF_HD void pfw_bins(PfwShared &S, const double *R, int lane, int nb) {
+    if constexpr (FORM == PFW_LOGLINEAR) {
+        pfw_bins_loglinear<KIND>(S, R, lane, nb);
+        return;
+    }
     if (lane >= nb) return;
     const int J = S.J;
     const double d = S.cD[lane], e = S.cE[lane], s2 = S.cS2[lane];
@@ -432,8 +495,8 @@ PISA_PF_HD void pfw_value_begin(PfwShared &S, int lane) {
     S.negative = 0;
 }
 
-// lanes own bins: `pf_value_bin` up to the bin's own term
-template <int KIND>
+// lanes own bins: `pf_value_bin` up to the bin's own term (FORM: the template at eta by the form's own function)
+template <int KIND, int FORM = PFW_LINEAR>
 PISA_PF_HD void pfw_value_bins(PfwShared &S, const double *R, int lane, int nb) {
     if (lane >= nb) return;
     const int J = S.J;
@@ -442,9 +505,15 @@ PISA_PF_HD void pfw_value_bins(PfwShared &S, const double *R, int lane, int nb) 
     if (pf_finite(d, e)) {
         if (d < 0.0 || e < 0.0) mark |= PFW_NEGATIVE;
         double lam = e;
-        for (int j = 0; j < J; j++) {
-            const double t = pfw_r(R, j, lane) * S.eta[j];
-            lam = lam + t;
+        if constexpr (FORM == PFW_LOGLINEAR) {
+            bool responds;
+            double a;
+            lam = pfw_mu_loglinear(R, S.eta, J, lane, e, responds, a);
+        } else {
+            for (int j = 0; j < J; j++) {
+                const double t = pfw_r(R, j, lane) * S.eta[j];
+                lam = lam + t;
+            }
         }
         if ((lam == lam) && !isinf(lam)) {
             if (KIND == PF_CHI2) {

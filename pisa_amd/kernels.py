@@ -975,11 +975,19 @@ def _bound_args(what, lower, upper, n_k, n_j):
     return out[0], out[1], n_j if per_template else 0
 
 
-def _profiled_call(what, wide, kind, data, expected, response, sigma2, inv_prior_sigma, center, max_iter, lower, upper):
+RESPONSE_FORM = {"linear": _lib.RESPONSE_LINEAR, "loglinear": _lib.RESPONSE_LOGLINEAR}
+
+
+def _profiled_call(what, wide, kind, data, expected, response, sigma2, inv_prior_sigma, center, max_iter, lower, upper,
+                   form="linear"):
     """the checked inputs of a profiled matrix call -> (the entry points' suffix, the arguments they begin with: [kind
     ... center, (the bounds)], n_params, [max_iter, T, K, B], the tensors behind the pointers, data first).  The narrow
     form without bounds goes to the unbounded entry points, with bounds to the `_bounded` ones; the wide entry points
-    take the bounds always (NULL: none)."""
+    take the bounds always (NULL: none).  A form other than "linear" (the wide form alone) goes to the `_wide_form`
+    entry points, which take the form after the kind."""
+    if form not in RESPONSE_FORM or (form != "linear" and not wide):
+        raise ValueError("%s: form '%s' is not one of 'linear', 'loglinear'%s"
+                         % (what, form, "" if wide else " (the narrow form is linear)"))
     (data, expected, response, sigma2, ips, center, stride, n_t, n_k, n_bins, n_j) = _profile_args(
         what, kind, data, expected, response, sigma2, inv_prior_sigma, center, max_iter,
         _lib.PROFILE_WIDE_MAX_PARAMS if wide else _lib.PROFILE_MAX_PARAMS)
@@ -992,14 +1000,16 @@ def _profiled_call(what, wide, kind, data, expected, response, sigma2, inv_prior
     elif wide:
         head += [None, None, 0]
     keep = (data, expected, response, sigma2, ips, center, lower, upper)     # (alive until the launch)
+    if form != "linear":
+        return "_wide_form", head[:1] + [RESPONSE_FORM[form]] + head[1:], n_j, [int(max_iter), n_t, n_k, n_bins], keep
     return "_wide" if wide else "_bounded" if bounded else "", head, n_j, [int(max_iter), n_t, n_k, n_bins], keep
 
 
 def _profiled_full(what, wide, kind, data, expected, response, sigma2, inv_prior_sigma, center, max_iter, want_eta,
-                   status, lower, upper):
+                   status, lower, upper, form="linear"):
     """the body of `profiled_metric_matrix` and `profiled_metric_matrix_wide`"""
     suffix, head, n_j, sizes, keep = _profiled_call(what, wide, kind, data, expected, response, sigma2, inv_prior_sigma,
-                                                    center, max_iter, lower, upper)
+                                                    center, max_iter, lower, upper, form)
     n_t, n_k, dev = sizes[1], sizes[2], keep[0].device
     value = torch.empty((n_t, n_k), dtype=F8, device=dev)
     eta = torch.empty((n_t, n_k, n_j), dtype=F8, device=dev) if want_eta else None
@@ -1016,10 +1026,10 @@ def _profiled_full(what, wide, kind, data, expected, response, sigma2, inv_prior
 
 
 def _profiled_best(what, wide, kind, data, expected, response, sigma2, inv_prior_sigma, center, offset, k0, max_iter,
-                   status, lower, upper):
+                   status, lower, upper, form="linear"):
     """the body of `profiled_metric_matrix_best` and `profiled_metric_matrix_best_wide`"""
     suffix, head, n_j, sizes, keep = _profiled_call(what, wide, kind, data, expected, response, sigma2, inv_prior_sigma,
-                                                    center, max_iter, lower, upper)
+                                                    center, max_iter, lower, upper, form)
     n_t, n_k, dev = sizes[1], sizes[2], keep[0].device
     offset = _offset_arg(what, offset, n_k)
     best = torch.empty(n_t, dtype=F8, device=dev)
@@ -1068,22 +1078,28 @@ def profiled_metric_matrix_best(kind, data, expected, response, sigma2=None, inv
 
 
 def profiled_metric_matrix_wide(kind, data, expected, response, sigma2=None, inv_prior_sigma=None, center=None,
-                                max_iter=32, want_eta=True, status=None, lower=None, upper=None):
+                                max_iter=32, want_eta=True, status=None, lower=None, upper=None, form="linear"):
     """`profiled_metric_matrix` in the wide form (`pisa_hip_profiled_metric_matrix_wide`, DESIGN.md §4, "Profiled
     trial ensembles: more than 8 parameters"): the same fit, arguments and outputs with 1 to
     `_lib.PROFILE_WIDE_MAX_PARAMS` = 32 nuisance parameters, one wavefront per (trial, template) pair.  With both
     bounds None it is the unbounded fit, otherwise the bounded one; up to 8 parameters the outputs are bit for bit those
-    of `profiled_metric_matrix`."""
+    of `profiled_metric_matrix`.
+    form="loglinear" (`pisa_hip_profiled_metric_matrix_wide_form`, DESIGN.md §4, "Profiled trial ensembles: the
+    log-linear response"): `response` holds rho and the template of pair (t, k) is expected[k] * exp(sum_j rho[k, j]
+    eta_j): positive for every eta, with all cross terms of a product of factors.  Everything else is the same fit.
+    Any other form than "linear" and "loglinear" raises ValueError."""
     return _profiled_full("profiled_metric_matrix_wide", True, kind, data, expected, response, sigma2, inv_prior_sigma,
-                          center, max_iter, want_eta, status, lower, upper)
+                          center, max_iter, want_eta, status, lower, upper, form)
 
 
 def profiled_metric_matrix_best_wide(kind, data, expected, response, sigma2=None, inv_prior_sigma=None, center=None,
-                                     offset=None, k0=0, max_iter=32, status=None, lower=None, upper=None):
+                                     offset=None, k0=0, max_iter=32, status=None, lower=None, upper=None,
+                                     form="linear"):
     """`profiled_metric_matrix_best` in the wide form (`pisa_hip_profiled_metric_matrix_best_wide`): the reduction of
-    `profiled_metric_matrix_wide` per trial, bit for bit, with 1 to 32 nuisance parameters"""
+    `profiled_metric_matrix_wide` per trial, bit for bit, with 1 to 32 nuisance parameters; form: as there
+    (`pisa_hip_profiled_metric_matrix_best_wide_form`)"""
     return _profiled_best("profiled_metric_matrix_best_wide", True, kind, data, expected, response, sigma2,
-                          inv_prior_sigma, center, offset, k0, max_iter, status, lower, upper)
+                          inv_prior_sigma, center, offset, k0, max_iter, status, lower, upper, form)
 
 
 def profiled_hesse(kind, data, expected, response, eta, k, sigma2=None, inv_prior_sigma=None, center=None, lower=None,

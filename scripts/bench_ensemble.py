@@ -191,10 +191,15 @@ def profiled_lines(n_params, reps, bounded=None):
         del d, e, r
 
 
-def profiled_wide_lines(n_params, reps):
+def profiled_wide_lines(n_params, reps, form="linear"):
     """the protocol of `profiled_lines` with the wide form (`profiled_metric_matrix_best_wide`, one wavefront per pair,
     J up to 32) at (T, K, B) = (1e4, 1e2, 128); iteration counts from the wide full output on the first trials.  With
-    J <= 8 the narrow form is timed in the same run: the price of the mapping."""
+    J <= 8 the narrow form is timed in the same run: the price of the mapping.
+    form="loglinear": the log-linear response rho = 0.05 x cosines (the same shapes without the factor E), the data
+    drawn at E exp(rho . eta0); the linear wide form is timed in the same run on the same data with the response rho E,
+    and both times go into the line with their ratio."""
+    if form == "loglinear":
+        return profiled_loglinear_lines(n_params, reps)
     import torch
 
     from pisa_amd import kernels as K
@@ -225,6 +230,50 @@ def profiled_wide_lines(n_params, reps):
         if J <= 8:
             narrow = _time(lambda: K.profiled_metric_matrix_best(kind, d, e, r, sig, ips, k0=n_k // 2, status=status), reps)
             line.update(ms_narrow=narrow["ms_median"], ratio_to_narrow=round(res["ms_median"] / narrow["ms_median"], 2))
+        print(json.dumps(line), flush=True)
+    assert int(status.item()) == 0
+
+
+def profiled_loglinear_lines(n_params, reps):
+    """`profiled_wide_lines` for the log-linear response (`profiled_metric_matrix_best_wide(..., form="loglinear")`):
+    unit priors, reduced output, and the linear wide form in the same run"""
+    import torch
+
+    from pisa_amd import kernels as K
+
+    dev = K.device()
+    J = int(n_params)
+    n_t, n_k, n_b = 10 ** 4, 10 ** 2, 128
+    e_host = _templates(n_k, n_b)
+    rs = np.random.RandomState(1)
+    x = (np.arange(n_b) + 0.5) / n_b
+    rho_host = np.ascontiguousarray(np.broadcast_to(
+        0.05 * np.cos((np.arange(J)[:, None] + 1) * np.pi * x[None, :])[None], (n_k, J, n_b)))
+    mu = e_host * np.exp(np.einsum("kjb,kj->kb", rho_host, 0.5 * rs.randn(n_k, J)))
+    d = torch.from_numpy(rs.poisson(np.maximum(mu, 1.0)[rs.randint(0, n_k, n_t)]).astype(np.float64)).to(dev)
+    e, rho = torch.from_numpy(e_host).to(dev), torch.from_numpy(rho_host).to(dev)
+    r = torch.from_numpy(rho_host * e_host[:, None, :]).to(dev)
+    s2 = 0.1 * e
+    ips = torch.ones(J, dtype=torch.float64, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    n_head = 256
+    for kind in ("llh", "poisson_llh", "chi2", "mod_chi2"):
+        sig = s2 if kind == "mod_chi2" else None
+        line = dict(workload="profiled_kernel_loglinear", T=n_t, K=n_k, B=n_b, J=J, kind=kind, output="reduced")
+        for name, resp in (("loglinear", rho), ("linear", r)):
+            head = K.profiled_metric_matrix_wide(kind, d[:n_head], e, resp, sig, ips, want_eta=False, status=status,
+                                                 form=name)
+            it = head["n_iter"].double()
+            res = _time(lambda: K.profiled_metric_matrix_best_wide(kind, d, e, resp, sig, ips, k0=n_k // 2,
+                                                                   status=status, form=name), reps)
+            tag = "" if name == "loglinear" else "_linear"
+            line.update({"ms_median" + tag: res["ms_median"], "ms_min" + tag: res["ms_min"],
+                         "iter_mean" + tag: round(float(it.mean().item()), 3), "iter_max" + tag: int(it.max().item()),
+                         "flagged_of_head" + tag: int((head["status"] != 0).sum().item()),
+                         "ms_per_sweep" + tag: round(res["ms_median"] / (float(it.mean().item()) + 2.0), 3)})
+        line.update(head_pairs=n_head * n_k, reps=reps,
+                    ratio_to_linear=round(line["ms_median"] / line["ms_median_linear"], 3),
+                    ratio_per_sweep=round(line["ms_per_sweep"] / line["ms_per_sweep_linear"], 3))
         print(json.dumps(line), flush=True)
     assert int(status.item()) == 0
 
@@ -563,6 +612,9 @@ def main():
     ap.add_argument("--wide", action="store_true",
                     help="with --profiled: time the wide form (one wavefront per pair) at (1e4, 1e2, 128), and for "
                          "J <= 8 the narrow form beside it")
+    ap.add_argument("--form", choices=("linear", "loglinear"), default="linear",
+                    help="with --profiled J --wide: the form of the response; loglinear times the log-linear kernels "
+                         "and the linear wide form in the same run")
     ap.add_argument("--bounded", type=float, default=None, metavar="H",
                     help="with --profiled: also time the bounded reduced form, every displacement inside -H ... +H "
                          "prior sigmas")
@@ -595,7 +647,7 @@ def main():
     if not args.skip_kernels:
         kernel_lines(args.reps, tuple(args.forms.split(",")))
     if args.profiled and args.wide:
-        profiled_wide_lines(args.profiled, args.reps)
+        profiled_wide_lines(args.profiled, args.reps, args.form)
     elif args.profiled:
         profiled_lines(args.profiled, args.reps, args.bounded)
     if not args.skip_draw:
