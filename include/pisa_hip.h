@@ -121,6 +121,38 @@ int pisa_hip_prob3_grid_planned(const pisa_hip_prob3_params *h_params, pisa_hip_
                                 double *d_prob_nu, double *d_prob_nubar, double *d_pepmu,
                                 void *stream);
 
+/* Production-height averaging.  Semantics of `prop_height_range` of the reference's nuSQuIDS stage
+ * (pisa/stages/osc/nusquids.py:83-88, 573-606): the production height is uniform in [mean - range/2, mean + range/2],
+ * projected onto the neutrino's direction, i.e. uniform in path length between the lengths L_min and L_max that
+ * the two heights give.  Here the first traversed layer of a row (the atmosphere, electron density exactly 0)
+ * has the length Lbar = (L_min + L_max) / 2 and `avg_range` holds dL = L_max - L_min per row; the probabilities are
+ * the mean over that layer's length in [Lbar - dL/2, Lbar + dL/2], in closed form ("Production-height
+ * average": with W = U.T, D_j = W[b][j] conj(U[a][j]), x_jk = (dm_j0 - dm_k0) 2.534 (dL/E) / 2,
+ * P_avg[a->b] = sum_j |D_j|^2 + 2 sum_{j<k} sin(x_jk)/x_jk Re(D_j conj(D_k))).  A row or element with range 0 gets the
+ * bits of the plain call.  PISA_HIP_ERR_INVALID, before anything is launched that writes an output: a negative
+ * or non-finite range; a positive range on a row whose first traversed layer has a density != 0; a positive range
+ * together with decay_flag == 1 or a non-zero lri_pot (the first layer is then not diagonal in the mass basis).
+ *
+ * Planned form: h_avg_range[n_cz] in km (NULL clears it: the plan then launches exactly the kernels of a plan that
+ * never had one).  The range stays with the plan and serves pisa_hip_prob3_grid_planned, _planned_multi and the
+ * evaluator.  Synchronises the device. */
+int pisa_hip_grid_plan_set_avg_range(pisa_hip_grid_plan *plan, const double *h_avg_range);
+
+/* Reference-order array form: the contracts of pisa_hip_propagate_array / _host plus d_avg_range: [n] if
+ * layers_per_element != 0, else [1] for the shared row; NULL is the plain call.  The device form checks ranges and
+ * rows with a small kernel and waits for its verdict before it launches the propagation (one stream
+ * synchronisation per call). */
+int pisa_hip_propagate_array_avg(const pisa_hip_prob3_params *h_params, int64_t nubar,
+                                 const double *d_energy, const double *d_densities,
+                                 const double *d_distances, const double *d_avg_range, int64_t n,
+                                 int32_t n_layers, int32_t layers_per_element, double *d_probability,
+                                 void *stream);
+int pisa_hip_propagate_array_avg_host(const pisa_hip_prob3_params *h_params, int64_t nubar,
+                                      const double *h_energy, const double *h_densities,
+                                      const double *h_distances, const double *h_avg_range, int64_t n,
+                                      int32_t n_layers, int32_t layers_per_element,
+                                      double *h_probability);
+
 /* Earth model as held by `Layers` (pisa/stages/osc/layers.py:216-335, 411-439):
  * shells ordered from the production sphere inwards. */
 typedef struct {

@@ -282,6 +282,9 @@ _SIGS = {
     "pisa_hip_grid_plan_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
     "pisa_hip_grid_plan_destroy": (C.c_int, [C.c_void_p]),
     "pisa_hip_prob3_grid_planned": (C.c_int, [C.POINTER(Prob3Params), C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pisa_hip_grid_plan_set_avg_range": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "pisa_hip_propagate_array_avg": (C.c_int, [C.POINTER(Prob3Params), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "pisa_hip_propagate_array_avg_host": (C.c_int, [C.POINTER(Prob3Params), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p]),
     "pisa_hip_calc_layers": (C.c_int, [C.POINTER(Earth), C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pisa_hip_prob3_events": (C.c_int, [C.POINTER(Prob3Params), C.POINTER(Earth), C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pisa_hip_prob3_events_multi": (C.c_int, [C.POINTER(Prob3Params), C.POINTER(Earth), C.POINTER(EventSet), C.c_int32, C.c_void_p, C.c_void_p]),

@@ -40,6 +40,50 @@ prob3_array_kernel(const Prob3Consts c, int side, const double *__restrict__ ene
     for (int k = 0; k < 9; k++) prob[9 * i + k] = P[k];
 }
 
+// The same with the production-height average (prob3_device.hpp: height_averaged_probs): element i averages over the
+// range avg_range[i * range_stride] of its first traversed layer's length; range 0 is the plain expression.  No decay.
+__global__ void __launch_bounds__(256)
+prob3_array_avg_kernel(const Prob3Consts c, int side, const double *__restrict__ energy,
+                       const double *__restrict__ densities, const double *__restrict__ distances,
+                       const double *__restrict__ avg_range, int64_t range_stride,
+                       int64_t n, int n_layers, int64_t row_stride, double *__restrict__ prob) {
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const double *rho_row = densities + i * row_stride;
+    const double *dist_row = distances + i * row_stride;
+    auto layer = [&](int l, double &rho, double &dist) {
+        rho = rho_row[l];
+        dist = dist_row[l];
+    };
+    double P[9];
+    const double e = energy[i];
+    propagate_element<false, true>(c.side[side], c.dm, e, n_layers, layer, P, avg_range[i * range_stride] / e);
+#pragma unroll
+    for (int k = 0; k < 9; k++) prob[9 * i + k] = P[k];
+}
+
+// What the host cannot see of an averaged call's device arrays: bit 0 of *flag for a range that is negative or not
+// finite, bit 1 for a positive range on a row whose first traversed layer has electrons (or that has no layer),
+// bit 2 for any positive range.
+__global__ void __launch_bounds__(256)
+prob3_avg_check_kernel(const double *__restrict__ densities, const double *__restrict__ distances,
+                       const double *__restrict__ avg_range, int64_t n_rows, int n_layers,
+                       int32_t *__restrict__ flag) {
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_rows) return;
+    const double r = avg_range[i];
+    if (!(r >= 0.0) || !(r <= 1.79769313486231570815e308)) {
+        atomicOr(flag, 1);
+        return;
+    }
+    if (r == 0.0) return;
+    atomicOr(flag, 4);
+    int f = -1;
+    for (int l = 0; l < n_layers && f < 0; l++)
+        if (distances[i * n_layers + l] > 0.0) f = l;
+    if (f < 0 || densities[i * n_layers + f] != 0.0) atomicOr(flag, 2);
+}
+
 // ------------------------------------------------------------------ grid form
 // blockIdx.x = coszen row, blockIdx.y = 0 (nu) / 1 (nubar), threads over energy.
 template <bool DECAY>
@@ -161,6 +205,100 @@ PISA_API int pisa_hip_propagate_array_host(const pisa_hip_prob3_params *h_params
     if (d_e) (void)hipFree(d_e);
     if (d_rho) (void)hipFree(d_rho);
     if (d_len) (void)hipFree(d_len);
+    if (d_p) (void)hipFree(d_p);
+    return rc;
+}
+
+// `propagate_array` with the production-height average (nusquids.py:83-88, 573-606; DESIGN.md §4, "Production-height
+// average").  The ranges and the rows are device arrays, so they are checked by a small kernel whose verdict the
+// host waits for BEFORE it launches the propagation: an invalid call writes nothing.
+PISA_API int pisa_hip_propagate_array_avg(const pisa_hip_prob3_params *h_params, int64_t nubar,
+                                          const double *d_energy, const double *d_densities,
+                                          const double *d_distances, const double *d_avg_range, int64_t n,
+                                          int32_t n_layers, int32_t layers_per_element,
+                                          double *d_probability, void *stream) {
+    if (!d_avg_range)
+        return pisa_hip_propagate_array(h_params, nubar, d_energy, d_densities, d_distances, n, n_layers,
+                                        layers_per_element, d_probability, stream);
+    if (n < 0 || n_layers < 0 || (nubar != 1 && nubar != -1)) return PISA_HIP_ERR_INVALID;
+    if (n_layers > PISA_HIP_MAX_LAYERS) return PISA_HIP_ERR_LAYERS;
+    if (n == 0) return PISA_HIP_OK;
+    if (!d_energy || !d_probability || (n_layers > 0 && (!d_densities || !d_distances)))
+        return PISA_HIP_ERR_INVALID;
+    Prob3Consts c;
+    int rc = make_consts(h_params, c);
+    if (rc) return rc;
+    hipStream_t s = as_stream(stream);
+    const int64_t n_rows = layers_per_element ? n : 1;
+    int32_t *d_flag = nullptr, h_flag = 0;
+    PISA_TRY_HIP(hipMalloc(&d_flag, sizeof(int32_t)));
+    rc = check_hip(hipMemsetAsync(d_flag, 0, sizeof(int32_t), s), "memset");
+    if (!rc) {
+        hipLaunchKernelGGL(prob3_avg_check_kernel, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, s,
+                           d_densities, d_distances, d_avg_range, n_rows, (int)n_layers, d_flag);
+        rc = check_hip(hipGetLastError(), "prob3_avg_check_kernel");
+    }
+    if (!rc) rc = check_hip(hipMemcpyAsync(&h_flag, d_flag, sizeof(int32_t), hipMemcpyDeviceToHost, s), "d2h");
+    if (!rc) rc = check_hip(hipStreamSynchronize(s), "sync");
+    (void)hipFree(d_flag);
+    if (rc) return rc;
+    if (h_flag & 3) return PISA_HIP_ERR_INVALID;
+    // decay and a long-range potential take the first layer out of the mass basis: refused with a positive range;
+    // with every range 0 this is the plain call
+    bool lri = false;
+    for (int i = 0; i < 9; i++) lri = lri || h_params->lri_pot[i] != 0.0;
+    if (c.decay || lri) {
+        if (h_flag & 4) return PISA_HIP_ERR_INVALID;
+        return pisa_hip_propagate_array(h_params, nubar, d_energy, d_densities, d_distances, n, n_layers,
+                                        layers_per_element, d_probability, stream);
+    }
+    int side = nubar > 0 ? 0 : 1;
+    int64_t stride = layers_per_element ? n_layers : 0;
+    dim3 block(256), grid((unsigned)((n + 255) / 256));
+    hipLaunchKernelGGL(prob3_array_avg_kernel, grid, block, 0, s, c, side, d_energy, d_densities, d_distances,
+                       d_avg_range, (int64_t)(layers_per_element ? 1 : 0), n, (int)n_layers, stride, d_probability);
+    PISA_CHECK_LAUNCH("prob3_array_avg_kernel");
+    return PISA_HIP_OK;
+}
+
+PISA_API int pisa_hip_propagate_array_avg_host(const pisa_hip_prob3_params *h_params, int64_t nubar,
+                                               const double *h_energy, const double *h_densities,
+                                               const double *h_distances, const double *h_avg_range, int64_t n,
+                                               int32_t n_layers, int32_t layers_per_element,
+                                               double *h_probability) {
+    if (!h_avg_range)
+        return pisa_hip_propagate_array_host(h_params, nubar, h_energy, h_densities, h_distances, n, n_layers,
+                                             layers_per_element, h_probability);
+    if (n < 0 || n_layers < 0) return PISA_HIP_ERR_INVALID;
+    if (n_layers > PISA_HIP_MAX_LAYERS) return PISA_HIP_ERR_LAYERS;
+    if (n == 0) return PISA_HIP_OK;
+    const size_t n_rows = layers_per_element ? (size_t)n : 1;
+    size_t ne = (size_t)n * sizeof(double);
+    size_t nl = n_rows * (size_t)n_layers * sizeof(double);
+    double *d_e = nullptr, *d_rho = nullptr, *d_len = nullptr, *d_p = nullptr, *d_r = nullptr;
+    int rc = PISA_HIP_OK;
+    hipStream_t s = nullptr;
+    do {
+        if ((rc = check_hip(hipMalloc(&d_e, ne), "hipMalloc"))) break;
+        if ((rc = check_hip(hipMalloc(&d_rho, nl ? nl : 8), "hipMalloc"))) break;
+        if ((rc = check_hip(hipMalloc(&d_len, nl ? nl : 8), "hipMalloc"))) break;
+        if ((rc = check_hip(hipMalloc(&d_r, n_rows * sizeof(double)), "hipMalloc"))) break;
+        if ((rc = check_hip(hipMalloc(&d_p, 9 * ne), "hipMalloc"))) break;
+        if ((rc = check_hip(hipMemcpyAsync(d_e, h_energy, ne, hipMemcpyHostToDevice, s), "h2d"))) break;
+        if ((rc = check_hip(hipMemcpyAsync(d_r, h_avg_range, n_rows * sizeof(double), hipMemcpyHostToDevice, s), "h2d"))) break;
+        if (nl) {
+            if ((rc = check_hip(hipMemcpyAsync(d_rho, h_densities, nl, hipMemcpyHostToDevice, s), "h2d"))) break;
+            if ((rc = check_hip(hipMemcpyAsync(d_len, h_distances, nl, hipMemcpyHostToDevice, s), "h2d"))) break;
+        }
+        if ((rc = pisa_hip_propagate_array_avg(h_params, nubar, d_e, d_rho, d_len, d_r, n, n_layers,
+                                               layers_per_element, d_p, s))) break;
+        if ((rc = check_hip(hipMemcpyAsync(h_probability, d_p, 9 * ne, hipMemcpyDeviceToHost, s), "d2h"))) break;
+        rc = check_hip(hipStreamSynchronize(s), "sync");
+    } while (0);
+    if (d_e) (void)hipFree(d_e);
+    if (d_rho) (void)hipFree(d_rho);
+    if (d_len) (void)hipFree(d_len);
+    if (d_r) (void)hipFree(d_r);
     if (d_p) (void)hipFree(d_p);
     return rc;
 }

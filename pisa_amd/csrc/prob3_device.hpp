@@ -1021,6 +1021,9 @@ __device__ __forceinline__ void su3_complete(mat3 &A) {
     }
 }
 
+__device__ __forceinline__ void height_averaged_probs(const mat3 &T, const mat3 &U, const double (&dm)[3][3],
+                                                      double dl_over_e, double (&P)[9]);   // (defined below)
+
 // Layer-matrix cache of the reference (numba_osc_kernels.py:230-249): layer i
 // re-uses the matrix of the LAST earlier layer j with |drho|<1e-5 and
 // |ddist|<1e-5.  Instead of storing up to 120 matrices per thread, the chain of
@@ -1047,10 +1050,12 @@ __device__ __forceinline__ void resolve_layer(const LayerFn &layer, int i, doubl
 // osc_probs_layers_kernel (numba_osc_kernels.py:121-345) for one element.
 // `layer(i, rho, dist)` yields the i-th layer of this element's path.
 // P receives P[init][final] (9 doubles).
-template <bool DECAY, class LayerFn>
+// AVG: the production-height average over a first-layer range of dl_over_e * energy (height_averaged_probs below);
+// a range of 0 takes the plain expression.
+template <bool DECAY, bool AVG = false, class LayerFn>
 __device__ __forceinline__ void propagate_element(const Prob3Side &S, const double (&dm)[3][3],
                                                   double energy, int n_layers,
-                                                  const LayerFn &layer, double (&P)[9]) {
+                                                  const LayerFn &layer, double (&P)[9], double dl_over_e = 0.0) {
     mat3 T;
     bool first = true;
 #pragma unroll
@@ -1073,6 +1078,10 @@ __device__ __forceinline__ void propagate_element(const Prob3Side &S, const doub
                 T = t2;
             }
         }
+    }
+    if (AVG && dl_over_e > 0.0) {
+        height_averaged_probs(T, S.U, dm, dl_over_e, P);
+        return;
     }
     // flavour basis (:326-328) and probabilities (:331-345)
     mat3 t2, Tf;
@@ -1313,6 +1322,47 @@ __device__ __forceinline__ void propagate_path_nested_lds(const Prob3Side &S, co
 #pragma unroll
         for (int j = 0; j < 3; j++)
             P[3 * i + j] = Tf.m[j][i].re * Tf.m[j][i].re + Tf.m[j][i].im * Tf.m[j][i].im;
+}
+
+// ------------------------------------------------- production-height average
+// The first traversed layer of a path is the atmosphere; its electron density is exactly 0 (Layers.setElecFrac), so
+// its Hamiltonian is diagonal in the mass basis, where the kernels hold the chain product T = A_last .. A_f: a first
+// layer of length Lbar + s multiplies column j of T by exp(-i dm_j0 2.534 s / E).  With W = U.T of the row whose first
+// layer has the length Lbar and D_j = W[b][j] conj(U[a][j]) (F[b][a] = sum_j D_j), the mean of |F[b][a]|^2 over s
+// uniform in [-dL/2, dL/2] (nusquids.py:83-88: uniform between the path lengths of the lowest and the highest
+// production height) is
+//     P_avg[a -> b] = sum_j |D_j|^2 + 2 sum_{j<k} sinc(x_jk) Re(D_j conj(D_k)),  x_jk = (dm_j0 - dm_k0) 2.534 (dL / E) / 2,
+// sinc(x) = sin(x) / x ("Production-height averaging").  A unit phase common to T drops out, so the
+// SU(3) form of the planned chain serves as it is.  No decay, no long-range potential: with either the first layer is
+// not diagonal in the mass basis (the entry points refuse the combination).
+__device__ __forceinline__ double sinc_phase(double x) {
+    double sn, cs;
+    sincos_phase(x, &sn, &cs);
+    return x == 0.0 ? 1.0 : sn / x;
+}
+
+// P[init][final] from the mass-basis chain product T of the midpoint row, the side's mixing matrix and dL / E
+__device__ __forceinline__ void height_averaged_probs(const mat3 &T, const mat3 &U, const double (&dm)[3][3],
+                                                      double dl_over_e, double (&P)[9]) {
+    mat3 W;
+    mat_mul(U, T, W);
+    const double hx = 0.5 * (2.534 * dl_over_e);
+    const double s01 = sinc_phase((dm[0][0] - dm[1][0]) * hx);
+    const double s02 = sinc_phase((dm[0][0] - dm[2][0]) * hx);
+    const double s12 = sinc_phase((dm[1][0] - dm[2][0]) * hx);
+#pragma unroll
+    for (int a = 0; a < 3; a++)
+#pragma unroll
+        for (int b = 0; b < 3; b++) {
+            const cplx d0 = cmul(W.m[b][0], cconj(U.m[a][0]));
+            const cplx d1 = cmul(W.m[b][1], cconj(U.m[a][1]));
+            const cplx d2 = cmul(W.m[b][2], cconj(U.m[a][2]));
+            const double diag = cabs2(d0) + cabs2(d1) + cabs2(d2);
+            const double r01 = d0.re * d1.re + d0.im * d1.im;   // Re(D_0 conj D_1)
+            const double r02 = d0.re * d2.re + d0.im * d2.im;
+            const double r12 = d1.re * d2.re + d1.im * d2.im;
+            P[3 * a + b] = diag + 2.0 * (s01 * r01 + s02 * r02 + s12 * r12);
+        }
 }
 
 // P[init][final] of one node -> full matrix and/or the compact gather tables

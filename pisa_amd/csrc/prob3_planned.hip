@@ -12,6 +12,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <cmath>
 #include <map>
 #include <type_traits>
 #include <vector>
@@ -60,11 +61,21 @@ constexpr int CHAIN_GROUPS_DEFAULT = 2;   // waves per row of the unpacked chain
 // address -- so both forms run the same instructions on the same numbers.
 struct ConstsByValue {
     Prob3Consts c;
+    static constexpr bool AVG = false;
     __device__ __forceinline__ const Prob3Consts &at(int) const { return c; }
 };
 struct ConstsByPointer {
     const Prob3Consts *__restrict__ p;
+    static constexpr bool AVG = false;
     __device__ __forceinline__ const Prob3Consts &at(int k) const { return p[k]; }
+};
+// The production-height average (prob3_device.hpp: height_averaged_probs) is a compile-time form of the chain kernel,
+// selected by the type of its first argument: the constants as above plus the plan's per-row range of the first
+// layer's length.  The plain forms keep their signature and their instructions; the terms kernel takes the base.
+template <class Base>
+struct WithAvgRange : Base {
+    const double *__restrict__ avg_range;   // [n_cz] km, >= 0
+    static constexpr bool AVG = true;
 };
 
 // host-mapped staging block -> device array of the points' constants (one small launch per batch)
@@ -194,11 +205,11 @@ __device__ unsigned long long g_chain_stamps[8 * 4096];
 #else
 #define CSTAMP(k) do {} while (0)
 #endif
-template <int G, int AMP>
+template <int G, int AMP, bool AVG>
 __device__ __forceinline__ void chain_tail(const Prob3Consts &c, const Prob3Side &S, mat3 &L, mat3 &R, mat3 &T, bool have_l, bool have_r,
                                            const double *s_part, int part_0, int lane, int Gr, int n_steps, int cnt, int mid,
                                            int e_major, int ie, int n_e, int n_cz, int jcz, int side, int n_points, int pt,
-                                           double *__restrict__ out, double2 *__restrict__ pepmu);
+                                           double *__restrict__ out, double2 *__restrict__ pepmu, double avg_dl_over_e);
 
 // A wave's partial product in LDS: [L | R][18][lane].  In the packed launch wave w owns slot (w + 3) & 3 -- the
 // partners of a leader at wave w are the next slots, and slot 3, wave 0's, has room for an L alone.
@@ -284,6 +295,7 @@ prob3_chain_kernel(const CS cs, int n_e, const int32_t *__restrict__ row_start,
                     int n_unique, const int32_t *__restrict__ slots, const int2 *__restrict__ lanes, int n_slots,
                     int n_points, int n_tiles) {
     auto MM = [](const mat3 &A_, const mat3 &B_, mat3 &C_) { mat_mul_fma(A_, B_, C_); };
+    static_assert(!CS::AVG || AMP == 1, "the production-height average: fused amplitudes without decay only");
     CSTAMP(0);
     // Packed launch: grid = (2 x points, slots): the (point, sign) index runs FASTEST and the slot -- a workgroup's
     // four wave records, which name its energy tile as well (prob3_plan.hpp) -- slowest.  The plan lists the slots
@@ -434,8 +446,10 @@ prob3_chain_kernel(const CS cs, int n_e, const int32_t *__restrict__ row_start,
     CSTAMP(3);
     if constexpr (!PACKED) {
         if (g != 0 || !live) return;
-        chain_tail<G, AMP>(c, S, L, R, T, have_l, have_r, s_part, part_0, lane, Gr, n_steps, cnt, mid, e_major, ie, n_e, n_cz, jl, side, n_points,
-                           pt, out, pepmu);
+        double avg = 0.0;
+        if constexpr (CS::AVG) avg = cs.avg_range[jl] * inv_e;
+        chain_tail<G, AMP, CS::AVG>(c, S, L, R, T, have_l, have_r, s_part, part_0, lane, Gr, n_steps, cnt, mid, e_major, ie, n_e, n_cz, jl, side,
+                                    n_points, pt, out, pepmu, avg);
     } else {
         // The join on two waves: the leader multiplies the R parts and T . R while the next wave of the row multiplies
         // the L parts; every wave of the workgroup meets at the second barrier (idle waves and the partners that have
@@ -461,18 +475,22 @@ prob3_chain_kernel(const CS cs, int n_e, const int32_t *__restrict__ row_start,
             T = t;
         }
         // joined already: the tail with one wave and no part of its own closes the chain
-        chain_tail<G, AMP>(c, S, L, R, T, false, false, s_part, 0, lane, 1, n_steps, cnt, mid, e_major, ie, n_e, n_cz, jl, side, n_points, pt, out,
-                           pepmu);
+        double avg = 0.0;
+        if constexpr (CS::AVG) avg = cs.avg_range[jl] * inv_e;
+        chain_tail<G, AMP, CS::AVG>(c, S, L, R, T, false, false, s_part, 0, lane, 1, n_steps, cnt, mid, e_major, ie, n_e, n_cz, jl, side, n_points, pt,
+                                    out, pepmu, avg);
     }
 }
 
 // the leader's part of the chain kernel: joins the partial products of its partner waves, closes the chain with the
 // mixing matrices and stores the node's probabilities
-template <int G, int AMP>
+// AVG: a row with a range of production heights (avg_dl_over_e = dL / E > 0) stores the average over the range of its
+// first layer's length instead of |F|^2; a row with range 0 takes the plain expression and gets the plain launch's bits
+template <int G, int AMP, bool AVG>
 __device__ __forceinline__ void chain_tail(const Prob3Consts &c, const Prob3Side &S, mat3 &L, mat3 &R, mat3 &T, bool have_l, bool have_r,
                                            const double *s_part, int part_0, int lane, int Gr, int n_steps, int cnt, int mid,
                                            int e_major, int ie, int n_e, int n_cz, int jcz, int side, int n_points, int pt,
-                                           double *__restrict__ out, double2 *__restrict__ pepmu) {
+                                           double *__restrict__ out, double2 *__restrict__ pepmu, double avg_dl_over_e) {
     auto MM = [](const mat3 &A_, const mat3 &B_, mat3 &C_) { mat_mul_fma(A_, B_, C_); };
     // wave 0: T_right = R_0 . R_1 .. (later groups further right), T_left = .. L_1 . L_0
     for (int h = 1; h < Gr; h++) {
@@ -509,15 +527,19 @@ __device__ __forceinline__ void chain_tail(const Prob3Consts &c, const Prob3Side
 #pragma unroll
             for (int j = 0; j < 3; j++) T.m[i][j] = cmake(0.0, 0.0);
     }
-    mat3 t2, Tf;
-    MM(T, S.Ud, t2);
-    MM(S.U, t2, Tf);
     double P[9];
+    if (AVG && avg_dl_over_e > 0.0) {
+        height_averaged_probs(T, S.U, c.dm, avg_dl_over_e, P);
+    } else {
+        mat3 t2, Tf;
+        MM(T, S.Ud, t2);
+        MM(S.U, t2, Tf);
 #pragma unroll
-    for (int i = 0; i < 3; i++)
+        for (int i = 0; i < 3; i++)
 #pragma unroll
-        for (int j = 0; j < 3; j++)
-            P[3 * i + j] = Tf.m[j][i].re * Tf.m[j][i].re + Tf.m[j][i].im * Tf.m[j][i].im;
+            for (int j = 0; j < 3; j++)
+                P[3 * i + j] = Tf.m[j][i].re * Tf.m[j][i].re + Tf.m[j][i].im * Tf.m[j][i].im;
+    }
     CSTAMP(5);
     int64_t node = e_major ? (int64_t)ie * n_cz + jcz : (int64_t)jcz * n_e + ie;
     if (n_points > 1) {
@@ -589,6 +611,9 @@ struct pisa_hip_grid_plan {
     // host copies for re-cutting the items when n_e changes
     int32_t *h_pair_u;
     int items_for_n_e;
+    // production-height average (pisa_hip_grid_plan_set_avg_range): the range of the first layer's length per row
+    double *d_avg_range;   // [n_cz] km, or null: the plain launch
+    int avg_positive;      // some row has a range > 0
 };
 
 static void free_launches(pisa_hip_grid_plan *p) {
@@ -606,7 +631,7 @@ PISA_API int pisa_hip_grid_plan_destroy(pisa_hip_grid_plan *p) {
     if (!p) return PISA_HIP_OK;
     void *ptrs[] = {p->d_item_u, p->d_item_p0, p->d_item_cnt, p->d_pair_dist, p->d_row_start,
                     p->d_row_cnt, p->d_row_pairs, p->d_rho, p->d_amp, p->d_pair_u, p->d_terms,
-                    p->d_chain_u, p->d_chain_dist};
+                    p->d_chain_u, p->d_chain_dist, p->d_avg_range};
     for (void *q : ptrs)
         if (q) (void)hipFree(q);
     if (p->d_consts) (void)hipFree(p->d_consts);
@@ -738,10 +763,11 @@ PISA_API int pisa_hip_grid_plan_create(const double *d_densities, const double *
 
 // the two launches of the fused-amplitude form for `n_points` parameter points whose constants `cs`
 // provides (by value: one point; by pointer: the plan's device array)
-template <class CS>
-static int launch_planned(const CS &cs, bool decay, int n_points, pisa_hip_grid_plan *plan, const double *d_energy,
-                          int32_t n_e, int32_t e_major, double *d_prob_nu, double *d_prob_nubar, double *d_pepmu,
-                          hipStream_t s) {
+// CC: CS itself, or WithAvgRange<CS> for the chain kernel of a plan with a range
+template <class CS, class CC>
+static int launch_planned_as(const CS &cs, const CC &cc, bool decay, int n_points, pisa_hip_grid_plan *plan, const double *d_energy,
+                             int32_t n_e, int32_t e_major, double *d_prob_nu, double *d_prob_nubar, double *d_pepmu,
+                             hipStream_t s) {
     const unsigned tiles = (unsigned)((n_e + 63) / 64);
     if (plan->chain_packed && plan->launch_n_e != n_e) {
         int rc = make_launch(plan, n_e);
@@ -765,7 +791,7 @@ static int launch_planned(const CS &cs, bool decay, int n_points, pisa_hip_grid_
                            plan->d_rho, plan->n_unique, plan->d_terms);
     PISA_CHECK_LAUNCH("prob3_terms_kernel");
     dim3 cblock(64 * CHAIN_GROUPS_DEFAULT), cgrid((unsigned)plan->n_cz, 2u * n_points, tiles);
-#define CHAIN(G, A) hipLaunchKernelGGL((prob3_chain_kernel<G, A, CS>), cgrid, cblock, 0, s, cs, (int)n_e, plan->d_row_start, \
+#define CHAIN(G, A) hipLaunchKernelGGL((prob3_chain_kernel<G, A, CC>), cgrid, cblock, 0, s, cc, (int)n_e, plan->d_row_start, \
                        plan->d_row_cnt, plan->d_row_pairs, plan->n_cz, plan->n_pairs, plan->d_terms,              \
                        (int)e_major, d_prob_nu, d_prob_nubar, (double2 *)d_pepmu, d_energy, plan->d_chain_u,      \
                        plan->d_chain_dist, plan->n_unique, plan->d_slots, (const int2 *)plan->d_lanes, plan->n_slots, \
@@ -776,11 +802,67 @@ static int launch_planned(const CS &cs, bool decay, int n_points, pisa_hip_grid_
         cblock = dim3(256);
         cgrid = dim3(2u * n_points, sy, (unsigned)((plan->n_slots + sy - 1) / (sy > 0 ? sy : 1)));
         if (plan->n_slots == 0) return PISA_HIP_OK;   // (no row: cannot happen, n_cz >= 1)
-        if (decay) CHAIN(0, 2); else CHAIN(0, 1);
-    } else if (decay) CHAIN(CHAIN_GROUPS_DEFAULT, 2);
+        if constexpr (CC::AVG) CHAIN(0, 1);
+        else if (decay) CHAIN(0, 2); else CHAIN(0, 1);
+    } else if constexpr (CC::AVG) CHAIN(CHAIN_GROUPS_DEFAULT, 1);
+    else if (decay) CHAIN(CHAIN_GROUPS_DEFAULT, 2);
     else CHAIN(CHAIN_GROUPS_DEFAULT, 1);
 #undef CHAIN
     PISA_CHECK_LAUNCH("prob3_chain_kernel");
+    return PISA_HIP_OK;
+}
+
+// a positive range needs a first layer that is diagonal in the mass basis: no decay, no long-range potential
+static bool avg_refused(const pisa_hip_grid_plan *plan, const pisa_hip_prob3_params *p) {
+    if (!plan->avg_positive) return false;
+    if (p->decay_flag == 1) return true;
+    for (int i = 0; i < 9; i++)
+        if (p->lri_pot[i] != 0.0) return true;
+    return false;
+}
+
+// A plan with a range launches the averaging form of the chain kernel (no decay: with decay only an all-zero range
+// gets here, and the plain launch is its definition); a plan without one launches exactly the plain kernels.
+template <class CS>
+static int launch_planned(const CS &cs, bool decay, int n_points, pisa_hip_grid_plan *plan, const double *d_energy,
+                          int32_t n_e, int32_t e_major, double *d_prob_nu, double *d_prob_nubar, double *d_pepmu,
+                          hipStream_t s) {
+    if (plan->d_avg_range && !decay) {
+        WithAvgRange<CS> cc{cs, plan->d_avg_range};
+        return launch_planned_as(cs, cc, decay, n_points, plan, d_energy, n_e, e_major, d_prob_nu, d_prob_nubar, d_pepmu, s);
+    }
+    return launch_planned_as(cs, cs, decay, n_points, plan, d_energy, n_e, e_major, d_prob_nu, d_prob_nubar, d_pepmu, s);
+}
+
+// The range of the first layer's length per coszen row, for the production-height average (nusquids.py:83-88, 573-606:
+// `prop_height_range`; formula in DESIGN.md §4, "Production-height averaging").  NULL clears it.
+PISA_API int pisa_hip_grid_plan_set_avg_range(pisa_hip_grid_plan *plan, const double *h_avg_range) {
+    if (!plan) return PISA_HIP_ERR_INVALID;
+    if (!h_avg_range) {
+        // (a launch that reads the array may still be queued)
+        if (plan->d_avg_range) {
+            PISA_TRY_HIP(hipDeviceSynchronize());
+            (void)hipFree(plan->d_avg_range);
+        }
+        plan->d_avg_range = nullptr;
+        plan->avg_positive = 0;
+        return PISA_HIP_OK;
+    }
+    const Prob3LayerPlan &lp = *plan->layers;
+    int positive = 0;
+    for (int j = 0; j < plan->n_cz; j++) {
+        const double r = h_avg_range[j];
+        if (!(r >= 0.0) || !std::isfinite(r)) return PISA_HIP_ERR_INVALID;
+        if (r == 0.0) continue;
+        // the first traversed layer must be free of electrons (the atmosphere)
+        if (lp.row_cnt[j] < 1 || lp.rho[lp.chain_u[lp.row_start[j]]] != 0.0) return PISA_HIP_ERR_INVALID;
+        positive = 1;
+    }
+    if (!plan->fused_amp) return PISA_HIP_ERR_INVALID;   // the stored-amplitude option has no averaging form
+    if (!plan->d_avg_range) PISA_TRY_HIP(hipMalloc(&plan->d_avg_range, (size_t)plan->n_cz * sizeof(double)));
+    else PISA_TRY_HIP(hipDeviceSynchronize());
+    PISA_TRY_HIP(hipMemcpy(plan->d_avg_range, h_avg_range, (size_t)plan->n_cz * sizeof(double), hipMemcpyHostToDevice));
+    plan->avg_positive = positive;
     return PISA_HIP_OK;
 }
 
@@ -793,6 +875,7 @@ PISA_API int pisa_hip_prob3_grid_planned(const pisa_hip_prob3_params *h_params,
     Prob3Consts &c = cv.c;
     int rc = make_consts(h_params, c);
     if (rc) return rc;
+    if (avg_refused(plan, h_params)) return PISA_HIP_ERR_INVALID;
     hipStream_t s = as_stream(stream);
     const unsigned tiles = (unsigned)((n_e + 63) / 64);
     const int fused_amp = plan->fused_amp;
@@ -839,6 +922,8 @@ PISA_API int pisa_hip_prob3_grid_planned_multi(const pisa_hip_prob3_params *h_pa
         n_points > PISA_HIP_MAX_POINTS)
         return PISA_HIP_ERR_INVALID;
     if (!plan->fused_amp) return PISA_HIP_ERR_INVALID;   // the stored-amplitude option has no batch form
+    for (int k = 0; k < n_points; k++)
+        if (avg_refused(plan, h_params + k)) return PISA_HIP_ERR_INVALID;
     hipStream_t s = as_stream(stream);
     if (!plan->d_consts) {
         PISA_TRY_HIP(hipMalloc(&plan->d_consts, sizeof(Prob3Consts) * PISA_HIP_MAX_POINTS));

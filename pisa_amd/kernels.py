@@ -60,14 +60,22 @@ def _status_buffer():
 
 
 # ---------------------------------------------------------------- prob3
-def propagate_array(params, nubar, energy, densities, distances, out=None):
-    """`propagate_array` gufunc (numba_osc_hostfuncs.py:56-70)."""
+def propagate_array(params, nubar, energy, densities, distances, out=None, avg_range=None):
+    """`propagate_array` gufunc (numba_osc_hostfuncs.py:56-70).  `avg_range` (device tensor, km: one value per
+    element with per-element rows, one value with a shared row): the production-height average over that range of
+    the first traversed layer's length (`pisa_hip_propagate_array_avg`); None is the plain call."""
     lib = _lib.lib()
     n = energy.numel()
     per_elem = 1 if densities.dim() == 2 else 0
     n_layers = densities.shape[-1]
     if out is None:
         out = torch.empty((n, 3, 3), dtype=F8, device=energy.device)
+    if avg_range is not None:
+        assert avg_range.dtype == F8 and avg_range.numel() == (n if per_elem else 1), "one range per row of layers"
+        _lib.check(lib.pisa_hip_propagate_array_avg(
+            C.byref(params), int(nubar), _ptr(energy), _ptr(densities), _ptr(distances), _ptr(avg_range), n,
+            n_layers, per_elem, _ptr(out), _stream()))
+        return out
     _lib.check(lib.pisa_hip_propagate_array(
         C.byref(params), int(nubar), _ptr(energy), _ptr(densities), _ptr(distances), n,
         n_layers, per_elem, _ptr(out), _stream()))
@@ -96,9 +104,10 @@ def prob3_grid(params, energy, densities, distances, e_major=True, out_nu=None, 
 
 class GridPlan:
     """Per-layer-table plan of the two-stage grid kernels (`pisa_hip_grid_plan`):
-    cache matches resolved per coszen row + list of distinct shell densities."""
+    cache matches resolved per coszen row + list of distinct shell densities.  `avg_range` (host array [n_cz], km):
+    the range of the first layer's length per row for the production-height average (`set_avg_range`)."""
 
-    def __init__(self, densities, distances):
+    def __init__(self, densities, distances, avg_range=None):
         lib = _lib.lib()
         self.n_cz, self.n_layers = densities.shape
         h = C.c_void_p()
@@ -106,6 +115,22 @@ class GridPlan:
         _lib.check(lib.pisa_hip_grid_plan_create(_ptr(densities), _ptr(distances), self.n_cz,
                                                  self.n_layers, C.byref(h)))
         self.handle = h
+        self.avg_range = None
+        if avg_range is not None:
+            self.set_avg_range(avg_range)
+
+    def set_avg_range(self, avg_range):
+        """attach the per-row range (None clears it): every planned evaluation on this plan then returns the
+        production-height average on the rows with a positive range (`pisa_hip_grid_plan_set_avg_range`)"""
+        if avg_range is None:
+            _lib.check(_lib.lib().pisa_hip_grid_plan_set_avg_range(self.handle, None))
+            self.avg_range = None
+            return
+        r = np.ascontiguousarray(avg_range, dtype=np.float64).ravel()
+        if r.size != self.n_cz:
+            raise ValueError("avg_range needs one value per coszen row (%d), got %d" % (self.n_cz, r.size))
+        _lib.check(_lib.lib().pisa_hip_grid_plan_set_avg_range(self.handle, r.ctypes.data))
+        self.avg_range = r
 
     def __del__(self):
         try:

@@ -131,6 +131,45 @@ class Layers:
             self._distance = self._dev[2].cpu().numpy()
         return self._distance
 
+    def _rows_at(self, cz, prop_height):
+        """(densities, distances) of `cz` for another production height, same Earth and electron fractions"""
+        other = Layers(self.prem, self.detector_depth, prop_height)
+        if hasattr(self, "YeFrac"):
+            other.setElecFrac(*self.YeFrac)
+        other.calcLayers(cz)
+        return other.device_arrays[1:]
+
+    def height_average_rows(self, cz, prop_height_range, rows_at=None):
+        """The rows of the production-height average (nusquids.py:576-606 builds the same two extra `Layers`):
+        production height uniform in prop_height -+ prop_height_range / 2, projected onto the neutrino's direction.
+
+        Returns (densities, distances, avg_range): the nominal rows of `cz` with the first traversed layer (the
+        atmosphere) set to Lbar = (L_min + L_max) / 2, and dL = L_max - L_min per row, L_min / L_max being that
+        layer's lengths at the lowest / highest production height.  Every other layer is the nominal row's (it does
+        not depend on the production height).  `rows_at(cz, height)` -> (densities, distances) replaces the device
+        computation (arrays of either numpy or torch)."""
+        self._need_model("average over the production height")
+        rng = float(prop_height_range)
+        if not rng > 0.0:
+            raise ValueError("prop_height_range must be positive, got %r km" % (prop_height_range,))
+        if rng > 2.0 * self.prop_height:
+            raise ValueError("prop_height_range %g km reaches below the surface: it may be at most twice prop_height "
+                             "(%g km)" % (rng, self.prop_height))
+        rows_at = rows_at or self._rows_at
+        dens, dist = rows_at(cz, self.prop_height)
+        _, d_lo = rows_at(cz, self.prop_height - 0.5 * rng)
+        _, d_hi = rows_at(cz, self.prop_height + 0.5 * rng)
+        if isinstance(dist, np.ndarray):
+            first, rows, dist = np.argmax(dist > 0.0, axis=1), np.arange(len(dist)), dist.copy()
+        else:
+            import torch
+
+            first = (dist > 0.0).to(torch.int8).argmax(dim=1)
+            rows, dist = torch.arange(dist.shape[0], device=dist.device), dist.clone()
+        l_min, l_max = d_lo[rows, first], d_hi[rows, first]
+        dist[rows, first] = 0.5 * (l_min + l_max)
+        return dens, dist, l_max - l_min
+
     def calcPathLength(self, cz):
         """Vacuum path length through an Earth-sized sphere (layers.py:384-405)."""
         r_prop = self.r_detector + self.detector_depth + self.prop_height

@@ -13,17 +13,23 @@ potential / decay / LRI matrices (prob3.py:476-578).  Device side:
 * any other binned calc_mode: generic `pisa_hip_propagate_array` with per-node
   layer rows.
 
+`prop_height_range` (a length; with `apply_height_avg_below_hor`, the names and meanings of the reference's nuSQuIDS
+stage, pisa/stages/osc/nusquids.py:83-104) averages the probabilities over a production height uniform in
+prop_height -+ range / 2, in closed form inside the prob3 kernels ("Production-height averaging"); binned
+calc modes without decay or LRI.
+
 `apply_function` (prob3.py:611-622) multiplies the weights by
 flux_e*prob_e + flux_mu*prob_mu; in an event representation this is recorded
 as a deferred operation and fused with aeff + hist by `utils.hist`.
 """
 import numpy as np
+import torch
 
 from pisa_amd import CTYPE, FTYPE, _lib
 from pisa_amd import kernels as K
 from pisa_amd.core.binning import MultiDimBinning
 from pisa_amd.core.stage import Stage
-from pisa_amd.core.units import ureg
+from pisa_amd.core.units import Quantity, ureg
 from pisa_amd.stages import deferred
 from pisa_amd.stages.osc.decay_params import DecayParams
 from pisa_amd.stages.osc.layers import Layers
@@ -46,7 +52,8 @@ NUBAR = ["nuebar_cc", "numubar_cc", "nutaubar_cc", "nuebar_nc", "numubar_nc", "n
 
 class prob3(Stage):  # pylint: disable=invalid-name
     def __init__(self, include_nlo=False, nsi_type=None, reparam_mix_matrix=False,
-                 neutrino_decay=False, tomography_type=None, lri_type=None, **std_kwargs):
+                 neutrino_decay=False, tomography_type=None, lri_type=None, prop_height_range=None,
+                 apply_height_avg_below_hor=True, **std_kwargs):
         expected_params = ("detector_depth", "earth_model", "prop_height", "YeI", "YeO", "YeM",
                            "theta12", "theta13", "theta23", "deltam21", "deltam31", "deltacp")
         expected_container_keys = ("true_energy", "true_coszen", "nubar", "flav", "nu_flux", "weights")
@@ -86,6 +93,29 @@ class prob3(Stage):  # pylint: disable=invalid-name
                                                               "middlemantle_density_scale")}[tomography_type]
         self.tomography_type = tomography_type
         self.tomography_params = None
+        # production-height average (nusquids.py:83-104, 346-353): None, or the range in km
+        if prop_height_range is not None:
+            if isinstance(prop_height_range, str):
+                from pisa_amd.core.config_parser import parse_quantity
+
+                q = parse_quantity(prop_height_range)
+                prop_height_range = Quantity(q.nominal_value, q.units)
+            if not hasattr(prop_height_range, "m_as"):
+                raise ValueError("prop_height_range needs units of length, got %r" % (prop_height_range,))
+            prop_height_range = float(prop_height_range.m_as("km"))
+            if not prop_height_range > 0.0:
+                raise ValueError("prop_height_range must be positive, got %g km" % prop_height_range)
+            if neutrino_decay:
+                raise ValueError("prop_height_range together with neutrino_decay=True is not supported: with decay "
+                                 "the atmosphere layer is not diagonal in the mass basis")
+            if lri_type is not None:
+                raise ValueError("prop_height_range together with lri_type=%r is not supported: with a long-range "
+                                 "potential the atmosphere layer is not diagonal in the mass basis" % lri_type)
+            if std_kwargs.get("calc_mode") == "events":
+                raise ValueError('prop_height_range together with calc_mode="events" is not supported: the '
+                                 "event-by-event kernels have no production-height average")
+        self.prop_height_range = prop_height_range
+        self.apply_height_avg_below_hor = bool(apply_height_avg_below_hor)
         super().__init__(expected_params=expected_params,
                          expected_container_keys=expected_container_keys, **std_kwargs)
         self.layers = self.osc_params = self.nsi_params = self.decay_params = self.lri_params = None
@@ -138,18 +168,36 @@ class prob3(Stage):  # pylint: disable=invalid-name
         self._calc_layers()
         self.data["_prob3_stage"] = self  # lets utils.hist find the gather tables
 
-    def _calc_layers(self):
-        if self.grid is not None:
-            self.layers.calcLayers(self.grid["coszen"])
+    def _rows(self, coszen):
+        """(densities, distances, avg_range or None) of `coszen`: the nominal rows, or with `prop_height_range` the
+        rows and ranges of the production-height average (`Layers.height_average_rows`)"""
+        if self.prop_height_range is None:
+            self.layers.calcLayers(coszen)
             _, dens, dist = self.layers.device_arrays
-            self.grid["plan"] = K.GridPlan(dens, dist)
+            return dens, dist, None
+        dens, dist, rng = self.layers.height_average_rows(coszen, self.prop_height_range)
+        if not self.apply_height_avg_below_hor:
+            # up-going rows keep the nominal first-layer length and are not averaged (nusquids.py:96-103)
+            self.layers.calcLayers(coszen)
+            up = (coszen < 0)[:, None]
+            dist = torch.where(up, self.layers.device_arrays[2], dist)
+            rng = torch.where(up[:, 0], torch.zeros_like(rng), rng)
+        return dens, dist.contiguous(), rng.contiguous()
+
+    def _calc_layers(self):
+        if self.prop_height_range is not None and self.calc_mode == "events":
+            raise ValueError('prop_height_range together with calc_mode="events" is not supported')
+        if self.grid is not None:
+            dens, dist, rng = self._rows(self.grid["coszen"])
+            self.grid["plan"] = K.GridPlan(dens, dist, avg_range=None if rng is None else rng.cpu().numpy())
             self.grid["rows"] = (dens, dist)
         elif self.calc_mode != "events":
             for container in self.data:
-                self.layers.calcLayers(container.device("true_coszen"))
-                _, dens, dist = self.layers.device_arrays
+                dens, dist, rng = self._rows(container.device("true_coszen"))
                 container["densities"] = dens
                 container["distances"] = dist
+                if rng is not None:
+                    container["avg_ranges"] = rng
 
     # ---------------------------------------------------------------- compute
     def _matrices(self):
@@ -296,7 +344,9 @@ class prob3(Stage):  # pylint: disable=invalid-name
                                        container.device("true_coszen"))
                 else:
                     P = K.propagate_array(params, container["nubar"], container.device("true_energy"),
-                                          container.device("densities"), container.device("distances"))
+                                          container.device("densities"), container.device("distances"),
+                                          avg_range=None if self.prop_height_range is None
+                                          else container.device("avg_ranges"))
                 container["probability"] = P
                 container["prob_e"] = K.fill_probs(P, 0, container["flav"])   # prob3.py:593-608
                 container["prob_mu"] = K.fill_probs(P, 1, container["flav"])
